@@ -11,19 +11,23 @@ A "step" is one pass of the hot path over one batch of synthetic input already r
           20 000 genes as 10 blocks of 50 000, ensize.K = 5, p = 474 (per block: projection, 125 base-clustering tasks, 25 wMetaC, sMetaC;
           then the cross-block sMetaC on the blocks' centroid tables).
   N = 1, --config cfg2: BASELINE.json configs[1]: one SHARP() call on 50 000 cells x 20 000 genes, ensize.K = 15 (SHARP_large: projectors,
-          RP matmul, 375 base-clustering tasks, 25 wMetaC, sMetaC).  (The default run times it too: "other_configs.cfg2".)
+          RP matmul, 375 base-clustering tasks, 25 wMetaC, sMetaC).  (A --full run times it too: "other_configs.cfg2".)
   N > 1, and N = 1 with --config cfg4: BASELINE.json configs[3]: SHARP_unlimited on 1.3 M cells x 27 000 genes, ensize.K = 5, as
           its EIGHT blocks of 162 500 cells whatever N is, block b on GPU b mod N (one per GPU at N = 8; all eight one after the other
           on the one GPU at N = 1: 140 GB of X), p = 508 from the global count: the total problem and its labels are the same for
-          every N ("scaling": "strong"), so `--gpus 1 --config cfg4` is the N = 1 point of the curve the N > 1 runs draw (the default
+          every N ("scaling": "strong"), so `--gpus 1 --config cfg4` is the N = 1 point of the curve the N > 1 runs draw (a --full
           run reports it under "other_configs.cfg4_one_gpu").  The only data-path collective is the all-gather of the per-block
           centroid table before the final sMetaC (sharp_amd/dist.py).
-`ms_per_step` is the step WITHOUT the view outputs; `ms_per_step_forview` the same step with the reference's default `forview = TRUE` /
-`viewflag = TRUE` outputs requested (viE and x0: R/SHARP.R:46,717-731,844; R/SHARP_unlimited.R:214-232) and brought to the host.
-The JSON carries `roofline` for the RP matmul stage (rp_pc_kernel, rp3.hip; HBM-bound: X is read once for all K projectors)
-from HIP events on the library's streams inside the timed region, `roofline.traffic` from two rocprofv3 --pmc child passes over the same
-stage, the same stage at the other shapes and on other value kinds (`roofline.by_config`), and `cpu_baseline`: the fp64 CPU oracle (a
-port of the reference's R path, not R itself) timed on the host cores on a bounded sample, with its per-stage seconds."""
+`ms_per_step` is the step WITHOUT the view outputs.  The JSON carries `roofline` for the RP matmul stage (rp_pc_kernel, rp3.hip; HBM-bound:
+X is read once for all K projectors) from HIP events on the library's streams inside the timed region.
+`--dump-outputs DIR` writes what the last timed step returned (the labels, the number of clusters, the reduced dimension) as float64 .npy
+files; the synthetic input depends on the arguments only, so two builds can be compared output for output.
+A plain run stops there.  `--full` measures, after the timed region, `ms_per_step_forview` (the same step with the reference's default
+`forview = TRUE` / `viewflag = TRUE` outputs requested: viE and x0, R/SHARP.R:46,717-731,844; R/SHARP_unlimited.R:214-232, brought to the
+host), the cfg2 attribution step, `roofline.traffic` from two rocprofv3 --pmc child passes over the same stage (a plain run names the
+committed figure instead), the other configurations and the same stage at the other shapes and on other value kinds
+(`other_configs`, `roofline.by_config`), and `cpu_baseline`: the fp64 CPU oracle (a port of the reference's R path, not R itself) timed
+on the host cores on a bounded sample, with its per-stage seconds and the GPU-vs-oracle `parity`."""
 import argparse
 import ctypes as C
 import json
@@ -166,14 +170,22 @@ def main():
     ap.add_argument("--config", choices=["cfg2", "cfg2_ch", "cfg3", "cfg4"], default="cfg3", help="N = 1 workload (N > 1 always runs cfg4)")
     ap.add_argument("--cells", type=int, default=0, help="override the TOTAL number of cells of the workload (tests)")
     ap.add_argument("--genes", type=int, default=0, help="override the number of genes (tests)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other configurations / shapes after the timed region")
-    ap.add_argument("--no-traffic", action="store_true", help="do not measure roofline.traffic under rocprofv3 (two child processes after the timed region)")
-    ap.add_argument("--no-forview", action="store_true", help="skip ms_per_step_forview")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure everything beyond the headline: ms_per_step_forview, the cfg2 attribution step, "
+                         "roofline.traffic, the other configurations / shapes and the CPU baseline with its parity (the --no-* options thin this out)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (labels, cluster count, reduced dimension) as DIR/<name>.npy, float64 "
+                         "(bench_outputs/ in the repository is ignored by git)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip cpu_baseline and parity")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the other configurations / shapes after the timed region")
+    ap.add_argument("--no-traffic", action="store_true", help="(--full) do not measure roofline.traffic under rocprofv3 (two child processes after the timed region)")
+    ap.add_argument("--no-forview", action="store_true", help="(--full) skip ms_per_step_forview")
     ap.add_argument("--traffic-child", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.traffic_child:
         return traffic_child(args.traffic_child)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np
     import torch
@@ -255,6 +267,7 @@ def main():
             out, nfin, p = sdist.unlimited_sharded(blocks, mine, ncb, run_block, dev.unlimited_merge, device=xdev)
             proj.close()
             state["p"], state["pred"], state["n_clusters"] = p, np.concatenate([out[b] for b in mine]), nfin
+            state["pred_by_block"] = {int(b): out[b] for b in mine}
             state["crc"] = {int(b): zlib.crc32(np.ascontiguousarray(out[b], np.int32).tobytes()) for b in mine}
         workload = ("SHARP_unlimited on synthetic %d cells x %d genes as %d blocks of %d cells, block b on GPU b mod %d, ensize.K=%d, rN.seed=%d"
                     % (n_total, m, B, ncb[0], world, K, RN_SEED))
@@ -314,10 +327,24 @@ def main():
         for d in parts:
             merged.update(d)
         crc_by_block = [merged[b] for b in sorted(merged)]
+    if args.dump_outputs:
+        # what the LAST timed step returned, before anything after the timed region runs another step
+        pred = state["pred"]
+        if sharded:
+            parts = [state["pred_by_block"]]
+            if world > 1:
+                parts = [None] * world
+                dist.all_gather_object(parts, state["pred_by_block"])
+            merged = {}
+            for d in parts:
+                merged.update(d)
+            pred = np.concatenate([merged[b] for b in sorted(merged)])        # global block order: the same array for every N
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"pred_clusters": pred, "n_pred_clusters": state["n_clusters"], "reduced_dim": state["p"]})
 
     # ---- the same step with the reference's default view outputs requested (outside the headline's timed region, same contract)
     ms_forview = None
-    if not args.no_forview:
+    if args.full and not args.no_forview:
         fsteps = max(2, min(args.steps, 3))
         step(view=True)                                    # two warm-up calls: the view projector and its buffers exist once per tail-helper slot,
         step(view=True)                                    # and which helper takes which block's tail is decided at run time
@@ -337,7 +364,7 @@ def main():
     prof = prof_timed
     attribution_note = ("per-kernel HIP-event times summed over the timed steps / steps; the blocks' kernels overlap (pipelined chunks, tail helpers), "
                         "so these add up to more than ms_per_step")
-    if tag in ("cfg2", "cfg2_ch") and world == 1:
+    if args.full and tag in ("cfg2", "cfg2_ch") and world == 1:
         # Attribution pass, outside the timed region: in the timed steps the two chunks of base-clustering tasks are in flight together
         # (SHARP_HC_PIPE) and a chunk of 194 tasks or more runs as two ranges on two streams, so the per-kernel event times overlap and
         # kernels sharing the chip run slower than alone; one more step with one chunk and one range at a time gives each kernel's own time.
@@ -364,7 +391,7 @@ def main():
         if st:
             traffic, tsrc = None, None
             shape_key = {"cfg2": "cfg2", "cfg2_ch": "cfg2", "cfg3": "cfg3", "cfg4": "cfg4"}[tag]
-            if full_size and world == 1 and not args.no_traffic:
+            if args.full and full_size and world == 1 and not args.no_traffic:
                 del blocks                                       # (the child processes need the HBM; the extras regenerate what they use)
                 if tag in ("cfg2", "cfg2_ch"):
                     del dX
@@ -418,9 +445,9 @@ def main():
         lv = level_rules(prof_timed, args.steps)
         if lv:
             result["level_rule_per_step"] = lv
-        if tag in ("cfg2", "cfg2_ch"):
+        if prof is not prof_timed:                           # (the one-step attribution pass of a --full cfg2 run)
             result["other_kernels"] = other_kernels(prof, n_total, K, p)
-        if world == 1 and full_size:
+        if args.full and world == 1 and full_size:
             if blocks is not None:
                 del blocks
                 if tag in ("cfg2", "cfg2_ch"):
@@ -445,6 +472,26 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_MAX_VALUES = 3 * 1024 * 1024      # float64 values per dumped array (24 MB; 48 MB with its sample positions): the dump stays under 64 MB
+DUMP_SAMPLE_SEED = 20261003
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as d/<name>.npy in float64 (labels and counts are exact there).  An array longer than DUMP_MAX_VALUES
+    is replaced by the same seeded sample of its positions on every run, the positions in d/<name>_sample_index.npy."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > DUMP_MAX_VALUES:
+            a = a.reshape(-1)
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, DUMP_MAX_VALUES, replace=False))
+            np.save(os.path.join(d, name + "_sample_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def host_cores_available():
@@ -572,7 +619,7 @@ def timed_calls(Bn, fn, calls, warm=1):
 
 
 def extra_configs(Bn, headline_tag):
-    """After the timed region of the default run: the other BASELINE.json configurations a single GPU holds, each under its own warm-up + timed
+    """After the timed region of a --full run: the other BASELINE.json configurations a single GPU holds, each under its own warm-up + timed
     calls, and the RP matmul stage at every block shape and on other kinds of values, so that the driver's box produces these numbers too."""
     np, torch, dev, lib, sa, ARI = Bn.np, Bn.torch, Bn.dev, Bn.lib, Bn.sa, Bn.ARI
     out, by_cfg = {}, {}

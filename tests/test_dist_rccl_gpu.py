@@ -6,12 +6,25 @@ import os
 import socket
 import subprocess
 import sys
+import zlib
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _give_back_gpu_memory():
+    """the bench is a process of its own on the same GPU: this one gives back what earlier tests left in its worker / helper slots and in
+    torch's cache first"""
+    import sharp_amd
+    import torch
+
+    if torch.cuda.is_initialized():
+        sharp_amd.init(0)
+        assert sharp_amd.lib().sharp_trim() == 0
+        torch.cuda.empty_cache()
 
 
 def _free_port():
@@ -43,7 +56,8 @@ def test_bench_two_ranks_sharing_the_gpu(tmp_path, cells, genes, nblocks):
     env = dict(os.environ, SHARP_BENCH_SHARE_GPU="1", SHARP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--cells", str(cells), "--genes", str(genes)]   # N > 1 runs cfg4 (1.3 M x 27 000 as eight blocks, block b on GPU b mod N), here shrunk
+           "--cells", str(cells), "--genes", str(genes),   # N > 1 runs cfg4 (1.3 M x 27 000 as eight blocks, block b on GPU b mod N), here shrunk
+           "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, env=env, timeout=900, capture_output=True, text=True, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -58,26 +72,25 @@ def test_bench_two_ranks_sharing_the_gpu(tmp_path, cells, genes, nblocks):
     assert d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] < 1
     assert d["ari_vs_planted_truth"] > 0.85                        # (what the algorithm finds on this data; parity is tested elsewhere)
     assert len(d["labels_crc32_by_block"]) == nblocks and "cfg4_one_gpu" in d["scaling_curve"]["n1_point"]
+    # --dump-outputs: rank 0 writes every rank's labels in global block order, block for block the labels the checksums were taken of
+    pred = np.load(tmp_path / "dump" / "pred_clusters.npy")
+    assert pred.dtype == np.float64 and pred.shape == (cells,)
+    nb = cells // nblocks
+    crc = [zlib.crc32(pred[b * nb:(b + 1) * nb].astype(np.int32).tobytes()) for b in range(nblocks)]
+    assert crc == d["labels_crc32_by_block"]
+    assert int(np.load(tmp_path / "dump" / "n_pred_clusters.npy")) == d["clusters_found"]
 
 
 def test_bench_default_line_names_cfg3_with_forview_roofline_and_cpu_baseline():
-    """`python bench.py` (N = 1): the headline is BASELINE.json configs[2], the largest single-GPU configuration, under the steps / warm-up
+    """`python bench.py --full` (N = 1): the headline is BASELINE.json configs[2], the largest single-GPU configuration, under the steps / warm-up
     contract, with the forview step, the RP-stage roofline of its block shape (traffic measured in the run), the CPU baseline with its
     per-stage seconds and the GPU-vs-oracle ARI of every configuration's sample.  (--no-extra: the other configurations' timings are the
-    driver's bench run; tools/dryrun_8ranks.sh and the two-rank test above cover N > 1.)"""
+    full bench run's; tools/dryrun_8ranks.sh and the two-rank test above cover N > 1.)"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    # the bench is a process of its own on the same GPU: this one gives back what earlier tests left in its worker / helper slots and in
-    # torch's cache first
-    import sharp_amd
-    import torch
-
-    if torch.cuda.is_initialized():
-        sharp_amd.init(0)
-        assert sharp_amd.lib().sharp_trim() == 0
-        torch.cuda.empty_cache()
-    # (--no-traffic: the two rocprofv3 child passes that measure roofline.traffic are the driver's bench run's; here the committed figure is named)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-extra", "--no-traffic"], env=env, timeout=1200,
-                       capture_output=True, text=True, cwd=ROOT)
+    _give_back_gpu_memory()
+    # (--no-traffic: the two rocprofv3 child passes that measure roofline.traffic are the full bench run's; here the committed figure is named)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-extra", "--no-traffic"], env=env,
+                       timeout=1200, capture_output=True, text=True, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -103,3 +116,40 @@ def test_bench_default_line_names_cfg3_with_forview_roofline_and_cpu_baseline():
     for k in ("cfg2", "cfg2_ch", "cfg3", "cfg4"):
         assert d["parity"][k]["ari_gpu_vs_oracle_on_sample"] >= 0.99, (k, d["parity"][k])
     assert d["parity"]["ari_gpu_vs_oracle_on_sample"] == d["parity"]["cfg3"]["ari_gpu_vs_oracle_on_sample"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """`python bench.py` without --full: the headline only (no side measurement after the timed region), exactly --steps timed steps, and
+    --dump-outputs writes the labels of the last timed step -- the labels the line's ARI was computed from -- identically on a second run."""
+    from sharp_amd import device as dev
+    from sharp_amd.api import ARI
+
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    _give_back_gpu_memory()
+    cells, genes = 60000, 3000                     # cfg3 shrunk: ten blocks of 6000 cells
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--cells", str(cells),
+                            "--genes", str(genes), "--dump-outputs", str(tmp_path / run)], env=env, timeout=600, capture_output=True, text=True, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    d = lines[0]
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "cells/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["value"] == pytest.approx(cells / (d["ms_per_step"] * 1e-3), rel=1e-3)
+    assert d["consistency"]["ms_per_step_x_steps_s"] == pytest.approx(d["consistency"]["timed_region_s"], rel=1e-2)
+    assert d["ms_per_step_forview"] is None and not {"cpu_baseline", "parity", "other_configs"} & set(d)
+    dumps = {}
+    for run in ("a", "b"):
+        dumps[run] = {name: np.load(tmp_path / run / (name + ".npy")) for name in ("pred_clusters", "n_pred_clusters", "reduced_dim")}
+        assert sorted(os.listdir(tmp_path / run)) == ["n_pred_clusters.npy", "pred_clusters.npy", "reduced_dim.npy"]
+    a = dumps["a"]
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["pred_clusters"].shape == (cells,) and np.array_equal(a["pred_clusters"], np.round(a["pred_clusters"]))
+    assert int(a["n_pred_clusters"]) == d["clusters_found"] and int(a["reduced_dim"]) == d["config"]["reduced_dim"]
+    assert len(np.unique(a["pred_clusters"])) <= d["clusters_found"]
+    truth = dev.synth_labels(20261003, 0, cells, 12)
+    assert round(float(ARI(truth, a["pred_clusters"].astype(np.int32))["HA"]), 4) == d["ari_vs_planted_truth"]
+    for name, v in a.items():
+        assert np.array_equal(v, dumps["b"][name]), name

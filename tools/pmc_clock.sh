@@ -6,7 +6,7 @@ PY=$(python3 -c 'import os,sys;print(os.path.realpath(sys.executable))')
 # kernel trace of the same run.  Short kernels read high: the busy window includes the dispatch overhead, the duration does not.
 REPO=$(pwd); OUT=$REPO/gpurun_out; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-SHARP_HC_PIPE=0 timeout -k 10 400 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pmc_clock -- "$PY" $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extra > $OUT/pmc_clock.log 2>&1
+SHARP_HC_PIPE=0 timeout -k 10 400 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pmc_clock -- "$PY" $REPO/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-extra > $OUT/pmc_clock.log 2>&1
 cd $REPO
 python3 - <<'PY'
 import csv, glob, collections
