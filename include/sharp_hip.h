@@ -365,6 +365,28 @@ int sharp_marker_genes_blocks_dev(const float *const *dX_blocks, const long long
 int sharp_marker_genes_blocks_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb,
                                   int nblocks, int m, const int *label, int n_cluster, double theta, int ng, double *out);
 
+/* ---- Rtsne for visualization_SHARP (R/visualization_SHARP.R:94: Rtsne(x1, check_duplicates = FALSE, pca = flag, ...)) ---------
+ * Exact t-SNE: PCA / normalisation of the input, exact k-NN (K = floor(3 perplexity), perplexity <= 85), per-row
+ * perplexity calibration, P = (P_cond + P_cond^T) / sum, then max_iter steps of bhtsne's optimiser with the repulsion computed EXACTLY
+ * (the theta -> 0 limit of Barnes-Hut; theta is accepted and unused): O(n^2) work per iteration.
+ * X: n rows of d values, row i at X + i * ld (R's t(X), column-major).  Y (out) and Y_init (NULL: 1e-4 N(0, 1) from R's set.seed(seed)
+ * stream): n x dims row-major, dims 1..3.  itercosts (NULL or one slot per iteration iter > 0 with iter % 50 == 0, plus the last
+ * iteration): the KL divergence there; costs (NULL or n): the per-point KL at the end.  Bitwise reproducible on one GPU. */
+int sharp_tsne(const double *X, long long n, int d, long long ld, int dims, int initial_dims, int pca, int pca_center, int pca_scale,
+               int normalize, int check_duplicates, double perplexity, double theta, int max_iter, int stop_lying_iter, int mom_switch_iter,
+               double momentum, double final_momentum, double eta, double exaggeration, const double *Y_init, double seed, double *Y,
+               double *itercosts, double *costs);
+/* Its stages one at a time (tests, tools).  _prepare: out (n x d) receives n x *d_out (the PCA / normalised input).  _knn: the K nearest
+ * rows of every row (self excluded, ties by the lower index), sorted; dist = sum (x_i - x_j)^2; idx 0-based.  _affinities: P in CSR
+ * (row_ptr n + 1, col / val with room for cap >= 2 n floor(3 perplexity) entries; *nnz out) for the already prepared X.  _gradient: dY
+ * (n x dims) at Y for that P. */
+int sharp_tsne_prepare(const double *X, long long n, int d, long long ld, int pca, int initial_dims, int pca_center, int pca_scale,
+                       int normalize, double *out, int *d_out);
+int sharp_tsne_knn(const double *X, long long n, int d, long long ld, int K, int *idx, double *dist);
+int sharp_tsne_affinities(const double *X, long long n, int d, long long ld, double perplexity, long long cap, long long *row_ptr, int *col,
+                          double *val, long long *nnz);
+int sharp_tsne_gradient(const long long *row_ptr, const int *col, const double *val, long long n, int dims, const double *Y, double *dY);
+
 /* ---- synthetic inputs (bench / tests; not part of the reference) ------------ */
 /* Counter-based generator, value = f(seed, gene, cell): bit-identical to
  * oracle_synth_value().  Fills dX (fp32, m x ncell column-major, leading dim ld). */
@@ -453,6 +475,12 @@ void sharp_C_unlimited_merge(double *means, double *counts, int *nC, int *p, dou
                              int *final_id, int *n_final, int *status);
 /* R/get_marker_genes.R:120-152 */
 void sharp_C_marker_genes(double *X, int *m, double *n, int *label, int *n_cluster, double *theta, int *ng, double *out, int *status);
+/* R/visualization_SHARP.R:94 (Rtsne): sharp_tsne with X = as.double(t(x1)) (rows of d values), n as double; has_Y_init = 0: Y_init is
+ * ignored (a buffer of length >= 1); itercosts / costs: buffers of the sizes sharp_tsne documents */
+void sharp_C_tsne(double *X, double *n, int *d, int *dims, int *initial_dims, int *pca, int *pca_center, int *pca_scale, int *normalize,
+                  int *check_duplicates, double *perplexity, double *theta, int *max_iter, int *stop_lying_iter, int *mom_switch_iter,
+                  double *momentum, double *final_momentum, double *eta, double *exaggeration, int *has_Y_init, double *Y_init, double *seed,
+                  double *Y, double *itercosts, double *costs, int *status);
 
 #ifdef __cplusplus
 }

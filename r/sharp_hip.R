@@ -277,3 +277,30 @@ sharp_last_decisions <- function(cap = 65536L) {
     d$branch <- c("silhouette", "CH", "height", "N.cluster")[d$branch + 1L]
     d
 }
+
+# Rtsne(x1, ...) as R/visualization_SHARP.R:94 calls it: replace `Rtsne(` there by `sharp_Rtsne(`.  Rtsne's formals and return list;
+# exact repulsion on the GPU (theta accepted and unused, DESIGN.md 10), Y drawn from set.seed(seed)'s stream when Y_init is NULL.
+sharp_Rtsne <- function(X, dims = 2, initial_dims = 50, perplexity = 30, theta = 0.5, check_duplicates = TRUE, pca = TRUE,
+                        partial_pca = FALSE, max_iter = 1000, verbose = getOption("verbose", FALSE), is_distance = FALSE, Y_init = NULL,
+                        pca_center = TRUE, pca_scale = FALSE, normalize = TRUE,
+                        stop_lying_iter = ifelse(is.null(Y_init), 250L, 0L), mom_switch_iter = ifelse(is.null(Y_init), 250L, 0L),
+                        momentum = 0.5, final_momentum = 0.8, eta = 200, exaggeration_factor = 12, num_threads = 1, seed = 10, ...) {
+    if (is_distance) stop("sharp_Rtsne: is_distance = TRUE is not supported")
+    X <- .sharp_dmat(X)
+    n <- nrow(X); d <- ncol(X)
+    has_init <- !is.null(Y_init)
+    if (has_init && !all(dim(Y_init) == c(n, dims))) stop("Y_init must be an n x dims matrix")
+    iters <- seq_len(max_iter) - 1L
+    ncost <- sum((iters > 0 & iters %% 50 == 0) | iters == max_iter - 1L)
+    r <- .C("sharp_C_tsne", as.double(t(X)), as.double(n), as.integer(d), as.integer(dims), as.integer(initial_dims), as.integer(pca),
+            as.integer(pca_center), as.integer(pca_scale), as.integer(normalize), as.integer(check_duplicates), as.double(perplexity),
+            as.double(theta), as.integer(max_iter), as.integer(stop_lying_iter), as.integer(mom_switch_iter), as.double(momentum),
+            as.double(final_momentum), as.double(eta), as.double(exaggeration_factor), as.integer(has_init),
+            if (has_init) as.double(t(Y_init)) else double(1), as.double(seed),
+            Y = double(n * dims), itercosts = double(max(ncost, 1)), costs = double(n), status = integer(1))
+    .sharp_check(r$status)
+    list(N = n, Y = matrix(r$Y, n, dims, byrow = TRUE), costs = r$costs, itercosts = r$itercosts[seq_len(ncost)],
+         origD = if (pca) min(initial_dims, d) else d, perplexity = perplexity, theta = theta, max_iter = max_iter,
+         stop_lying_iter = stop_lying_iter, mom_switch_iter = mom_switch_iter, momentum = momentum, final_momentum = final_momentum,
+         eta = eta, exaggeration_factor = exaggeration_factor)
+}

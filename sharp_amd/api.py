@@ -13,7 +13,8 @@ from ._lib import SharpError, check, lib
 
 __all__ = ["ranM", "ranM2", "RPmat", "Projector", "SharpError", "get_opt_hclust", "getrowColor", "colorL", "HMETHODS",
            "wMetaC", "sMetaC", "SHARP", "SHARP_small", "SHARP_large", "SHARP_unlimited", "SHARP_unlimited2", "SHARP_unlimited3", "run_Mtimes_SHARP", "get_marker_genes", "get_marker_genes_unlimited",
-           "get_marker_genes_unlimited2", "testlog", "ARI", "decision_log", "last_decisions", "decision_margins", "DECISION_FIELDS"]
+           "get_marker_genes_unlimited2", "testlog", "ARI", "decision_log", "last_decisions", "decision_margins", "DECISION_FIELDS",
+           "visualization_SHARP", "vis_colors"]
 
 
 def _dp(a):
@@ -341,7 +342,8 @@ def SHARP(scExp, exp_type=None, ensize_K=None, reduced_ndim=None, base_ncells=No
           N_cluster=None, enpN_cluster=None, indN_cluster=None, minN_cluster=None, maxN_cluster=None, sil_thre=None,
           height_Ntimes=None, flashmark=False, logflag=None, sncells=None, n_cores=None, forview=True, prep=None,
           rM=None, rN_seed=None, gene_names=None, cell_names=None, testlog_cells=None):
-    """R/SHARP.R:44-318.  scExp: (genes, cells).  Returns the `enresults` list as a dict."""
+    """R/SHARP.R:44-318.  scExp: (genes, cells).  Returns the `enresults` list as a dict.
+    With forview (the default) it holds x0 and viE, the inputs of visualization_SHARP(result, label) -- the 2-D t-SNE map."""
     import time as _t
     import warnings
 
@@ -445,7 +447,8 @@ def SHARP_unlimited(scExp, viewflag=True, n_cores=None, ensize_K=None, N_cluster
                     maxN_cluster=None, rN_seed=None, devices=None):
     """R/SHARP_unlimited.R:29-242.  scExp: list of (genes, cells) blocks sharing the gene axis.
     devices (no reference counterpart: the reference's block loop is serial, :125-163): GPU indices; block b runs on devices[b mod N],
-    one host thread and one device context per GPU inside this process (sharp_SHARP_unlimited_multi), same labels as on one GPU."""
+    one host thread and one device context per GPU inside this process (sharp_SHARP_unlimited_multi), same labels as on one GPU.
+    With viewflag (the default) the result holds x0 (one-hot, CSR) and viE: visualization_SHARP(result, label) draws its 2-D t-SNE map."""
     import time as _t
     import warnings
 
@@ -944,3 +947,94 @@ def ARI(label, res):
     erand = (tot + (ra ** 2).sum() * (rb ** 2).sum() / n ** 2 - 0.5 * ((ra ** 2).sum() + (rb ** 2).sum())) / tot
     return {"Rand": rand, "HA": ha, "MA": (rand - erand) / (1 - erand), "FM": A / np.sqrt((A + B) * (A + Cc)),
             "Jaccard": A / (A + B + Cc)}
+
+
+# ---- visualization_SHARP (R/visualization_SHARP.R:31-177) ------------------------------------------------------------------------------
+# R/visualization_SHARP.R:129: the colours of the labelled map, recycled past 40 (a different order from colorL)
+vis_colors = ["black", "red", "green", "blue", "cyan", "magenta", "yellow", "grey", "brown", "purple", "orange", "turquoise", "beige",
+              "coral", "khaki", "violet", "pink", "salmon", "goldenrod", "orchid", "seagreen", "slategray", "darkred", "darkblue",
+              "darkcyan", "darkgreen", "darkgray", "darkkhaki", "darkorange", "darkmagenta", "darkviolet", "darkturquoise", "darksalmon",
+              "darkgoldenrod", "darkorchid", "darkseagreen", "darkslategray", "deeppink", "lightcoral", "lightcyan"]
+
+
+def _dense(x):
+    return np.asarray(x.toarray() if _is_sparse(x) else x, dtype=np.float64)
+
+
+def _scale_cols(x, what):
+    """R's scale(): centre, divide by the sd over n - 1; a constant column is an error here (NaN in R)"""
+    mu = x.mean(0)
+    sd = x.std(0, ddof=1)
+    bad = np.flatnonzero(~(sd > 0))
+    if bad.size:
+        raise SharpError(f"visualization_SHARP: column {bad[0] + 1} of {what} is constant (scale() would make it NaN)")
+    return (x - mu) / sd
+
+
+def _vis_input(y, w=2, seed=10):
+    """x1 of R/visualization_SHARP.R:52-60 from SHARP()'s x0 and viE"""
+    if y.get("x0") is None or y.get("viE") is None:
+        raise SharpError("visualization_SHARP: the result holds no x0 / viE (run SHARP with forview = TRUE)")
+    if w >= 100:                                                     # x0 alone, jitter(x0, amount = 0): U(-z/50, z/50), z = range
+        x0 = _dense(y["x0"])
+        z = float(x0.max() - x0.min())
+        if z == 0:
+            z = abs(float(x0.mean())) or 1.0
+        return x0 + np.random.default_rng(seed).uniform(-z / 50, z / 50, size=x0.shape)
+    if w <= 0.01:                                                    # viE alone
+        return np.array(_dense(y["viE"]))
+    return np.hstack([w * _scale_cols(_dense(y["x0"]), "x0"), _scale_cols(_dense(y["viE"]), "viE")])
+
+
+def _draw_sharp_map(Y, label, filename, filetype, legendtitle="Cell Type", width=9.5, height=8.5, res=400):
+    """the scatter of R/visualization_SHARP.R:113-170 with matplotlib's Agg canvas (pyplot's backend and state are left alone): coloured by
+    label, or black points"""
+    from matplotlib.backends.backend_agg import FigureCanvasAgg
+    from matplotlib.figure import Figure
+
+    Y = np.asarray(Y, dtype=np.float64)
+    y2 = Y[:, 1] if Y.shape[1] > 1 else np.zeros(Y.shape[0])
+    fig = Figure(figsize=(width, height))
+    FigureCanvasAgg(fig)
+    ax = fig.add_subplot()
+    if label is not None:
+        lab = np.asarray([str(v) for v in np.asarray(label).ravel()])
+        for k, u in enumerate(sorted(set(lab.tolist()))):
+            m = lab == u
+            ax.scatter(Y[m, 0], y2[m], s=4, c=vis_colors[k % len(vis_colors)], label=u, linewidths=0)
+        ax.legend(title=legendtitle, markerscale=3, frameon=False, loc="center left", bbox_to_anchor=(1.0, 0.5))
+    else:
+        ax.scatter(Y[:, 0], y2, s=4, c="black", linewidths=0)
+        ax.set_aspect("equal", adjustable="datalim")
+    ax.set_xlabel("SHARP Dim-1")
+    ax.set_ylabel("SHARP Dim-2")
+    ax.set_title("2D SHARP Visualization")
+    fig.savefig(filename, format=filetype, dpi=res, bbox_inches="tight")
+
+
+def visualization_SHARP(y, label=None, w=2, filename=None, filetype=None, n_cores=None, legendtitle="Cell Type", width=9.5, height=8.5,
+                        res=400, plot=True, **tsne_kwargs):
+    """R/visualization_SHARP.R:31-177: the 2-D t-SNE map of a SHARP() / SHARP_unlimited() result.
+
+    x1 = cbind(w * scale(x0), scale(viE)) (w >= 100: x0 with jitter; w <= 0.01: viE alone) goes to Rtsne(x1, check_duplicates = FALSE,
+    pca = ncol(x1) > 50, **tsne_kwargs) on the GPU (sharp_amd.tsne.Rtsne: exact repulsion, O(n^2) per iteration).  The figure (pdf
+    below 5000 cells, png otherwise; default name vi_SHARP.<type>) is drawn with matplotlib; plot=False skips it.  n_cores is accepted
+    and ignored.  Returns {"Y", "itercosts", "filename", "time"} (time in minutes, as R reports it)."""
+    import time as _t
+
+    from .tsne import Rtsne
+
+    t0 = _t.time()
+    x1 = _vis_input(y, w)
+    if filetype is None:
+        filetype = "pdf" if x1.shape[0] < 5000 else "png"
+    if filename is None:
+        filename = f"vi_SHARP.{filetype}"
+    kw = dict(tsne_kwargs)
+    kw.setdefault("check_duplicates", False)
+    kw.setdefault("pca", x1.shape[1] > 50)
+    kw.setdefault("seed", 10)                                         # set.seed(10), R/visualization_SHARP.R:85
+    out = Rtsne(x1, **kw)
+    if plot:
+        _draw_sharp_map(out["Y"], label, filename, filetype, legendtitle, width, height, res)
+    return {"Y": out["Y"], "itercosts": out["itercosts"], "filename": filename if plot else None, "time": (_t.time() - t0) / 60.0}

@@ -224,4 +224,14 @@ void sharp_C_marker_genes(double *X, int *m, double *n, int *label, int *n_clust
     *status = sharp_marker_genes(X, *m, as_ll(n), static_cast<long long>(*m), label, *n_cluster, *theta, *ng, out);
 }
 
+/* ---- Rtsne, as visualization_SHARP calls it (R/visualization_SHARP.R:94); X: as.double(t(x1)), rows of d values */
+void sharp_C_tsne(double *X, double *n, int *d, int *dims, int *initial_dims, int *pca, int *pca_center, int *pca_scale, int *normalize,
+                  int *check_duplicates, double *perplexity, double *theta, int *max_iter, int *stop_lying_iter, int *mom_switch_iter,
+                  double *momentum, double *final_momentum, double *eta, double *exaggeration, int *has_Y_init, double *Y_init, double *seed,
+                  double *Y, double *itercosts, double *costs, int *status) {
+    *status = sharp_tsne(X, as_ll(n), *d, static_cast<long long>(*d), *dims, *initial_dims, *pca, *pca_center, *pca_scale, *normalize,
+                         *check_duplicates, *perplexity, *theta, *max_iter, *stop_lying_iter, *mom_switch_iter, *momentum, *final_momentum, *eta,
+                         *exaggeration, *has_Y_init ? Y_init : nullptr, *seed, Y, itercosts, costs);
+}
+
 }  // extern "C"

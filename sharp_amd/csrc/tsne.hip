@@ -1,0 +1,1172 @@
+// tsne.hip -- exact t-SNE for visualization_SHARP (R/visualization_SHARP.R:94 hands x1 to Rtsne): DESIGN.md §10.
+//   input preparation   column means / sd (slab partials), X^T X on the f64 MFMA as slab partials summed in a fixed order, a host
+//                       symmetric eigensolver (Householder tridiagonalisation + implicit QL), the projection X V; centring and division
+//                       by the largest |entry|
+//   exact k-NN          distances ||x_i||^2 + ||x_j||^2 - 2 x_i.x_j on v_mfma_f64_16x16x4_f64 over streamed column tiles, a per-row top-K
+//                       in LDS behind a threshold filter, the chosen K re-ranked by a direct sum (x_i - x_j)^2
+//   calibration         one wave per row, fp64 bisection on beta (bhtsne's rule)
+//   symmetrisation      COO (i, j, p) + (j, i, p), radix sort by (row, col), duplicates merged, normalised by a fixed-order sum -> CSR
+//   optimiser loop      attraction over the CSR rows (fp64); exact repulsion, a workgroup owning 256 rows and streaming every y_j through
+//                       LDS (fp32 pair terms, fp64 per-tile folds, launches cut so that none exceeds ~1e11 pairs); one update kernel
+//                       (gains, velocity, position), mean subtraction, KL every 50 iterations
+// No floating-point atomics anywhere; every reduction runs in an order fixed by n alone, so a call is bitwise reproducible.
+#include "tsne.hpp"
+
+#include <algorithm>
+#include <cfloat>
+#include <climits>
+#include <cstring>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_reduce_by_key.hpp>
+
+#include "linalg.hpp"
+#include "rrng.hpp"
+
+namespace sharp {
+namespace {
+
+typedef double v4f64 __attribute__((ext_vector_type(4)));
+
+inline unsigned grid_for(long long n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// fixed-order reductions
+// ---------------------------------------------------------------------------------------------------------------------------
+// sum of v[0..n): block b sums its chunk (strided per thread, then a tree), one block sums the block partials the same way
+constexpr int kSumBlocks = 1024;
+__global__ __launch_bounds__(256) void sum_partial_kernel(const double *__restrict__ v, long long n, long long chunk, double *__restrict__ part) {
+    __shared__ double s[256];
+    const int tid = threadIdx.x;
+    const long long b0 = static_cast<long long>(blockIdx.x) * chunk, e = b0 + chunk < n ? b0 + chunk : n;
+    double a = 0.0;
+    for (long long k = b0 + tid; k < e; k += 256) a += v[k];
+    s[tid] = a;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) s[tid] += s[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) part[blockIdx.x] = s[0];
+}
+
+void sum_fixed(const double *v, long long n, double *part, double *out) {   // out: device scalar; part: kSumBlocks doubles
+    const long long chunk = std::max<long long>(256, (n + kSumBlocks - 1) / kSumBlocks);
+    const unsigned nb = grid_for(std::max<long long>(n, 1), static_cast<int>(std::min<long long>(chunk, INT_MAX)));
+    hipLaunchKernelGGL(sum_partial_kernel, dim3(nb), dim3(256), 0, ctx().stream, v, n, chunk, part);
+    hipLaunchKernelGGL(sum_partial_kernel, dim3(1), dim3(256), 0, ctx().stream, part, static_cast<long long>(nb), static_cast<long long>(nb), out);
+    launch_check("sum_partial_kernel");
+}
+
+// column sums of X (n x d, row i at X + i * ld) over slabs of rows: part[s * d + c]; with mu, sums of (x - mu)^2
+__global__ __launch_bounds__(256) void colsum_kernel(const double *__restrict__ X, long long n, int d, long long ld, long long rps,
+                                                     const double *__restrict__ mu, double *__restrict__ part) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= d) return;
+    const long long r0 = static_cast<long long>(blockIdx.y) * rps, r1 = r0 + rps < n ? r0 + rps : n;
+    double a = 0.0;
+    if (mu) {
+        const double m = mu[c];
+        for (long long r = r0; r < r1; ++r) { const double t = X[r * ld + c] - m; a += t * t; }
+    } else {
+        for (long long r = r0; r < r1; ++r) a += X[r * ld + c];
+    }
+    part[static_cast<long long>(blockIdx.y) * d + c] = a;
+}
+
+__global__ void slab_sum_kernel(const double *__restrict__ part, int nslab, long long len, double div, double *__restrict__ out) {
+    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= len) return;
+    double a = 0.0;
+    for (int s = 0; s < nslab; ++s) a += part[s * len + e];
+    out[e] = a / div;
+}
+
+// column means (mu == nullptr) or sums of squared deviations / div: out[0..d), device
+void column_stat(const double *X, long long n, int d, long long ld, const double *mu, double div, DevBuf<double> &part, double *out) {
+    const int nslab = static_cast<int>(std::min<long long>(256, std::max<long long>(1, n / 256)));
+    const long long rps = (n + nslab - 1) / nslab;
+    part.ensure(static_cast<size_t>(nslab) * d);
+    hipLaunchKernelGGL(colsum_kernel, dim3(grid_for(d, 256), nslab), dim3(256), 0, ctx().stream, X, n, d, ld, rps, mu, part.p);
+    hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(d, 256)), dim3(256), 0, ctx().stream, part.p, nslab, static_cast<long long>(d), div, out);
+    launch_check("colsum_kernel");
+}
+
+// out[i * d + c] = (X[i * ld + c] - mu[c]) / (sd ? sd[c] : scal)
+__global__ __launch_bounds__(256) void affine_kernel(const double *X, long long n, int d, long long ld, const double *__restrict__ mu,
+                                                     const double *__restrict__ sd, double scal, double *out) {   // (in place when out == X, ld == d)
+    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= n * d) return;
+    const long long r = e / d;
+    const int c = static_cast<int>(e - r * d);
+    double v = X[r * ld + c];
+    if (mu) v = v - mu[c];
+    out[e] = v / (sd ? sd[c] : scal);
+}
+
+__global__ __launch_bounds__(256) void absmax_kernel(const double *__restrict__ v, long long n, long long chunk, double *__restrict__ part) {
+    __shared__ double s[256];
+    const int tid = threadIdx.x;
+    const long long b0 = static_cast<long long>(blockIdx.x) * chunk, e = b0 + chunk < n ? b0 + chunk : n;
+    double a = 0.0;
+    for (long long k = b0 + tid; k < e; k += 256) a = fmax(a, fabs(v[k]));
+    s[tid] = a;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) s[tid] = fmax(s[tid], s[tid + w]);
+        __syncthreads();
+    }
+    if (tid == 0) part[blockIdx.x] = s[0];
+}
+
+// out (n x k) = Xc (n x d) . V (d x k), one thread per output, sequential over d
+__global__ __launch_bounds__(256) void project_kernel(const double *__restrict__ Xc, const double *__restrict__ V, long long n, int d, int k,
+                                                      double *__restrict__ out) {
+    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= n * k) return;
+    const long long r = e / k;
+    const int j = static_cast<int>(e - r * k);
+    double a = 0.0;
+    for (int c = 0; c < d; ++c) a += Xc[r * d + c] * V[static_cast<long long>(c) * k + j];
+    out[e] = a;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// host symmetric eigensolver: Householder tridiagonalisation + implicit QL (the EISPACK tred2 / tql2 pair); V (n x n, row-major) holds
+// the matrix on entry and the eigenvectors (columns) on exit, w the eigenvalues in ascending order
+// ---------------------------------------------------------------------------------------------------------------------------
+void tred2(int n, std::vector<double> &V, std::vector<double> &d, std::vector<double> &e) {
+    auto A = [&](int i, int j) -> double & { return V[static_cast<size_t>(i) * n + j]; };
+    for (int j = 0; j < n; ++j) d[j] = A(n - 1, j);
+    for (int i = n - 1; i > 0; --i) {
+        double scale = 0.0, h = 0.0;
+        for (int k = 0; k < i; ++k) scale += std::fabs(d[k]);
+        if (scale == 0.0) {
+            e[i] = d[i - 1];
+            for (int j = 0; j < i; ++j) { d[j] = A(i - 1, j); A(i, j) = 0.0; A(j, i) = 0.0; }
+        } else {
+            for (int k = 0; k < i; ++k) { d[k] /= scale; h += d[k] * d[k]; }
+            double f = d[i - 1], g = std::sqrt(h);
+            if (f > 0) g = -g;
+            e[i] = scale * g;
+            h = h - f * g;
+            d[i - 1] = f - g;
+            for (int j = 0; j < i; ++j) e[j] = 0.0;
+            for (int j = 0; j < i; ++j) {
+                f = d[j];
+                A(j, i) = f;
+                g = e[j] + A(j, j) * f;
+                for (int k = j + 1; k <= i - 1; ++k) { g += A(k, j) * d[k]; e[k] += A(k, j) * f; }
+                e[j] = g;
+            }
+            f = 0.0;
+            for (int j = 0; j < i; ++j) { e[j] /= h; f += e[j] * d[j]; }
+            const double hh = f / (h + h);
+            for (int j = 0; j < i; ++j) e[j] -= hh * d[j];
+            for (int j = 0; j < i; ++j) {
+                f = d[j];
+                g = e[j];
+                for (int k = j; k <= i - 1; ++k) A(k, j) -= (f * e[k] + g * d[k]);
+                d[j] = A(i - 1, j);
+                A(i, j) = 0.0;
+            }
+        }
+        d[i] = h;
+    }
+    for (int i = 0; i < n - 1; ++i) {
+        A(n - 1, i) = A(i, i);
+        A(i, i) = 1.0;
+        const double h = d[i + 1];
+        if (h != 0.0) {
+            for (int k = 0; k <= i; ++k) d[k] = A(k, i + 1) / h;
+            for (int j = 0; j <= i; ++j) {
+                double g = 0.0;
+                for (int k = 0; k <= i; ++k) g += A(k, i + 1) * A(k, j);
+                for (int k = 0; k <= i; ++k) A(k, j) -= g * d[k];
+            }
+        }
+        for (int k = 0; k <= i; ++k) A(k, i + 1) = 0.0;
+    }
+    for (int j = 0; j < n; ++j) { d[j] = A(n - 1, j); A(n - 1, j) = 0.0; }
+    A(n - 1, n - 1) = 1.0;
+    e[0] = 0.0;
+}
+
+void tql2(int n, std::vector<double> &V, std::vector<double> &d, std::vector<double> &e) {
+    auto A = [&](int i, int j) -> double & { return V[static_cast<size_t>(i) * n + j]; };
+    for (int i = 1; i < n; ++i) e[i - 1] = e[i];
+    e[n - 1] = 0.0;
+    double f = 0.0, tst1 = 0.0;
+    const double eps = std::ldexp(1.0, -52);
+    for (int l = 0; l < n; ++l) {
+        tst1 = std::max(tst1, std::fabs(d[l]) + std::fabs(e[l]));
+        int m = l;
+        while (m < n - 1 && !(std::fabs(e[m]) <= eps * tst1)) ++m;
+        if (m > l) {
+            int guard = 0;
+            do {
+                double g = d[l];
+                double p = (d[l + 1] - g) / (2.0 * e[l]);
+                double r = std::hypot(p, 1.0);
+                if (p < 0) r = -r;
+                d[l] = e[l] / (p + r);
+                d[l + 1] = e[l] * (p + r);
+                const double dl1 = d[l + 1];
+                double h = g - d[l];
+                for (int i = l + 2; i < n; ++i) d[i] -= h;
+                f += h;
+                p = d[m];
+                double c = 1.0, c2 = c, c3 = c, s = 0.0, s2 = 0.0;
+                const double el1 = e[l + 1];
+                for (int i = m - 1; i >= l; --i) {
+                    c3 = c2; c2 = c; s2 = s;
+                    g = c * e[i];
+                    h = c * p;
+                    r = std::hypot(p, e[i]);
+                    e[i + 1] = s * r;
+                    s = e[i] / r;
+                    c = p / r;
+                    p = c * d[i] - s * g;
+                    d[i + 1] = h + s * (c * g + s * d[i]);
+                    for (int k = 0; k < n; ++k) {
+                        h = A(k, i + 1);
+                        A(k, i + 1) = s * A(k, i) + c * h;
+                        A(k, i) = c * A(k, i) - s * h;
+                    }
+                }
+                p = -s * s2 * c3 * el1 * e[l] / dl1;
+                e[l] = s * p;
+                d[l] = c * p;
+            } while (std::fabs(e[l]) > eps * tst1 && ++guard < 60);
+            SHARP_REQUIRE(guard < 60, "Rtsne: the PCA eigensolver did not converge (non-finite input?)");
+        }
+        d[l] += f;
+        e[l] = 0.0;
+    }
+}
+
+// the k leading eigenvectors of the symmetric G (d x d) as the columns of Vk (d x k, row-major); sign: the largest |component| positive
+void leading_eigenvectors(std::vector<double> G, int d, int k, std::vector<double> &Vk) {
+    std::vector<double> w(d), e(d);
+    tred2(d, G, w, e);
+    tql2(d, G, w, e);
+    std::vector<int> ord(d);
+    for (int i = 0; i < d; ++i) ord[i] = i;
+    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return w[a] > w[b]; });
+    Vk.assign(static_cast<size_t>(d) * k, 0.0);
+    for (int j = 0; j < k; ++j) {
+        const int src = ord[j];
+        int arg = 0;
+        for (int i = 1; i < d; ++i)
+            if (std::fabs(G[static_cast<size_t>(i) * d + src]) > std::fabs(G[static_cast<size_t>(arg) * d + src])) arg = i;
+        const double sg = G[static_cast<size_t>(arg) * d + src] < 0 ? -1.0 : 1.0;
+        for (int i = 0; i < d; ++i) Vk[static_cast<size_t>(i) * k + j] = sg * G[static_cast<size_t>(i) * d + src];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// exact k-NN
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int KQ = 16;       // query rows per workgroup (one MFMA row block)
+constexpr int KCT = 64;      // candidates per column tile (4 waves x 16 MFMA columns)
+constexpr int KDT = KCT + 1; // LDS row of the distance tile
+constexpr double KNN_INF = 1.0e300;
+
+__device__ __forceinline__ bool lex_less(double a, int ia, double b, int ib) { return a < b || (a == b && ia < ib); }
+
+__global__ __launch_bounds__(256) void rownorm_kernel(const double *__restrict__ X, long long n, int d, double *__restrict__ nrm) {
+    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n) return;
+    double a = 0.0;
+    for (int c = 0; c < d; ++c) { const double t = X[i * d + c]; a += t * t; }
+    nrm[i] = a;
+}
+
+// Offers a tile of 64 candidates (lane l: distance v, index ci, valid) to one row's top-K list in LDS (Ld / Li, K entries, unsorted; the
+// row's current worst (thr, widx) at wpos).  A ballot of (dist, index) < worst leaves the few that enter; each replaces the worst and the
+// new worst is found by a wave-wide argmax.  Comparisons are lexicographic on (distance, index): ties go to the lower index.
+__device__ __forceinline__ void knn_offer(double v, int ci, bool valid, double *Ld, int *Li, int K, int lane, double &thr, int &widx, int &wpos) {
+    unsigned long long m = __ballot(valid && lex_less(v, ci, thr, widx));
+    while (m) {
+        const int bsel = __ffsll(static_cast<long long>(m)) - 1;
+        m &= m - 1;
+        const double vb = __shfl(v, bsel);
+        const int ib = __shfl(ci, bsel);
+        if (!lex_less(vb, ib, thr, widx)) continue;
+        if (lane == 0) { Ld[wpos] = vb; Li[wpos] = ib; }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        double bd = -1.0;
+        int bi = -1, bp = 0;
+        for (int p = lane; p < K; p += 64) {
+            const double dv = Ld[p];
+            const int iv = Li[p];
+            if (lex_less(bd, bi, dv, iv)) { bd = dv; bi = iv; bp = p; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double od = __shfl_xor(bd, off);
+            const int oi = __shfl_xor(bi, off), op = __shfl_xor(bp, off);
+            if (lex_less(bd, bi, od, oi)) { bd = od; bi = oi; bp = op; }
+        }
+        thr = bd;
+        widx = bi;
+        wpos = bp;   // (lane 0's copy is the one used: a position holding the worst)
+    }
+}
+
+// Workgroup (blockIdx.x, blockIdx.y): KQ query rows [q0, q0 + 16) against the candidate columns of chunk blockIdx.y, tile by tile of KCT.
+// Wave w computes the 16 x 16 block of columns c0 + 16 w .. + 16 on the f64 MFMA (C/D: row (lane >> 4) + 4 r, column lane & 15) into the
+// LDS tile; then wave w offers them to rows 4w .. 4w + 3.  The chunk's top-K of every row (GEMM distances, unsorted; sentinels
+// (KNN_INF, INT_MAX) where the chunk holds fewer than K candidates) goes to part[(chunk * rows + r) * K ..].
+__global__ __launch_bounds__(256) void knn_kernel(const double *__restrict__ X, const double *__restrict__ nrm, long long n, int d, int K,
+                                                  long long row0, long long row_end, long long cj, int *__restrict__ part_idx,
+                                                  double *__restrict__ part_dist) {
+    extern __shared__ double smem[];
+    double *dt = smem;                              // [KQ][KDT]
+    double *Ld = dt + KQ * KDT;                     // [KQ][K]
+    int *Li = reinterpret_cast<int *>(Ld + KQ * K);   // [KQ][K]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long q0 = row0 + static_cast<long long>(blockIdx.x) * KQ, rows = row_end - row0;
+    const long long cbeg = static_cast<long long>(blockIdx.y) * cj, cend = cbeg + cj < n ? cbeg + cj : n;
+    for (int e = tid; e < KQ * K; e += 256) { Ld[e] = KNN_INF; Li[e] = INT_MAX; }
+    double thr[4];
+    int widx[4], wpos[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { thr[r] = KNN_INF; widx[r] = INT_MAX; wpos[r] = 0; }
+    const long long qa = q0 + (lane & 15);
+    const bool qa_ok = qa < row_end;
+    double nq[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long long qq = q0 + (lane >> 4) + 4 * r;
+        nq[r] = qq < row_end ? nrm[qq] : 0.0;
+    }
+    __syncthreads();
+    for (long long c0 = cbeg; c0 < cend; c0 += KCT) {
+        const long long cb = c0 + wave * 16 + (lane & 15);
+        const bool cb_ok = cb < cend;
+        v4f64 acc = {0.0, 0.0, 0.0, 0.0};
+        for (int k0 = 0; k0 < d; k0 += 4) {
+            const int k = k0 + (lane >> 4);
+            const double a = (qa_ok && k < d) ? X[qa * d + k] : 0.0;
+            const double b = (cb_ok && k < d) ? X[cb * d + k] : 0.0;
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+        }
+        const double nc = cb_ok ? nrm[cb] : 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = (lane >> 4) + 4 * r;
+            dt[row * KDT + wave * 16 + (lane & 15)] = nq[r] + nc - 2.0 * acc[r];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int row = wave * 4 + rr;
+            const long long qq = q0 + row;
+            if (qq >= row_end) continue;
+            const long long ci = c0 + lane;
+            knn_offer(dt[row * KDT + lane], static_cast<int>(ci), ci < cend && ci != qq, Ld + row * K, Li + row * K, K, lane, thr[rr], widx[rr],
+                      wpos[rr]);
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < KQ * K; e += 256) {
+        const long long r = q0 - row0 + e / K;
+        if (r < rows) {
+            part_idx[(static_cast<long long>(blockIdx.y) * rows + r) * K + e % K] = Li[e];
+            part_dist[(static_cast<long long>(blockIdx.y) * rows + r) * K + e % K] = Ld[e];
+        }
+    }
+}
+
+// One wave per row of the launch: the K best of the chunks' lists (nc x K candidates, chunk after chunk), re-ranked by the direct sum
+// (x_i - x_j)^2 and sorted by (distance, index).  A row left with a sentinel (no finite distance to enough rows) sets *bad and writes
+// nothing it would have to read X for.
+__global__ __launch_bounds__(256) void knn_merge_kernel(const double *__restrict__ X, long long n, int d, int K, long long row0, long long rows,
+                                                        int nc, const int *__restrict__ part_idx, const double *__restrict__ part_dist,
+                                                        int *__restrict__ out_idx, double *__restrict__ out_dist, int *__restrict__ bad) {
+    extern __shared__ double smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double *Ld = smem + wave * K;                                  // [4][K] doubles, then [4][K] ints
+    int *Li = reinterpret_cast<int *>(smem + 4 * K) + wave * K;
+    const long long r = static_cast<long long>(blockIdx.x) * 4 + wave, qq = row0 + r;
+    if (r >= rows || qq >= n) return;
+    for (int p = lane; p < K; p += 64) { Ld[p] = KNN_INF; Li[p] = INT_MAX; }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    double thr = KNN_INF;
+    int widx = INT_MAX, wpos = 0;
+    for (int c = 0; c < nc; ++c) {
+        const long long base = (static_cast<long long>(c) * rows + r) * K;
+        for (int t = 0; t < K; t += 64) {
+            const bool in = t + lane < K;
+            const int ci = in ? part_idx[base + t + lane] : INT_MAX;
+            const double v = in ? part_dist[base + t + lane] : KNN_INF;
+            knn_offer(v, ci, in && ci >= 0 && ci < n, Ld, Li, K, lane, thr, widx, wpos);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int p = lane; p < K; p += 64) {
+        const int j = Li[p];
+        double s = KNN_INF;
+        if (j >= 0 && j < n) {
+            s = 0.0;
+            for (int c = 0; c < d; ++c) { const double t = X[qq * d + c] - X[static_cast<long long>(j) * d + c]; s += t * t; }
+        } else {
+            *bad = 1;   // every writer stores the same value
+        }
+        Ld[p] = s;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int p = lane; p < K; p += 64) {
+        const double dp = Ld[p];
+        const int ip = Li[p];
+        int rank = 0;
+        for (int q = 0; q < K; ++q) rank += lex_less(Ld[q], Li[q], dp, ip) ? 1 : 0;
+        out_idx[qq * K + rank] = ip < n ? ip : -1;
+        out_dist[qq * K + rank] = dp;
+    }
+}
+
+// *bad = 1 when a row norm is not finite or so large that a squared distance could overflow (NaN / Inf / huge input)
+__global__ __launch_bounds__(256) void norm_check_kernel(const double *__restrict__ nrm, long long n, int *__restrict__ bad) {
+    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (i < n && !(nrm[i] <= 0.125 * DBL_MAX)) *bad = 1;   // (false for NaN too)
+}
+
+__global__ __launch_bounds__(256) void dup_flag_kernel(const double *__restrict__ dist, long long n, int K, int *__restrict__ flag) {
+    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (i < n && dist[i * K] == 0.0) *flag = 1;   // every writer stores the same value
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// perplexity calibration: one wave per row, fp64 (bhtsne's bisection: beta from 1, doubling / halving while a bound is open, tol 1e-5
+// on the entropy in nats, at most 200 steps)
+// ---------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+
+__global__ __launch_bounds__(256) void calib_kernel(const double *__restrict__ dist, long long n, int K, double logU, double *__restrict__ P) {
+    const int lane = threadIdx.x & 63;
+    const long long i = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    double dv[4], pv[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { const int p = lane + 64 * t; dv[t] = p < K ? dist[i * K + p] : 0.0; pv[t] = 0.0; }
+    double beta = 1.0, minb = -DBL_MAX, maxb = DBL_MAX, sumP = DBL_MIN;
+    for (int it = 0; it < 200; ++it) {
+        double s = 0.0, h = 0.0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            pv[t] = lane + 64 * t < K ? exp(-beta * dv[t]) : 0.0;
+            s += pv[t];
+            h += beta * (dv[t] * pv[t]);
+        }
+        s = wave_sum(s);
+        h = wave_sum(h);
+        sumP = DBL_MIN + s;
+        const double Hdiff = (h / sumP + log(sumP)) - logU;
+        if (Hdiff < 1e-5 && -Hdiff < 1e-5) break;
+        if (Hdiff > 0) {
+            minb = beta;
+            beta = (maxb == DBL_MAX || maxb == -DBL_MAX) ? beta * 2.0 : (beta + maxb) / 2.0;
+        } else {
+            maxb = beta;
+            beta = (minb == -DBL_MAX || minb == DBL_MAX) ? beta / 2.0 : (beta + minb) / 2.0;
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int p = lane + 64 * t;
+        if (p < K) P[i * K + p] = pv[t] / sumP;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// symmetrisation
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void coo_kernel(const int *__restrict__ idx, const double *__restrict__ Pc, long long n, int K,
+                                                  unsigned long long *__restrict__ keys, double *__restrict__ vals) {
+    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= n * K) return;
+    const unsigned long long i = static_cast<unsigned long long>(e / K), j = static_cast<unsigned long long>(idx[e]);
+    const double p = Pc[e];
+    keys[2 * e] = i * static_cast<unsigned long long>(n) + j;
+    vals[2 * e] = p;
+    keys[2 * e + 1] = j * static_cast<unsigned long long>(n) + i;
+    vals[2 * e + 1] = p;
+}
+
+__global__ __launch_bounds__(256) void csr_kernel(const unsigned long long *__restrict__ keys, const double *__restrict__ uvals, long long nnz,
+                                                  long long n, const double *__restrict__ total, long long *__restrict__ rp, int *__restrict__ col,
+                                                  double *__restrict__ val) {
+    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= nnz) return;
+    const unsigned long long un = static_cast<unsigned long long>(n);
+    const long long r = static_cast<long long>(keys[e] / un);
+    col[e] = static_cast<int>(keys[e] - static_cast<unsigned long long>(r) * un);
+    val[e] = uvals[e] / total[0];
+    if (e == 0 || static_cast<long long>(keys[e - 1] / un) != r) rp[r] = e;
+    if (e == nnz - 1) rp[n] = nnz;
+}
+
+__global__ __launch_bounds__(256) void scale_kernel(double *__restrict__ v, long long n, double f, int divide) {
+    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (e < n) v[e] = divide ? v[e] / f : v[e] * f;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// gradient: attraction (CSR rows, fp64), exact repulsion (fp32 pair terms, fp64 folds), Z
+// ---------------------------------------------------------------------------------------------------------------------------
+template <int DIMS>
+__global__ __launch_bounds__(256) void attr_kernel(const long long *__restrict__ rp, const int *__restrict__ col, const double *__restrict__ val,
+                                                   const double *__restrict__ Y, long long n, double *__restrict__ attr) {
+    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n) return;
+    double yi[DIMS], acc[DIMS];
+#pragma unroll
+    for (int k = 0; k < DIMS; ++k) { yi[k] = Y[i * DIMS + k]; acc[k] = 0.0; }
+    for (long long e = rp[i]; e < rp[i + 1]; ++e) {
+        const long long j = col[e];
+        double diff[DIMS], D = 1.0;
+#pragma unroll
+        for (int k = 0; k < DIMS; ++k) { diff[k] = yi[k] - Y[j * DIMS + k]; D += diff[k] * diff[k]; }
+        D = val[e] / D;
+#pragma unroll
+        for (int k = 0; k < DIMS; ++k) acc[k] += D * diff[k];
+    }
+#pragma unroll
+    for (int k = 0; k < DIMS; ++k) attr[i * DIMS + k] = acc[k];
+}
+
+constexpr int RT = 256;                 // rows per workgroup and points per LDS tile of the repulsion
+constexpr double kPairsPerLaunch = 1e11;  // ~25 ms at the arithmetic rate: no repulsion launch near 0.1 s at any n
+
+// Workgroup (blockIdx.x, blockIdx.y): rows row0 + 256 blockIdx.x + tid against the columns of chunk blockIdx.y, 256 points per LDS tile.
+// Per pair (fp32, explicit fmaf): d = y_i - y_j, q = 1 / (1 + |d|^2), z += q, f += q^2 d.  Each tile's fp32 partials are folded into
+// fp64; the self pair (q = 1, d = 0) is taken out of z in fp64.  part[(chunk * rows + r) * 4 + k]: f_k (k < DIMS), z (k = DIMS).
+template <int DIMS>
+__global__ __launch_bounds__(256) void rep_kernel(const float *__restrict__ Yf, long long n, long long row0, long long rows, long long cj,
+                                                  double *__restrict__ part) {
+    __shared__ float ys[RT * DIMS];
+    const int tid = threadIdx.x;
+    const long long r = static_cast<long long>(blockIdx.x) * RT + tid, i = row0 + r;
+    const bool active = r < rows && i < n;
+    float yi[DIMS];
+#pragma unroll
+    for (int k = 0; k < DIMS; ++k) yi[k] = active ? Yf[i * DIMS + k] : 0.0f;
+    double F[DIMS + 1];
+#pragma unroll
+    for (int k = 0; k <= DIMS; ++k) F[k] = 0.0;
+    const long long jb = static_cast<long long>(blockIdx.y) * cj, je = jb + cj < n ? jb + cj : n;
+    for (long long t0 = jb; t0 < je; t0 += RT) {
+        const int cnt = static_cast<int>(je - t0 < RT ? je - t0 : RT);
+        __syncthreads();
+        for (int e = tid; e < cnt * DIMS; e += RT) ys[e] = Yf[t0 * DIMS + e];
+        __syncthreads();
+        float f[DIMS], z = 0.0f;
+#pragma unroll
+        for (int k = 0; k < DIMS; ++k) f[k] = 0.0f;
+#pragma unroll 8
+        for (int jj = 0; jj < cnt; ++jj) {
+            float dv[DIMS], d2 = 0.0f;
+#pragma unroll
+            for (int k = 0; k < DIMS; ++k) { dv[k] = yi[k] - ys[jj * DIMS + k]; d2 = fmaf(dv[k], dv[k], d2); }
+            const float q = __builtin_amdgcn_rcpf(1.0f + d2);
+            z += q;
+            const float q2 = q * q;
+#pragma unroll
+            for (int k = 0; k < DIMS; ++k) f[k] = fmaf(q2, dv[k], f[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < DIMS; ++k) F[k] += static_cast<double>(f[k]);
+        F[DIMS] += static_cast<double>(z);
+        if (i >= t0 && i < t0 + cnt) F[DIMS] -= 1.0;
+    }
+    if (r < rows) {
+#pragma unroll
+        for (int k = 0; k <= DIMS; ++k) part[(static_cast<long long>(blockIdx.y) * rows + r) * 4 + k] = F[k];
+    }
+}
+
+template <int DIMS>
+__global__ __launch_bounds__(256) void fold_kernel(const double *__restrict__ part, int nc, long long row0, long long rows, long long n,
+                                                   double *__restrict__ rep, double *__restrict__ zrow) {
+    const long long r = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x, i = row0 + r;
+    if (r >= rows || i >= n) return;
+    double F[DIMS + 1];
+#pragma unroll
+    for (int k = 0; k <= DIMS; ++k) F[k] = 0.0;
+    for (int c = 0; c < nc; ++c)
+#pragma unroll
+        for (int k = 0; k <= DIMS; ++k) F[k] += part[(static_cast<long long>(c) * rows + r) * 4 + k];
+#pragma unroll
+    for (int k = 0; k < DIMS; ++k) rep[i * DIMS + k] = F[k];
+    zrow[i] = F[DIMS];
+}
+
+template <int DIMS>
+__global__ __launch_bounds__(256) void grad_kernel(const double *__restrict__ attr, const double *__restrict__ rep, const double *__restrict__ Z,
+                                                   long long ne, double *__restrict__ dY) {
+    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (e < ne) dY[e] = attr[e] - rep[e] / Z[0];
+}
+
+__device__ __forceinline__ double sgn(double x) { return x == 0.0 ? 0.0 : (x < 0.0 ? -1.0 : 1.0); }
+
+// gains, velocity and position of one coordinate
+__global__ __launch_bounds__(256) void update_kernel(const double *__restrict__ attr, const double *__restrict__ rep, const double *__restrict__ Z,
+                                                     long long ne, double momentum, double eta, double *__restrict__ gains,
+                                                     double *__restrict__ uY, double *__restrict__ Y) {
+    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= ne) return;
+    const double dY = attr[e] - rep[e] / Z[0];
+    double g = gains[e];
+    const double u = uY[e];
+    g = sgn(dY) != sgn(u) ? g + 0.2 : g * 0.8;
+    if (g < 0.01) g = 0.01;
+    gains[e] = g;
+    const double un = momentum * u - eta * g * dY;
+    uY[e] = un;
+    Y[e] = Y[e] + un;
+}
+
+// Y -= mean (when mean), and the fp32 copy the repulsion reads
+template <int DIMS>
+__global__ __launch_bounds__(256) void center_kernel(double *__restrict__ Y, long long n, const double *__restrict__ mean, float *__restrict__ Yf) {
+    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= n * DIMS) return;
+    double v = Y[e];
+    if (mean) { v = v - mean[e % DIMS]; Y[e] = v; }
+    Yf[e] = static_cast<float>(v);
+}
+
+// per-row KL: sum_j P_ij log((P_ij + FLT_MIN) / (q_ij / Z + FLT_MIN))
+template <int DIMS>
+__global__ __launch_bounds__(256) void kl_kernel(const long long *__restrict__ rp, const int *__restrict__ col, const double *__restrict__ val,
+                                                 const double *__restrict__ Y, long long n, const double *__restrict__ Z, double *__restrict__ kl) {
+    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n) return;
+    double yi[DIMS];
+#pragma unroll
+    for (int k = 0; k < DIMS; ++k) yi[k] = Y[i * DIMS + k];
+    const double z = Z[0];
+    double c = 0.0;
+    for (long long e = rp[i]; e < rp[i + 1]; ++e) {
+        const long long j = col[e];
+        double D = 1.0;
+#pragma unroll
+        for (int k = 0; k < DIMS; ++k) { const double t = yi[k] - Y[j * DIMS + k]; D += t * t; }
+        const double Q = (1.0 / D) / z;
+        c += val[e] * log((val[e] + FLT_MIN) / (Q + FLT_MIN));
+    }
+    kl[i] = c;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// host orchestration
+// ---------------------------------------------------------------------------------------------------------------------------
+struct RepPlan {
+    long long rows = 0, cj = 0;   // rows per launch, columns per chunk
+    int nc = 1;                   // chunks
+};
+
+RepPlan rep_plan(long long n) {
+    RepPlan p;
+    const long long n_up = (n + RT - 1) / RT * RT;
+    long long rows = static_cast<long long>(kPairsPerLaunch / static_cast<double>(std::max<long long>(n, 1))) / RT * RT;
+    p.rows = std::min(n_up, std::max<long long>(RT, rows));
+    const long long rb = (p.rows + RT - 1) / RT;
+    long long nc = std::max<long long>(1, std::min<long long>((n + RT - 1) / RT, (2048 + rb - 1) / rb));   // >= ~2048 workgroups per launch
+    p.cj = ((n + nc - 1) / nc + RT - 1) / RT * RT;
+    p.nc = static_cast<int>((n + p.cj - 1) / p.cj);
+    return p;
+}
+
+struct Work {
+    long long n = 0;
+    int dims = 2;
+    RepPlan plan;
+    DevBuf<double> Y, uY, gains, attr, rep, zrow, kl, part, red, scal, colpart;   // scal: [0] Z, [1] KL sum, [2..] mean
+    DevBuf<float> Yf;
+    void init(long long n_, int dims_) {
+        n = n_;
+        dims = dims_;
+        plan = rep_plan(n);
+        const size_t ne = static_cast<size_t>(n) * dims;
+        Y.alloc(ne); uY.alloc(ne); gains.alloc(ne); attr.alloc(ne); rep.alloc(ne); Yf.alloc(ne);
+        zrow.alloc(n); kl.alloc(n);
+        part.alloc(static_cast<size_t>(plan.nc) * plan.rows * 4);
+        red.alloc(kSumBlocks);
+        scal.alloc(8);
+    }
+};
+
+template <int DIMS>
+void to_f32(Work &w, bool center) {
+    if (center) column_stat(w.Y.p, w.n, DIMS, DIMS, nullptr, static_cast<double>(w.n), w.colpart, w.scal.p + 2);
+    hipLaunchKernelGGL(center_kernel<DIMS>, dim3(grid_for(w.n * DIMS, 256)), dim3(256), 0, ctx().stream, w.Y.p, w.n, center ? w.scal.p + 2 : nullptr, w.Yf.p);
+    launch_check("center_kernel");
+}
+
+// attr, rep, zrow and Z (scal[0]) at the current Y / Yf
+template <int DIMS>
+void gradient_terms(const TsneP &P, Work &w) {
+    Ctx &c = ctx();
+    {
+        KernelTimer t("tsne_attr");
+        hipLaunchKernelGGL(attr_kernel<DIMS>, dim3(grid_for(w.n, 256)), dim3(256), 0, c.stream, P.row_ptr.p, P.col.p, P.val.p, w.Y.p, w.n, w.attr.p);
+        launch_check("attr_kernel");
+    }
+    KernelTimer t("tsne_rep");
+    for (long long r0 = 0; r0 < w.n; r0 += w.plan.rows) {
+        hipLaunchKernelGGL(rep_kernel<DIMS>, dim3(grid_for(w.plan.rows, RT), w.plan.nc), dim3(RT), 0, c.stream, w.Yf.p, w.n, r0, w.plan.rows, w.plan.cj,
+                           w.part.p);
+        hipLaunchKernelGGL(fold_kernel<DIMS>, dim3(grid_for(w.plan.rows, 256)), dim3(256), 0, c.stream, w.part.p, w.plan.nc, r0, w.plan.rows, w.n,
+                           w.rep.p, w.zrow.p);
+        launch_check("rep_kernel");
+    }
+    sum_fixed(w.zrow.p, w.n, w.red.p, w.scal.p);
+}
+
+template <int DIMS>
+void kl_eval(const TsneP &P, Work &w, double *dst) {
+    KernelTimer t("tsne_kl");
+    hipLaunchKernelGGL(kl_kernel<DIMS>, dim3(grid_for(w.n, 256)), dim3(256), 0, ctx().stream, P.row_ptr.p, P.col.p, P.val.p, w.Y.p, w.n, w.scal.p, w.kl.p);
+    launch_check("kl_kernel");
+    sum_fixed(w.kl.p, w.n, w.red.p, dst);
+}
+
+struct LoopArgs {
+    int max_iter, stop_lying_iter, mom_switch_iter;
+    double momentum, final_momentum, eta, exaggeration;
+};
+
+template <int DIMS>
+void optimise(TsneP &P, Work &w, const LoopArgs &a, std::vector<double> &itercosts, double *costs) {
+    Ctx &c = ctx();
+    const long long ne = w.n * DIMS;
+    const bool lying = a.stop_lying_iter > 0;
+    if (lying) hipLaunchKernelGGL(scale_kernel, dim3(grid_for(P.nnz, 256)), dim3(256), 0, c.stream, P.val.p, P.nnz, a.exaggeration, 0);
+    SHARP_HIP_CHECK(hipMemsetAsync(w.uY.p, 0, ne * sizeof(double), c.stream));
+    std::vector<double> ones(static_cast<size_t>(ne), 1.0);
+    w.gains.upload(ones.data(), ones.size());
+    to_f32<DIMS>(w, false);
+    std::vector<int> record;   // iterations whose KL is recorded
+    for (int it = 0; it < a.max_iter; ++it)
+        if ((it > 0 && it % 50 == 0) || it == a.max_iter - 1) record.push_back(it);
+    DevBuf<double> dcost(std::max<size_t>(1, record.size()));
+    size_t next_cost = 0;
+    bool pending = false;     // the KL of the previous iteration's positions is due: it is evaluated with this iteration's Z
+    double momentum = a.momentum;
+    for (int it = 0; it < a.max_iter; ++it) {
+        gradient_terms<DIMS>(P, w);
+        if (pending) { kl_eval<DIMS>(P, w, dcost.p + next_cost++); pending = false; }
+        {
+            KernelTimer t("tsne_update");
+            hipLaunchKernelGGL(update_kernel, dim3(grid_for(ne, 256)), dim3(256), 0, c.stream, w.attr.p, w.rep.p, w.scal.p, ne, momentum, a.eta,
+                               w.gains.p, w.uY.p, w.Y.p);
+            launch_check("update_kernel");
+            to_f32<DIMS>(w, true);
+        }
+        if (it == a.stop_lying_iter && lying)
+            hipLaunchKernelGGL(scale_kernel, dim3(grid_for(P.nnz, 256)), dim3(256), 0, c.stream, P.val.p, P.nnz, a.exaggeration, 1);
+        if (it == a.mom_switch_iter) momentum = a.final_momentum;
+        if (next_cost < record.size() && record[next_cost] == it) pending = true;
+    }
+    // the last recorded KL (the last iteration's), or the cost at the start when there are no iterations
+    if (pending || costs) {
+        gradient_terms<DIMS>(P, w);
+        kl_eval<DIMS>(P, w, pending ? dcost.p + next_cost++ : w.scal.p + 1);
+    }
+    itercosts.assign(record.size(), 0.0);
+    if (!record.empty()) dcost.download(itercosts.data(), record.size());
+    if (costs) w.kl.download(costs, static_cast<size_t>(w.n));
+}
+
+// ---- stage helpers used by the entries -----------------------------------------------------------------------------------
+void upload_rows(const double *X, long long n, int d, long long ld, DevBuf<double> &dst) {
+    dst.alloc(static_cast<size_t>(n) * d);
+    if (ld == d) {
+        dst.upload(X, static_cast<size_t>(n) * d);
+    } else {
+        SHARP_HIP_CHECK(hipMemcpy2DAsync(dst.p, d * sizeof(double), X, ld * sizeof(double), d * sizeof(double), n, hipMemcpyHostToDevice, ctx().stream));
+    }
+}
+
+int perplexity_K(double perplexity) {
+    SHARP_REQUIRE(std::isfinite(perplexity) && perplexity > 0, "Rtsne: perplexity must be positive");
+    SHARP_REQUIRE(perplexity <= 85.0, "Rtsne: perplexity above 85 is not supported (at most 255 neighbours per row)");
+    return static_cast<int>(std::floor(3.0 * perplexity));
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------------
+void tsne_prepare(const double *X, long long n, int d, long long ld, bool pca, int initial_dims, bool pca_center, bool pca_scale, bool normalize,
+                  DevBuf<double> &out, int *d_out) {
+    Ctx &c = ctx();
+    DevBuf<double> raw, part, stat(static_cast<size_t>(2) * d + 2);
+    upload_rows(X, n, d, ld, raw);
+    int dd = d;
+    if (pca) {
+        KernelTimer t("tsne_pca");
+        const int k = std::min(initial_dims, d);
+        SHARP_REQUIRE(k >= 1, "Rtsne: initial_dims must be >= 1");
+        const double *mu = nullptr, *sd = nullptr;
+        if (pca_center) { column_stat(raw.p, n, d, d, nullptr, static_cast<double>(n), part, stat.p); mu = stat.p; }
+        if (pca_scale) {
+            // prcomp(scale. = TRUE): the sd (n - 1) around the centre used (the column mean, or 0 without centring: the root mean square)
+            DevBuf<double> zero;
+            if (!mu) { zero.alloc(d); zero.zero(); }
+            column_stat(raw.p, n, d, d, mu ? mu : zero.p, static_cast<double>(std::max<long long>(n - 1, 1)), part, stat.p + d);
+            std::vector<double> v(d);
+            SHARP_HIP_CHECK(hipMemcpyAsync(v.data(), stat.p + d, d * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+            stream_sync();
+            for (int j = 0; j < d; ++j) {
+                SHARP_REQUIRE(v[j] > 0 && std::isfinite(v[j]), "Rtsne: cannot rescale a constant/zero column to unit variance (column " + std::to_string(j + 1) + ")");
+                v[j] = std::sqrt(v[j]);
+            }
+            SHARP_HIP_CHECK(hipMemcpyAsync(stat.p + d, v.data(), d * sizeof(double), hipMemcpyHostToDevice, c.stream));
+            stream_sync();
+            sd = stat.p + d;
+        }
+        DevBuf<double> xc(static_cast<size_t>(n) * d);
+        hipLaunchKernelGGL(affine_kernel, dim3(grid_for(n * d, 256)), dim3(256), 0, c.stream, raw.p, n, d, static_cast<long long>(d), mu, sd, 1.0, xc.p);
+        launch_check("affine_kernel");
+        raw.release();
+        // X^T X: slab partials on the f64 MFMA (linalg.hip's TN GEMM, symmetric tiles), summed in slab order
+        const size_t dd2 = static_cast<size_t>(d) * d;
+        int nslab = static_cast<int>(std::min<long long>({64, std::max<long long>(1, n / 512),
+                                                          std::max<long long>(1, static_cast<long long>((512ull << 20) / (dd2 * sizeof(double))))}));
+        const long long rps = (n + nslab - 1) / nslab;
+        nslab = static_cast<int>((n + rps - 1) / rps);
+        DevBuf<double> gpart(dd2 * nslab), gram(dd2);
+        std::vector<GemmTask> tasks(nslab);
+        for (int s = 0; s < nslab; ++s) {
+            const long long r0 = s * rps, rows = std::min(rps, n - r0);
+            GemmTask &g = tasks[s];
+            g.At = xc.p + r0 * d;
+            g.Bt = g.At;
+            g.C = gpart.p + s * dd2;
+            g.M = g.N = d;
+            g.K = static_cast<int>(rows);
+            g.lda = g.ldb = g.ldc = d;
+            g.epilogue = 0;
+            g.symmetric = 1;
+            g.fast = 0;
+        }
+        DevBuf<GemmTask> dtasks(tasks.size());
+        dtasks.upload(tasks.data(), tasks.size());
+        gemm_tn_f64_batched(dtasks.p, nslab, d, d, "tsne_pca_gram", false, true);
+        hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(static_cast<long long>(dd2), 256)), dim3(256), 0, c.stream, gpart.p, nslab,
+                           static_cast<long long>(dd2), 1.0, gram.p);
+        launch_check("slab_sum_kernel");
+        std::vector<double> G(dd2), Vk;
+        gram.download(G.data(), dd2);
+        {
+            HostTimer ht("tsne_pca_eigen");
+            leading_eigenvectors(std::move(G), d, k, Vk);
+        }
+        DevBuf<double> dV(Vk.size());
+        dV.upload(Vk.data(), Vk.size());
+        out.alloc(static_cast<size_t>(n) * k);
+        hipLaunchKernelGGL(project_kernel, dim3(grid_for(n * k, 256)), dim3(256), 0, c.stream, xc.p, dV.p, n, d, k, out.p);
+        launch_check("project_kernel");
+        stream_sync();
+        dd = k;
+    } else {
+        out = std::move(raw);
+    }
+    if (normalize) {
+        KernelTimer t("tsne_normalize");
+        column_stat(out.p, n, dd, dd, nullptr, static_cast<double>(n), part, stat.p);
+        hipLaunchKernelGGL(affine_kernel, dim3(grid_for(n * dd, 256)), dim3(256), 0, c.stream, out.p, n, dd, static_cast<long long>(dd), stat.p,
+                           nullptr, 1.0, out.p);
+        const long long chunk = std::max<long long>(256, (n * dd + kSumBlocks - 1) / kSumBlocks);
+        const unsigned nb = grid_for(n * dd, static_cast<int>(std::min<long long>(chunk, INT_MAX)));
+        DevBuf<double> mx(nb);
+        hipLaunchKernelGGL(absmax_kernel, dim3(nb), dim3(256), 0, c.stream, out.p, n * dd, chunk, mx.p);
+        launch_check("absmax_kernel");
+        std::vector<double> hm(nb);
+        mx.download(hm.data(), nb);
+        double m = 0.0;
+        for (double v : hm) m = std::max(m, v);
+        SHARP_REQUIRE(m > 0 && std::isfinite(m), "Rtsne: the normalised input is all zero or not finite");
+        hipLaunchKernelGGL(affine_kernel, dim3(grid_for(n * dd, 256)), dim3(256), 0, c.stream, out.p, n, dd, static_cast<long long>(dd), nullptr,
+                           nullptr, m, out.p);
+        launch_check("affine_kernel");
+    }
+    *d_out = dd;
+}
+
+void tsne_knn(const double *dX, long long n, int d, int K, DevBuf<int> &idx, DevBuf<double> &dist) {
+    Ctx &c = ctx();
+    SHARP_REQUIRE(K >= 1 && K <= 255 && n - 1 >= K, "tsne_knn: need 1 <= K <= 255 and K < n");
+    KernelTimer t("tsne_knn");
+    DevBuf<double> nrm(n);
+    DevBuf<int> bad(1);
+    bad.zero();
+    hipLaunchKernelGGL(rownorm_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, dX, n, d, nrm.p);
+    hipLaunchKernelGGL(norm_check_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, nrm.p, n, bad.p);
+    launch_check("norm_check_kernel");
+    int hb = 0;
+    bad.download(&hb, 1);
+    SHARP_REQUIRE(hb == 0, "Rtsne: the (prepared) input holds NA / NaN / Inf, or values so large that squared distances overflow");
+    idx.alloc(static_cast<size_t>(n) * K);
+    dist.alloc(static_cast<size_t>(n) * K);
+    // Launches of about 8e9 candidate pairs at d = 50 (measured 1e11 pairs / s at d = 50: under 0.1 s each at any n): rows per launch
+    // from that budget, and the candidate columns cut into chunks so that a launch has >= ~1024 workgroups however few its rows are.
+    const double budget = 8e9 / (std::max(d, 4) / 50.0 + 0.25);
+    const long long rows = std::min((n + KQ - 1) / KQ * KQ, std::max<long long>(KQ, static_cast<long long>(budget / static_cast<double>(n)) / KQ * KQ));
+    const long long rb = (rows + KQ - 1) / KQ;
+    const long long nc0 = std::max<long long>(1, std::min<long long>((n + KCT - 1) / KCT, (1024 + rb - 1) / rb));
+    const long long cj = ((n + nc0 - 1) / nc0 + KCT - 1) / KCT * KCT;
+    const int nc = static_cast<int>((n + cj - 1) / cj);
+    DevBuf<int> pidx(static_cast<size_t>(nc) * rows * K);
+    DevBuf<double> pdist(static_cast<size_t>(nc) * rows * K);
+    const size_t lds = sizeof(double) * KQ * KDT + (sizeof(double) + sizeof(int)) * KQ * K;
+    const size_t lds_merge = (sizeof(double) + sizeof(int)) * 4 * K;
+    for (long long r0 = 0; r0 < n; r0 += rows) {
+        const long long r1 = std::min(n, r0 + rows);
+        hipLaunchKernelGGL(knn_kernel, dim3(grid_for(r1 - r0, KQ), nc), dim3(256), lds, c.stream, dX, nrm.p, n, d, K, r0, r1, cj, pidx.p, pdist.p);
+        launch_check("knn_kernel");
+        hipLaunchKernelGGL(knn_merge_kernel, dim3(grid_for(r1 - r0, 4)), dim3(256), lds_merge, c.stream, dX, n, d, K, r0, r1 - r0, nc, pidx.p,
+                           pdist.p, idx.p, dist.p, bad.p);
+        launch_check("knn_merge_kernel");
+    }
+    bad.download(&hb, 1);
+    SHARP_REQUIRE(hb == 0, "Rtsne: fewer than K rows at a finite distance from some row (non-finite input?)");
+}
+
+void tsne_affinities(const DevBuf<int> &idx, const DevBuf<double> &dist, long long n, int K, double perplexity, TsneP &P) {
+    Ctx &c = ctx();
+    DevBuf<double> Pc(static_cast<size_t>(n) * K);
+    {
+        KernelTimer t("tsne_calib");
+        hipLaunchKernelGGL(calib_kernel, dim3(grid_for(n, 4)), dim3(256), 0, c.stream, dist.p, n, K, std::log(perplexity), Pc.p);
+        launch_check("calib_kernel");
+    }
+    KernelTimer t("tsne_sym");
+    const size_t ne = static_cast<size_t>(n) * K * 2;
+    DevBuf<unsigned long long> keys(ne), keys2(ne);
+    DevBuf<double> vals(ne), vals2(ne);
+    hipLaunchKernelGGL(coo_kernel, dim3(grid_for(n * K, 256)), dim3(256), 0, c.stream, idx.p, Pc.p, n, K, keys.p, vals.p);
+    launch_check("coo_kernel");
+    Pc.release();
+    unsigned bits = 1;
+    while (bits < 64 && (static_cast<unsigned long long>(n) * static_cast<unsigned long long>(n) >> bits) != 0) ++bits;
+    size_t tmp_bytes = 0;
+    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.p, keys2.p, vals.p, vals2.p, ne, 0, bits, c.stream));
+    DevBuf<unsigned char> tmp(std::max<size_t>(tmp_bytes, 1));
+    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys.p, keys2.p, vals.p, vals2.p, ne, 0, bits, c.stream));
+    // merge the (at most two) entries of a key: p_ij + p_ji
+    DevBuf<size_t> count(1);
+    size_t tmp2 = 0;
+    SHARP_HIP_CHECK(rocprim::reduce_by_key(nullptr, tmp2, keys2.p, vals2.p, ne, keys.p, vals.p, count.p, rocprim::plus<double>(),
+                                           rocprim::equal_to<unsigned long long>(), c.stream));
+    if (tmp2 > tmp.n) tmp.alloc(tmp2);
+    tmp2 = tmp.n;
+    SHARP_HIP_CHECK(rocprim::reduce_by_key(tmp.p, tmp2, keys2.p, vals2.p, ne, keys.p, vals.p, count.p, rocprim::plus<double>(),
+                                           rocprim::equal_to<unsigned long long>(), c.stream));
+    size_t nnz = 0;
+    count.download(&nnz, 1);
+    DevBuf<double> red(kSumBlocks), total(1);
+    sum_fixed(vals.p, static_cast<long long>(nnz), red.p, total.p);
+    P.n = n;
+    P.nnz = static_cast<long long>(nnz);
+    P.row_ptr.alloc(n + 1);
+    P.col.alloc(nnz);
+    P.val.alloc(nnz);
+    hipLaunchKernelGGL(csr_kernel, dim3(grid_for(P.nnz, 256)), dim3(256), 0, c.stream, keys.p, vals.p, P.nnz, n, total.p, P.row_ptr.p, P.col.p, P.val.p);
+    launch_check("csr_kernel");
+    stream_sync();
+}
+
+void tsne_gradient(const TsneP &P, const double *dY_in, int dims, double *dGrad) {
+    Work w;
+    w.init(P.n, dims);
+    SHARP_HIP_CHECK(hipMemcpyAsync(w.Y.p, dY_in, static_cast<size_t>(P.n) * dims * sizeof(double), hipMemcpyDeviceToDevice, ctx().stream));
+    const long long ne = P.n * dims;
+    auto run = [&](auto tag) {
+        constexpr int D = decltype(tag)::value;
+        to_f32<D>(w, false);
+        gradient_terms<D>(P, w);
+        hipLaunchKernelGGL(grad_kernel<D>, dim3(grid_for(ne, 256)), dim3(256), 0, ctx().stream, w.attr.p, w.rep.p, w.scal.p, ne, dGrad);
+        launch_check("grad_kernel");
+    };
+    if (dims == 1) run(std::integral_constant<int, 1>());
+    else if (dims == 2) run(std::integral_constant<int, 2>());
+    else run(std::integral_constant<int, 3>());
+    stream_sync();
+}
+
+}  // namespace sharp
+
+using namespace sharp;
+
+namespace {
+void check_dims(int dims) { SHARP_REQUIRE(dims >= 1 && dims <= 3, "Rtsne: dims must be 1, 2 or 3"); }
+void check_X(const double *X, long long n, int d, long long ld) {
+    SHARP_REQUIRE(X && n >= 2 && d >= 1 && ld >= d, "Rtsne: bad input matrix (need n >= 2 rows of d >= 1 values, ld >= d)");
+    SHARP_REQUIRE(n < INT_MAX, "Rtsne: at most 2^31 - 1 rows");
+    for (long long i = 0; i < n; ++i)
+        for (int c = 0; c < d; ++c)
+            if (!std::isfinite(X[i * ld + c]))
+                throw sharp::Error(SHARP_ERR_ARG, "Rtsne: the input holds NA / NaN / Inf (row " + std::to_string(i + 1) + ", column " +
+                                                      std::to_string(c + 1) + ")");
+}
+}  // namespace
+
+extern "C" {
+
+// R/visualization_SHARP.R:94: Rtsne(x1, check_duplicates = FALSE, pca = flag, ...), with an exact repulsion (theta accepted, unused)
+int sharp_tsne(const double *X, long long n, int d, long long ld, int dims, int initial_dims, int pca, int pca_center, int pca_scale, int normalize,
+               int check_duplicates, double perplexity, double theta, int max_iter, int stop_lying_iter, int mom_switch_iter, double momentum,
+               double final_momentum, double eta, double exaggeration, const double *Y_init, double seed, double *Y, double *itercosts,
+               double *costs) {
+    SHARP_API_BEGIN
+    (void)theta;
+    ctx();
+    check_X(X, n, d, ld);
+    check_dims(dims);
+    SHARP_REQUIRE(Y, "sharp_tsne: null Y");
+    SHARP_REQUIRE(max_iter >= 0 && std::isfinite(eta) && std::isfinite(momentum) && std::isfinite(final_momentum), "Rtsne: bad optimiser arguments");
+    SHARP_REQUIRE(std::isfinite(exaggeration) && exaggeration > 0, "Rtsne: exaggeration_factor must be positive");
+    const int K = perplexity_K(perplexity);
+    SHARP_REQUIRE(static_cast<double>(n - 1) >= 3.0 * perplexity, "Perplexity is too large.");
+    DevBuf<double> Xp;
+    int dp = 0;
+    tsne_prepare(X, n, d, ld, pca != 0, initial_dims, pca_center != 0, pca_scale != 0, normalize != 0, Xp, &dp);
+    DevBuf<int> idx;
+    DevBuf<double> dist;
+    tsne_knn(Xp.p, n, dp, K, idx, dist);
+    if (check_duplicates) {
+        DevBuf<int> flag(1);
+        flag.zero();
+        hipLaunchKernelGGL(dup_flag_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx().stream, dist.p, n, K, flag.p);
+        int f = 0;
+        flag.download(&f, 1);
+        SHARP_REQUIRE(f == 0, "Remove duplicates before running TSNE.");
+    }
+    Xp.release();
+    TsneP P;
+    tsne_affinities(idx, dist, n, K, perplexity, P);
+    idx.release();
+    dist.release();
+    Work w;
+    w.init(n, dims);
+    const size_t ne = static_cast<size_t>(n) * dims;
+    std::vector<double> y0(ne);
+    if (Y_init) {
+        for (size_t e = 0; e < ne; ++e) SHARP_REQUIRE(std::isfinite(Y_init[e]), "Rtsne: Y_init holds NA / NaN / Inf");
+        std::copy(Y_init, Y_init + ne, y0.begin());
+    } else {
+        // Y = 1e-4 N(0, 1): R's set.seed(seed) stream, one normal per pair of unif_rand() (polar method, the second draw discarded)
+        RRng rng(static_cast<uint32_t>(static_cast<int>(seed)));
+        for (size_t e = 0; e < ne; ++e) {
+            double x, y, rad;
+            do {
+                x = 2.0 * rng.unif() - 1.0;
+                y = 2.0 * rng.unif() - 1.0;
+                rad = x * x + y * y;
+            } while (rad >= 1.0 || rad == 0.0);
+            y0[e] = x * std::sqrt(-2.0 * std::log(rad) / rad) * 1e-4;
+        }
+    }
+    w.Y.upload(y0.data(), ne);
+    const LoopArgs la{max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta, exaggeration};
+    std::vector<double> ic;
+    if (dims == 1) optimise<1>(P, w, la, ic, costs);
+    else if (dims == 2) optimise<2>(P, w, la, ic, costs);
+    else optimise<3>(P, w, la, ic, costs);
+    w.Y.download(Y, ne);
+    if (itercosts) std::copy(ic.begin(), ic.end(), itercosts);
+    SHARP_API_END
+}
+
+int sharp_tsne_prepare(const double *X, long long n, int d, long long ld, int pca, int initial_dims, int pca_center, int pca_scale, int normalize,
+                       double *out, int *d_out) {
+    SHARP_API_BEGIN
+    ctx();
+    check_X(X, n, d, ld);
+    SHARP_REQUIRE(out && d_out, "sharp_tsne_prepare: null output");
+    DevBuf<double> Xp;
+    tsne_prepare(X, n, d, ld, pca != 0, initial_dims, pca_center != 0, pca_scale != 0, normalize != 0, Xp, d_out);
+    Xp.download(out, static_cast<size_t>(n) * *d_out);
+    SHARP_API_END
+}
+
+int sharp_tsne_knn(const double *X, long long n, int d, long long ld, int K, int *idx, double *dist) {
+    SHARP_API_BEGIN
+    ctx();
+    check_X(X, n, d, ld);
+    SHARP_REQUIRE(idx && dist, "sharp_tsne_knn: null output");
+    DevBuf<double> dX;
+    upload_rows(X, n, d, ld, dX);
+    DevBuf<int> di;
+    DevBuf<double> dd;
+    tsne_knn(dX.p, n, d, K, di, dd);
+    di.download(idx, static_cast<size_t>(n) * K);
+    dd.download(dist, static_cast<size_t>(n) * K);
+    SHARP_API_END
+}
+
+int sharp_tsne_affinities(const double *X, long long n, int d, long long ld, double perplexity, long long cap, long long *row_ptr, int *col,
+                          double *val, long long *nnz) {
+    SHARP_API_BEGIN
+    ctx();
+    check_X(X, n, d, ld);
+    SHARP_REQUIRE(row_ptr && col && val && nnz, "sharp_tsne_affinities: null output");
+    const int K = perplexity_K(perplexity);
+    SHARP_REQUIRE(static_cast<double>(n - 1) >= 3.0 * perplexity, "Perplexity is too large.");
+    DevBuf<double> dX;
+    upload_rows(X, n, d, ld, dX);
+    DevBuf<int> di;
+    DevBuf<double> dd;
+    tsne_knn(dX.p, n, d, K, di, dd);
+    TsneP P;
+    tsne_affinities(di, dd, n, K, perplexity, P);
+    *nnz = P.nnz;
+    SHARP_REQUIRE(cap >= P.nnz, "sharp_tsne_affinities: col / val hold fewer than nnz entries (2 n floor(3 perplexity) always suffice)");
+    P.row_ptr.download(row_ptr, static_cast<size_t>(n) + 1);
+    P.col.download(col, static_cast<size_t>(P.nnz));
+    P.val.download(val, static_cast<size_t>(P.nnz));
+    SHARP_API_END
+}
+
+int sharp_tsne_gradient(const long long *row_ptr, const int *col, const double *val, long long n, int dims, const double *Y, double *dY) {
+    SHARP_API_BEGIN
+    ctx();
+    check_dims(dims);
+    SHARP_REQUIRE(row_ptr && col && val && Y && dY && n >= 2, "sharp_tsne_gradient: null argument");
+    TsneP P;
+    P.n = n;
+    SHARP_REQUIRE(row_ptr[0] == 0 && row_ptr[n] >= 0, "sharp_tsne_gradient: row_ptr must run from 0 to nnz");
+    P.nnz = row_ptr[n];
+    P.row_ptr.alloc(n + 1);
+    P.row_ptr.upload(row_ptr, n + 1);
+    P.col.alloc(std::max<long long>(P.nnz, 1));
+    P.val.alloc(std::max<long long>(P.nnz, 1));
+    if (P.nnz) { P.col.upload(col, P.nnz); P.val.upload(val, P.nnz); }
+    const size_t ne = static_cast<size_t>(n) * dims;
+    for (size_t e = 0; e < ne; ++e) SHARP_REQUIRE(std::isfinite(Y[e]), "sharp_tsne_gradient: Y holds NA / NaN / Inf");
+    for (long long i = 0; i < n; ++i) SHARP_REQUIRE(row_ptr[i] <= row_ptr[i + 1], "sharp_tsne_gradient: row_ptr is not monotone");
+    for (long long e = 0; e < P.nnz; ++e) SHARP_REQUIRE(col[e] >= 0 && col[e] < n, "sharp_tsne_gradient: a column index out of range");
+    DevBuf<double> dYin(ne), dG(ne);
+    dYin.upload(Y, ne);
+    tsne_gradient(P, dYin.p, dims, dG.p);
+    dG.download(dY, ne);
+    SHARP_API_END
+}
+
+}  // extern "C"

@@ -1,0 +1,29 @@
+// tsne.hpp -- the exact t-SNE embedding behind visualization_SHARP (R/visualization_SHARP.R:94 calls Rtsne there): input preparation
+// (PCA, normalisation), exact k-NN on the f64 MFMA, per-row perplexity calibration, the symmetric P in CSR, and the optimiser loop with
+// an exact O(n^2) repulsion.  The C ABI entries (sharp_tsne*, include/sharp_hip.h) are thin wrappers over these.
+#pragma once
+#include "common.hpp"
+
+namespace sharp {
+
+// P = (P_cond + P_cond^T) / sum, CSR on the device (rows sorted by column)
+struct TsneP {
+    long long n = 0, nnz = 0;
+    DevBuf<long long> row_ptr;   // n + 1
+    DevBuf<int> col;             // nnz
+    DevBuf<double> val;          // nnz
+};
+
+// X (n rows of d values, row i at X + i * ld, host) -> the prepared matrix on the device (n x d_out, row-major, ld d_out):
+// PCA to min(initial_dims, d) components if pca, then centring and division by the largest |entry| if normalize
+void tsne_prepare(const double *X, long long n, int d, long long ld, bool pca, int initial_dims, bool pca_center, bool pca_scale,
+                  bool normalize, DevBuf<double> &out, int *d_out);
+// exact K nearest neighbours of every row of dX (n x d, device), self excluded, ties by the lower index; sorted by (distance, index),
+// distances re-ranked as sum (x_i - x_j)^2
+void tsne_knn(const double *dX, long long n, int d, int K, DevBuf<int> &idx, DevBuf<double> &dist);
+// calibration + symmetrisation: P from the k-NN lists
+void tsne_affinities(const DevBuf<int> &idx, const DevBuf<double> &dist, long long n, int K, double perplexity, TsneP &P);
+// dY = sum_j P_ij q_ij (y_i - y_j) - (1/Z) sum_j q_ij^2 (y_i - y_j) at Y (device, n x dims)
+void tsne_gradient(const TsneP &P, const double *dY_in, int dims, double *dGrad);
+
+}  // namespace sharp

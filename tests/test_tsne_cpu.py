@@ -1,0 +1,167 @@
+"""t-SNE without a GPU: the numpy reference of DESIGN.md §10 (tests/_tsne_ref.py) against sklearn and against finite differences,
+the C ABI of sharp_tsne / sharp_C_tsne (declared, exported, failing loudly without a device), visualization_SHARP's x1 and its figure."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import _tsne_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _blobs(n, d, groups, seed, spread=0.3):
+    rng = np.random.default_rng(seed)
+    centres = rng.normal(0, 3, size=(groups, d))
+    lab = rng.integers(0, groups, n)
+    return centres[lab] + spread * rng.normal(size=(n, d)), lab
+
+
+def test_reference_p_matches_sklearn_joint_probabilities_nn():
+    import scipy.sparse as sp
+    from sklearn.manifold._t_sne import _joint_probabilities_nn
+
+    X, _ = _blobs(400, 10, 4, 1)
+    X = ref.normalize(X)
+    perp = 20
+    K = int(np.floor(3 * perp))
+    idx, dist = ref.knn(X, K)
+    n = X.shape[0]
+    D = sp.csr_matrix((dist.ravel(), idx.ravel(), np.arange(0, n * K + 1, K)), shape=(n, n))
+    P_sk = _joint_probabilities_nn(D, perp, 0).toarray()
+    P_ref = ref.joint_p(X, perp).toarray()
+    np.testing.assert_allclose(P_ref, P_sk, rtol=1e-4, atol=1e-4 * P_sk.max())
+    assert abs(P_ref.sum() - 1.0) < 1e-12 and np.allclose(P_ref, P_ref.T, rtol=0, atol=1e-18)
+
+
+def test_reference_gradient_is_the_kl_derivative_over_four():
+    X, _ = _blobs(60, 5, 3, 2)
+    P = ref.joint_p(ref.normalize(X), 5)
+    Y = np.random.default_rng(3).normal(size=(60, 2))
+    g = ref.gradient(P, Y)
+    h = 1e-6
+    fd = np.zeros_like(Y)
+    for i in range(Y.shape[0]):
+        for k in range(2):
+            Yp, Ym = Y.copy(), Y.copy()
+            Yp[i, k] += h
+            Ym[i, k] -= h
+            fd[i, k] = (ref.kl(P, Yp) - ref.kl(P, Ym)) / (2 * h)
+    np.testing.assert_allclose(g, fd / 4.0, rtol=1e-5, atol=1e-5 * np.abs(fd / 4).max())
+
+
+def _declared():
+    src = open(os.path.join(ROOT, "include", "sharp_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return set(re.findall(r"\b(sharp_[A-Za-z0-9_]+)\s*\(", src))
+
+
+@pytest.fixture(scope="module")
+def so():
+    import __graft_entry__ as g
+
+    path = os.path.join(ROOT, "sharp_amd", "libsharp_hip.so")
+    if not os.path.exists(path):
+        g.build()
+    return C.CDLL(path)
+
+
+def test_tsne_entries_declared_and_exported(so):
+    names = _declared()
+    for n in ["sharp_tsne", "sharp_C_tsne", "sharp_tsne_prepare", "sharp_tsne_knn", "sharp_tsne_affinities", "sharp_tsne_gradient"]:
+        assert n in names, n
+        assert hasattr(so, n), n
+
+
+def test_tsne_without_a_device_fails_loudly(so):
+    import torch
+
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    so.sharp_last_error.restype = C.c_char_p
+    X = np.random.default_rng(0).normal(size=(100, 5))
+    Y = np.zeros((100, 2))
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))       # noqa: E731
+    rc = so.sharp_tsne(dp(X), C.c_longlong(100), 5, C.c_longlong(5), 2, 50, 1, 1, 0, 1, 1, C.c_double(10.0), C.c_double(0.5), 10, 250, 250,
+                       C.c_double(0.5), C.c_double(0.8), C.c_double(200.0), C.c_double(12.0), None, C.c_double(10.0), dp(Y), None, None)
+    assert rc != 0 and b"no device context" in so.sharp_last_error()
+    st = np.array([-1], np.int32)
+    P = lambda a: a.ctypes.data_as(C.c_void_p)                      # noqa: E731
+    I = lambda v: np.array([v], np.int32)                           # noqa: E731
+    D = lambda v: np.array([v], np.float64)                         # noqa: E731
+    so.sharp_C_tsne.restype = None
+    ic, costs = np.zeros(20), np.zeros(100)
+    args = [X, D(100), I(5), I(2), I(50), I(1), I(1), I(0), I(1), I(1), D(10.0), D(0.5), I(10), I(250), I(250), D(0.5), D(0.8), D(200.0),
+            D(12.0), I(0), np.zeros(1), D(10.0), Y, ic, costs, st]
+    so.sharp_C_tsne(*[P(a) for a in args])
+    assert st[0] != 0
+    import sharp_amd
+
+    with pytest.raises(sharp_amd.SharpError):
+        sharp_amd.Rtsne(X, perplexity=10, max_iter=10)
+
+
+def _result(n=80, p=7, ncl=3, seed=4, sparse=False):
+    rng = np.random.default_rng(seed)
+    lab = rng.integers(1, ncl + 1, n)
+    lab[:ncl] = np.arange(1, ncl + 1)
+    x0 = np.eye(ncl)[lab - 1]
+    if sparse:
+        import scipy.sparse as sp
+
+        x0 = sp.csr_matrix(x0)
+    return {"x0": x0, "viE": rng.normal(size=(n, p)), "pred_clusters": lab}
+
+
+def test_vis_input_three_branches_against_numpy():
+    from sharp_amd.api import _vis_input
+
+    y = _result()
+    x0, viE = y["x0"], y["viE"]
+    sc = lambda a: (a - a.mean(0)) / a.std(0, ddof=1)                # noqa: E731
+    np.testing.assert_allclose(_vis_input(y, 2), np.hstack([2 * sc(x0), sc(viE)]), rtol=1e-14, atol=1e-14)
+    np.testing.assert_allclose(_vis_input(y, 0.5), np.hstack([0.5 * sc(x0), sc(viE)]), rtol=1e-14, atol=1e-14)
+    assert np.array_equal(_vis_input(y, 0.01), viE)
+    j = _vis_input(y, 100)
+    z = x0.max() - x0.min()
+    assert j.shape == x0.shape and np.abs(j - x0).max() <= z / 50 and np.abs(j - x0).max() > 0
+    ys = _result(sparse=True)
+    np.testing.assert_allclose(_vis_input(ys, 2), _vis_input(y, 2), rtol=0, atol=0)
+    np.testing.assert_allclose(_vis_input(ys, 1000), _vis_input(y, 1000), rtol=0, atol=0)
+
+
+def test_vis_input_constant_column_is_an_error_naming_it():
+    import sharp_amd
+    from sharp_amd.api import _vis_input
+
+    y = _result()
+    y["viE"][:, 4] = 1.5
+    with pytest.raises(sharp_amd.SharpError, match="column 5 of viE"):
+        _vis_input(y, 2)
+    y = _result()
+    y["x0"] = np.hstack([y["x0"], np.zeros((y["x0"].shape[0], 1))])
+    with pytest.raises(sharp_amd.SharpError, match="column 4 of x0"):
+        _vis_input(y, 2)
+
+
+@pytest.mark.parametrize("filetype", ["png", "pdf"])
+def test_figure_from_given_coordinates(tmp_path, filetype):
+    from sharp_amd.api import _draw_sharp_map, vis_colors
+
+    assert len(vis_colors) == 40 and vis_colors[0] == "black" and vis_colors[-1] == "lightcyan"
+    import sys
+
+    had_pyplot = "matplotlib.pyplot" in sys.modules
+    Y = np.random.default_rng(5).normal(size=(300, 2))
+    lab = np.repeat(np.arange(45), 300 // 45 + 1)[:300]            # more labels than colours: recycled
+    f1 = str(tmp_path / f"lab.{filetype}")
+    _draw_sharp_map(Y, lab, f1, filetype, res=50)
+    f2 = str(tmp_path / f"nolab.{filetype}")
+    _draw_sharp_map(Y, None, f2, filetype, res=50)
+    assert "matplotlib.pyplot" not in sys.modules or had_pyplot       # the figure leaves pyplot (and its backend) alone
+    magic = b"\x89PNG" if filetype == "png" else b"%PDF"
+    for f in (f1, f2):
+        assert os.path.getsize(f) > 1000
+        assert open(f, "rb").read(4) == magic

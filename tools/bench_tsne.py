@@ -1,0 +1,84 @@
+"""Per-stage timing of sharp_tsne (the Rtsne behind visualization_SHARP) on synthetic x1 matrices of the clustering configurations'
+forview outputs.  One JSON line per size on stdout.
+
+    python tools/bench_tsne.py --n 50000 --d 400 --iters 200      # cfg2's x1: ncl + p ~ 400 columns, through PCA to 50
+    python tools/bench_tsne.py --n 500000 --d 70 --iters 30       # cfg3's x1: ncl + 50 columns
+
+Stages come from the library's per-kernel HIP-event timers (sharp_profile_*); total_ms is a second, unprofiled call timed on a
+synchronised host clock.  Per-iteration figures are the timer totals over the calls they cover; total_1000_est_ms extrapolates the
+unprofiled call to max_iter = 1000 from its measured parts (marked as an estimate)."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def synth_x1(n, d, ncl, seed):
+    """cbind(w * scale(x0), scale(viE))-like: ncl one-hot cluster columns (weighted) + d - ncl noisy projections of cluster centres"""
+    rng = np.random.default_rng(seed)
+    lab = rng.integers(0, ncl, n)
+    p = d - ncl
+    centres = rng.normal(0, 1, size=(ncl, p))
+    viE = centres[lab] + 0.5 * rng.normal(size=(n, p))
+    x0 = np.zeros((n, ncl))
+    x0[np.arange(n), lab] = 1.0
+    return np.hstack([2 * (x0 - x0.mean(0)) / x0.std(0, ddof=1), (viE - viE.mean(0)) / viE.std(0, ddof=1)])
+
+
+def stat(L, name):
+    ms, k = C.c_double(), C.c_longlong()
+    L.sharp_profile_get(name.encode(), C.byref(ms), C.byref(k))
+    return ms.value, k.value
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=50000)
+    ap.add_argument("--d", type=int, default=400)
+    ap.add_argument("--ncl", type=int, default=20)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--seed", type=int, default=1)
+    a = ap.parse_args()
+    import sharp_amd
+
+    sharp_amd.init(0)
+    L = sharp_amd.lib()
+    X = synth_x1(a.n, a.d, a.ncl, a.seed)
+    kw = dict(perplexity=30, max_iter=a.iters, check_duplicates=False, pca=a.d > 50)
+    sharp_amd.Rtsne(X[: min(a.n, 2000)], **dict(kw, max_iter=2))       # first call: code objects, allocations
+    L.sharp_profile_enable(1)
+    L.sharp_profile_reset()
+    sharp_amd.Rtsne(X, **kw)
+    L.sharp_synchronize()
+    st = {k: stat(L, k) for k in ["tsne_pca", "tsne_normalize", "tsne_knn", "tsne_calib", "tsne_sym", "tsne_attr", "tsne_rep", "tsne_update",
+                                  "tsne_kl"]}
+    eig = stat(L, "host:tsne_pca_eigen")
+    L.sharp_profile_enable(0)
+    t0 = time.perf_counter()
+    sharp_amd.Rtsne(X, **kw)
+    total = (time.perf_counter() - t0) * 1e3
+    per = lambda k: st[k][0] / max(st[k][1], 1)                       # noqa: E731
+    iter_ms = per("tsne_attr") + per("tsne_rep") + per("tsne_update")
+    fixed = st["tsne_pca"][0] + st["tsne_normalize"][0] + st["tsne_knn"][0] + st["tsne_calib"][0] + st["tsne_sym"][0]
+    loop = total - fixed
+    out = {"n": a.n, "d": a.d, "dims": 2, "perplexity": 30, "iters": a.iters,
+           "pca_ms": round(st["tsne_pca"][0], 3), "pca_eigen_host_ms": round(eig[0], 3), "normalize_ms": round(st["tsne_normalize"][0], 3),
+           "knn_ms": round(st["tsne_knn"][0], 3), "calib_ms": round(st["tsne_calib"][0], 3), "sym_ms": round(st["tsne_sym"][0], 3),
+           "attr_ms_per_iter": round(per("tsne_attr"), 4), "rep_ms_per_iter": round(per("tsne_rep"), 4),
+           "update_ms_per_iter": round(per("tsne_update"), 4), "kl_ms_per_eval": round(per("tsne_kl"), 4),
+           "iter_ms": round(iter_ms, 4), "rep_pairs_per_s": float(f"{a.n * a.n / (per('tsne_rep') * 1e-3):.4g}"),
+           "knn_pairs_per_s": float(f"{a.n * a.n / (st['tsne_knn'][0] * 1e-3):.4g}"),
+           "total_ms": round(total, 2), "loop_ms_per_iter_unprofiled": round(loop / max(a.iters, 1), 4),
+           "total_1000_est_ms": round(fixed + 1000 * loop / max(a.iters, 1), 1), "total_1000_is_estimate": a.iters != 1000}
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
