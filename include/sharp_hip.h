@@ -386,6 +386,16 @@ int sharp_tsne_knn(const double *X, long long n, int d, long long ld, int K, int
 int sharp_tsne_affinities(const double *X, long long n, int d, long long ld, double perplexity, long long cap, long long *row_ptr, int *col,
                           double *val, long long *nnz);
 int sharp_tsne_gradient(const long long *row_ptr, const int *col, const double *val, long long n, int dims, const double *Y, double *dY);
+/* sharp_tsne with bhtsne's Barnes-Hut repulsion (DESIGN.md §10 "Barnes-Hut"): theta is honoured.  0 < theta <= 1: a quadtree (octree
+ * in 3-D) of Y rebuilt at every gradient evaluation, O(n log n) work per iteration; theta == 0: exactly sharp_tsne; theta outside
+ * [0, 1] or not finite: "Incorrect theta." (SHARP_ERR_ARG).  Same arguments and outputs as sharp_tsne; bitwise reproducible on one GPU. */
+int sharp_tsne_bh(const double *X, long long n, int d, long long ld, int dims, int initial_dims, int pca, int pca_center, int pca_scale,
+                  int normalize, int check_duplicates, double perplexity, double theta, int max_iter, int stop_lying_iter, int mom_switch_iter,
+                  double momentum, double final_momentum, double eta, double exaggeration, const double *Y_init, double seed, double *Y,
+                  double *itercosts, double *costs);
+/* The gradient stage with that repulsion: dY (n x dims) at Y for P; Z (NULL or one double) receives the normalisation Z it used. */
+int sharp_tsne_gradient_bh(const long long *row_ptr, const int *col, const double *val, long long n, int dims, const double *Y, double theta,
+                           double *dY, double *Z);
 
 /* ---- synthetic inputs (bench / tests; not part of the reference) ------------ */
 /* Counter-based generator, value = f(seed, gene, cell): bit-identical to
@@ -481,6 +491,11 @@ void sharp_C_tsne(double *X, double *n, int *d, int *dims, int *initial_dims, in
                   int *check_duplicates, double *perplexity, double *theta, int *max_iter, int *stop_lying_iter, int *mom_switch_iter,
                   double *momentum, double *final_momentum, double *eta, double *exaggeration, int *has_Y_init, double *Y_init, double *seed,
                   double *Y, double *itercosts, double *costs, int *status);
+/* sharp_tsne_bh in the same convention: sharp_C_tsne's arguments, theta honoured */
+void sharp_C_tsne_bh(double *X, double *n, int *d, int *dims, int *initial_dims, int *pca, int *pca_center, int *pca_scale, int *normalize,
+                     int *check_duplicates, double *perplexity, double *theta, int *max_iter, int *stop_lying_iter, int *mom_switch_iter,
+                     double *momentum, double *final_momentum, double *eta, double *exaggeration, int *has_Y_init, double *Y_init, double *seed,
+                     double *Y, double *itercosts, double *costs, int *status);
 
 #ifdef __cplusplus
 }

@@ -279,12 +279,16 @@ sharp_last_decisions <- function(cap = 65536L) {
 }
 
 # Rtsne(x1, ...) as R/visualization_SHARP.R:94 calls it: replace `Rtsne(` there by `sharp_Rtsne(`.  Rtsne's formals and return list;
-# exact repulsion on the GPU (theta accepted and unused, DESIGN.md 10), Y drawn from set.seed(seed)'s stream when Y_init is NULL.
+# Y drawn from set.seed(seed)'s stream when Y_init is NULL.  repulsion = "exact": the exact repulsion on the GPU (theta accepted and
+# unused, DESIGN.md 10); "barnes_hut": bhtsne's Barnes-Hut repulsion with theta honoured (sharp_C_tsne_bh).
 sharp_Rtsne <- function(X, dims = 2, initial_dims = 50, perplexity = 30, theta = 0.5, check_duplicates = TRUE, pca = TRUE,
                         partial_pca = FALSE, max_iter = 1000, verbose = getOption("verbose", FALSE), is_distance = FALSE, Y_init = NULL,
                         pca_center = TRUE, pca_scale = FALSE, normalize = TRUE,
                         stop_lying_iter = ifelse(is.null(Y_init), 250L, 0L), mom_switch_iter = ifelse(is.null(Y_init), 250L, 0L),
-                        momentum = 0.5, final_momentum = 0.8, eta = 200, exaggeration_factor = 12, num_threads = 1, seed = 10, ...) {
+                        momentum = 0.5, final_momentum = 0.8, eta = 200, exaggeration_factor = 12, num_threads = 1, seed = 10,
+                        repulsion = "exact", ...) {
+    entry <- switch(repulsion, exact = "sharp_C_tsne", barnes_hut = "sharp_C_tsne_bh",
+                    stop("sharp_Rtsne: repulsion must be \"exact\" or \"barnes_hut\""))
     if (is_distance) stop("sharp_Rtsne: is_distance = TRUE is not supported")
     X <- .sharp_dmat(X)
     n <- nrow(X); d <- ncol(X)
@@ -292,7 +296,7 @@ sharp_Rtsne <- function(X, dims = 2, initial_dims = 50, perplexity = 30, theta =
     if (has_init && !all(dim(Y_init) == c(n, dims))) stop("Y_init must be an n x dims matrix")
     iters <- seq_len(max_iter) - 1L
     ncost <- sum((iters > 0 & iters %% 50 == 0) | iters == max_iter - 1L)
-    r <- .C("sharp_C_tsne", as.double(t(X)), as.double(n), as.integer(d), as.integer(dims), as.integer(initial_dims), as.integer(pca),
+    r <- .C(entry, as.double(t(X)), as.double(n), as.integer(d), as.integer(dims), as.integer(initial_dims), as.integer(pca),
             as.integer(pca_center), as.integer(pca_scale), as.integer(normalize), as.integer(check_duplicates), as.double(perplexity),
             as.double(theta), as.integer(max_iter), as.integer(stop_lying_iter), as.integer(mom_switch_iter), as.double(momentum),
             as.double(final_momentum), as.double(eta), as.double(exaggeration_factor), as.integer(has_init),

@@ -1017,7 +1017,8 @@ def visualization_SHARP(y, label=None, w=2, filename=None, filetype=None, n_core
     """R/visualization_SHARP.R:31-177: the 2-D t-SNE map of a SHARP() / SHARP_unlimited() result.
 
     x1 = cbind(w * scale(x0), scale(viE)) (w >= 100: x0 with jitter; w <= 0.01: viE alone) goes to Rtsne(x1, check_duplicates = FALSE,
-    pca = ncol(x1) > 50, **tsne_kwargs) on the GPU (sharp_amd.tsne.Rtsne: exact repulsion, O(n^2) per iteration).  The figure (pdf
+    pca = ncol(x1) > 50, **tsne_kwargs) on the GPU (sharp_amd.tsne.Rtsne: exact repulsion, O(n^2) per iteration; repulsion="barnes_hut"
+    in tsne_kwargs takes bhtsne's Barnes-Hut repulsion at Rtsne's theta = 0.5, O(n log n) per iteration).  The figure (pdf
     below 5000 cells, png otherwise; default name vi_SHARP.<type>) is drawn with matplotlib; plot=False skips it.  n_cores is accepted
     and ignored.  Returns {"Y", "itercosts", "filename", "time"} (time in minutes, as R reports it)."""
     import time as _t

@@ -234,4 +234,14 @@ void sharp_C_tsne(double *X, double *n, int *d, int *dims, int *initial_dims, in
                          *exaggeration, *has_Y_init ? Y_init : nullptr, *seed, Y, itercosts, costs);
 }
 
+/* ---- Rtsne with its Barnes-Hut repulsion (sharp_tsne_bh), sharp_C_tsne's arguments */
+void sharp_C_tsne_bh(double *X, double *n, int *d, int *dims, int *initial_dims, int *pca, int *pca_center, int *pca_scale, int *normalize,
+                     int *check_duplicates, double *perplexity, double *theta, int *max_iter, int *stop_lying_iter, int *mom_switch_iter,
+                     double *momentum, double *final_momentum, double *eta, double *exaggeration, int *has_Y_init, double *Y_init, double *seed,
+                     double *Y, double *itercosts, double *costs, int *status) {
+    *status = sharp_tsne_bh(X, as_ll(n), *d, static_cast<long long>(*d), *dims, *initial_dims, *pca, *pca_center, *pca_scale, *normalize,
+                            *check_duplicates, *perplexity, *theta, *max_iter, *stop_lying_iter, *mom_switch_iter, *momentum, *final_momentum, *eta,
+                            *exaggeration, *has_Y_init ? Y_init : nullptr, *seed, Y, itercosts, costs);
+}
+
 }  // extern "C"

@@ -22,6 +22,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_reduce_by_key.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include "linalg.hpp"
 #include "rrng.hpp"
@@ -673,6 +674,275 @@ __global__ __launch_bounds__(256) void kl_kernel(const long long *__restrict__ r
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// Barnes-Hut repulsion (DESIGN.md §10 "Barnes-Hut"): bhtsne's SPTree as a compressed 2^DIMS-ary tree over quantised Morton keys,
+// rebuilt from the fp64 Y at every gradient evaluation and laid out in preorder with a skip index per node, so that one lane per point
+// walks it without a stack.  fp64 throughout; every sum in an order fixed by n and the keys; no atomics, no inter-workgroup flags.
+// ---------------------------------------------------------------------------------------------------------------------------
+template <int DIMS> struct BhBits { static constexpr int value = DIMS == 1 ? 63 : (DIMS == 2 ? 32 : 21); };   // levels below the root
+constexpr int kBhSlabs = 256;        // slabs of the bounding-box reduction
+constexpr int kBhRadix = 32;         // chunk length of the layered sums behind the centres of mass
+constexpr int kBhMaxLayers = 8;      // 32^7 > 2^31 rows
+constexpr unsigned kBhInternal = 0xFFFFFFFFu;   // meta.z of an internal node (a leaf holds its lowest point index there)
+
+// layer 0: the sorted Y (n x DIMS); layer l + 1: sums of kBhRadix consecutive entries of layer l, in order
+struct BhLayers {
+    const double *p[kBhMaxLayers];
+    long long len[kBhMaxLayers];
+    int nl;
+};
+
+// slab b: per-dimension sum, min and max of Y's rows [b rps, (b + 1) rps) -> part[b * 3 DIMS + {k, DIMS + k, 2 DIMS + k}]
+template <int DIMS>
+__global__ __launch_bounds__(256) void bh_bounds_kernel(const double *__restrict__ Y, long long n, long long rps, double *__restrict__ part) {
+    __shared__ double s[3 * DIMS][256];
+    const int tid = threadIdx.x;
+    const long long r0 = static_cast<long long>(blockIdx.x) * rps, r1 = r0 + rps < n ? r0 + rps : n;
+    double a[3 * DIMS];
+#pragma unroll
+    for (int k = 0; k < DIMS; ++k) { a[k] = 0.0; a[DIMS + k] = DBL_MAX; a[2 * DIMS + k] = -DBL_MAX; }
+    for (long long r = r0 + tid; r < r1; r += 256)
+#pragma unroll
+        for (int k = 0; k < DIMS; ++k) {
+            const double v = Y[r * DIMS + k];
+            a[k] += v;
+            a[DIMS + k] = fmin(a[DIMS + k], v);
+            a[2 * DIMS + k] = fmax(a[2 * DIMS + k], v);
+        }
+#pragma unroll
+    for (int k = 0; k < 3 * DIMS; ++k) s[k][tid] = a[k];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w)
+#pragma unroll
+            for (int k = 0; k < DIMS; ++k) {
+                s[k][tid] += s[k][tid + w];
+                s[DIMS + k][tid] = fmin(s[DIMS + k][tid], s[DIMS + k][tid + w]);
+                s[2 * DIMS + k][tid] = fmax(s[2 * DIMS + k][tid], s[2 * DIMS + k][tid + w]);
+            }
+        __syncthreads();
+    }
+    if (tid < 3 * DIMS) part[static_cast<long long>(blockIdx.x) * 3 * DIMS + tid] = s[tid][0];
+}
+
+// the root cell (bhtsne's SPTree constructor): centre = mean, half-width w_d = max(max - mean, mean - min) + 1e-5.
+// root[3 + k] = mean - w (the lower corner), root[6 + k] = 2^bits / (2 w) (finest cells per unit), root[9] = max_d w_d
+template <int DIMS>
+__global__ void bh_root_kernel(const double *__restrict__ part, int nslab, long long n, double *__restrict__ root) {
+    if (threadIdx.x != 0) return;
+    double wmax = 0.0;
+    for (int k = 0; k < DIMS; ++k) {
+        double sum = 0.0, mn = DBL_MAX, mx = -DBL_MAX;
+        for (int b = 0; b < nslab; ++b) {
+            sum += part[b * 3 * DIMS + k];
+            mn = fmin(mn, part[b * 3 * DIMS + DIMS + k]);
+            mx = fmax(mx, part[b * 3 * DIMS + 2 * DIMS + k]);
+        }
+        const double mean = sum / static_cast<double>(n);
+        const double w = fmax(mx - mean, mean - mn) + 1e-5;
+        root[k] = mean;
+        root[3 + k] = mean - w;
+        root[6 + k] = ldexp(1.0, BhBits<DIMS>::value) / (2.0 * w);
+        wmax = fmax(wmax, w);
+    }
+    root[9] = wmax;
+}
+
+// key[i]: the finest cell of y_i as a Morton key.  Per dimension c = floor((y - lower corner) * cells per unit), clamped to the grid
+// (a point on a midline goes to the upper half), then inverted so that the upper half sorts first: digit L (from the top) holds bit
+// (bits - L) of every dimension, dimension k at bit k -- bhtsne's child number, so ascending keys visit children in bhtsne's order.
+template <int DIMS>
+__global__ __launch_bounds__(256) void bh_key_kernel(const double *__restrict__ Y, long long n, const double *__restrict__ root,
+                                                     unsigned long long *__restrict__ key) {
+    constexpr int bits = BhBits<DIMS>::value;
+    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double lim = ldexp(1.0, bits);
+    const unsigned long long top = (1ull << bits) - 1ull;
+    unsigned long long c[DIMS];
+#pragma unroll
+    for (int k = 0; k < DIMS; ++k) {
+        const double t = (Y[i * DIMS + k] - root[3 + k]) * root[6 + k];
+        const unsigned long long u = t >= lim ? top : (t >= 0.0 ? static_cast<unsigned long long>(t) : 0ull);   // (NaN: 0)
+        c[k] = top - u;
+    }
+    unsigned long long K = 0;
+    for (int b = bits - 1; b >= 0; --b)
+#pragma unroll
+        for (int k = 0; k < DIMS; ++k) K |= ((c[k] >> b) & 1ull) << (b * DIMS + k);
+    key[i] = K;
+}
+
+__global__ __launch_bounds__(256) void iota_kernel(int *__restrict__ v, long long n) {
+    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (i < n) v[i] = static_cast<int>(i);
+}
+
+template <int DIMS>
+__global__ __launch_bounds__(256) void bh_gather_kernel(const double *__restrict__ Y, const int *__restrict__ perm, long long n, double *__restrict__ Ys) {
+    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= n * DIMS) return;
+    const long long s = e / DIMS;
+    Ys[e] = Y[static_cast<long long>(perm[s]) * DIMS + (e - s * DIMS)];
+}
+
+template <int DIMS>
+__global__ __launch_bounds__(256) void bh_layer_kernel(const double *__restrict__ in, long long len_in, double *__restrict__ out, long long len_out) {
+    const long long c = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (c >= len_out) return;
+    const long long t0 = c * kBhRadix, t1 = t0 + kBhRadix < len_in ? t0 + kBhRadix : len_in;
+    double a[DIMS];
+#pragma unroll
+    for (int k = 0; k < DIMS; ++k) a[k] = 0.0;
+    for (long long t = t0; t < t1; ++t)
+#pragma unroll
+        for (int k = 0; k < DIMS; ++k) a[k] += in[t * DIMS + k];
+#pragma unroll
+    for (int k = 0; k < DIMS; ++k) out[c * DIMS + k] = a[k];
+}
+
+// sum of sorted rows [a, b) from the layers: the partial chunks at each end of a layer, then the whole chunks one layer up
+template <int DIMS>
+__device__ void bh_range_sum(const BhLayers &Ls, long long a, long long b, double *acc) {
+    for (int l = 0;; ++l) {
+        const double *p = Ls.p[l];
+        const long long au = (a + kBhRadix - 1) / kBhRadix * kBhRadix, bd = b / kBhRadix * kBhRadix;
+        if (l + 1 >= Ls.nl || au >= bd) {
+            for (long long t = a; t < b; ++t)
+#pragma unroll
+                for (int k = 0; k < DIMS; ++k) acc[k] += p[t * DIMS + k];
+            return;
+        }
+        for (long long t = a; t < au; ++t)
+#pragma unroll
+            for (int k = 0; k < DIMS; ++k) acc[k] += p[t * DIMS + k];
+        for (long long t = bd; t < b; ++t)
+#pragma unroll
+            for (int k = 0; k < DIMS; ++k) acc[k] += p[t * DIMS + k];
+        a = au / kBhRadix;
+        b = bd / kBhRadix;
+    }
+}
+
+// leading digits two keys share (bits when they are equal)
+template <int DIMS>
+__device__ __forceinline__ int bh_lcp(unsigned long long a, unsigned long long b) {
+    if (a == b) return BhBits<DIMS>::value;
+    return BhBits<DIMS>::value - 1 - (63 - __builtin_clzll(a ^ b)) / DIMS;
+}
+
+// the first sorted position after s outside the level-L cell of key[s]: galloping, then bisection
+template <int DIMS>
+__device__ long long bh_cell_end(const unsigned long long *__restrict__ key, long long n, long long s, int L) {
+    if (L == 0) return n;
+    const unsigned long long v = key[s] | ((1ull << ((BhBits<DIMS>::value - L) * DIMS)) - 1ull);
+    long long a = s, b, step = 1;   // key[a] <= v; key[b] > v or b == n
+    for (;;) {
+        b = a + step;
+        if (b >= n) { b = n; break; }
+        if (key[b] > v) break;
+        a = b;
+        step *= 2;
+    }
+    while (b - a > 1) {
+        const long long m = a + (b - a) / 2;
+        if (key[m] <= v) a = m; else b = m;
+    }
+    return b;
+}
+
+// The nodes of the compressed tree that start at the sorted position s of a run of equal keys: f(level, end) for each internal node,
+// outermost first (a chain of cells with one non-empty child is one node, at the level of its deepest cell), then f(bits, end) for the
+// leaf, the run itself.  Cells at levels <= lcp(key[s - 1], key[s]) start before s.
+template <int DIMS, class F>
+__device__ void bh_chain(const unsigned long long *__restrict__ key, long long n, long long s, F f) {
+    constexpr int bits = BhBits<DIMS>::value;
+    int L = s == 0 ? 0 : bh_lcp<DIMS>(key[s - 1], key[s]) + 1;
+    while (L < bits) {
+        const long long e = bh_cell_end<DIMS>(key, n, s, L);
+        const int g = bh_lcp<DIMS>(key[s], key[e - 1]);   // the deepest level of the chain: its cells all hold [s, e)
+        if (g >= bits) break;
+        f(g, e);
+        L = g + 1;
+    }
+    f(bits, bh_cell_end<DIMS>(key, n, s, bits));
+}
+
+__device__ __forceinline__ bool bh_run_start(const unsigned long long *__restrict__ key, long long s) { return s == 0 || key[s] != key[s - 1]; }
+
+// cnt[s]: nodes that start at sorted position s (0 unless s starts a run; cnt[n] = 0)
+template <int DIMS>
+__global__ __launch_bounds__(256) void bh_count_kernel(const unsigned long long *__restrict__ key, long long n, unsigned *__restrict__ cnt) {
+    const long long s = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (s > n) return;
+    unsigned c = 0;
+    if (s < n && bh_run_start(key, s)) bh_chain<DIMS>(key, n, s, [&](int, long long) { ++c; });
+    cnt[s] = c;
+}
+
+// The nodes in preorder: those starting at s go to off[s], off[s] + 1, ... (off: exclusive scan of cnt, off[n] = node count).  A node
+// holding sorted rows [s, e) skips to off[e], the first node that starts at or after e.  meta = (points, skip, lowest point index of a
+// leaf or kBhInternal, level); com: the centre of mass (fp64 sum from the layers / count).
+template <int DIMS>
+__global__ __launch_bounds__(256) void bh_node_kernel(const unsigned long long *__restrict__ key, const int *__restrict__ perm, long long n,
+                                                      const unsigned *__restrict__ off, BhLayers Ls, uint4 *__restrict__ meta,
+                                                      double *__restrict__ com) {
+    const long long s = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (s >= n || !bh_run_start(key, s)) return;
+    unsigned o = off[s];
+    bh_chain<DIMS>(key, n, s, [&](int level, long long e) {
+        const bool leaf = level == BhBits<DIMS>::value;
+        meta[o] = make_uint4(static_cast<unsigned>(e - s), off[e], leaf ? static_cast<unsigned>(perm[s]) : kBhInternal, static_cast<unsigned>(level));
+        double acc[DIMS];
+#pragma unroll
+        for (int k = 0; k < DIMS; ++k) acc[k] = 0.0;
+        bh_range_sum<DIMS>(Ls, s, e, acc);
+#pragma unroll
+        for (int k = 0; k < DIMS; ++k) com[static_cast<size_t>(o) * DIMS + k] = acc[k] / static_cast<double>(e - s);
+        ++o;
+    });
+}
+
+// One lane per point, lanes in sorted-key order: bhtsne's computeNonEdgeForces over the preorder layout.  A leaf whose lowest index is
+// i is skipped; a leaf, or an internal node with max_d(half-width) / sqrt(D) < theta, is a summary (cnt q to z, cnt q^2 (y_i - com) to
+// the repulsion; k = skip); otherwise the walk enters its first child (k + 1).  rep / zrow as rep_kernel + fold_kernel leave them.
+template <int DIMS>
+__global__ __launch_bounds__(256) void bh_walk_kernel(const double *__restrict__ Ys, const int *__restrict__ perm, long long n,
+                                                      const uint4 *__restrict__ meta, const double *__restrict__ com,
+                                                      const double *__restrict__ root, double theta, double *__restrict__ rep,
+                                                      double *__restrict__ zrow) {
+    const long long s = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (s >= n) return;
+    const unsigned i = static_cast<unsigned>(perm[s]);
+    double yi[DIMS], f[DIMS], z = 0.0;
+#pragma unroll
+    for (int k = 0; k < DIMS; ++k) { yi[k] = Ys[s * DIMS + k]; f[k] = 0.0; }
+    const double wmax = root[9];
+    const unsigned M = meta[0].y;   // the root's skip: the node count
+    unsigned k = 0;
+    while (k < M) {
+        const uint4 m = meta[k];
+        if (m.z == i) { k = m.y; continue; }
+        double d[DIMS], D = 0.0;
+#pragma unroll
+        for (int c = 0; c < DIMS; ++c) { d[c] = yi[c] - com[static_cast<size_t>(k) * DIMS + c]; D += d[c] * d[c]; }
+        if (m.z != kBhInternal || ldexp(wmax, -static_cast<int>(m.w)) / sqrt(D) < theta) {
+            const double q = 1.0 / (1.0 + D);
+            double mult = static_cast<double>(m.x) * q;
+            z += mult;
+            mult *= q;
+#pragma unroll
+            for (int c = 0; c < DIMS; ++c) f[c] += mult * d[c];
+            k = m.y;
+        } else {
+            ++k;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < DIMS; ++c) rep[static_cast<long long>(i) * DIMS + c] = f[c];
+    zrow[i] = z;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------------------------------------------
 struct RepPlan {
@@ -692,24 +962,105 @@ RepPlan rep_plan(long long n) {
     return p;
 }
 
+// the Barnes-Hut tree's buffers, allocated once per call (at most 2n - 1 nodes)
+struct BhTree {
+    DevBuf<unsigned long long> key, key_s;
+    DevBuf<int> iota, perm;
+    DevBuf<double> Ys, lay, part, root, com;
+    DevBuf<unsigned> cnt, off;
+    DevBuf<uint4> meta;
+    DevBuf<unsigned char> sort_tmp, scan_tmp;
+    size_t sort_bytes = 0, scan_bytes = 0;
+    BhLayers L{};
+    int nslab = 1, end_bit = 64;
+    long long rps = 1;
+    void init(long long n, int dims) {
+        Ctx &c = ctx();
+        const size_t nn = static_cast<size_t>(n);
+        key.alloc(nn); key_s.alloc(nn); iota.alloc(nn); perm.alloc(nn);
+        Ys.alloc(nn * dims);
+        cnt.alloc(nn + 1); off.alloc(nn + 1);
+        meta.alloc(2 * nn); com.alloc(2 * nn * dims);
+        root.alloc(16);
+        nslab = static_cast<int>(std::min<long long>(kBhSlabs, std::max<long long>(1, n / 256)));
+        rps = (n + nslab - 1) / nslab;
+        nslab = static_cast<int>((n + rps - 1) / rps);
+        part.alloc(static_cast<size_t>(nslab) * 3 * dims);
+        std::vector<long long> len{n}, at{0};
+        long long total = 0;
+        while (len.back() > kBhRadix) {
+            at.push_back(total);
+            len.push_back((len.back() + kBhRadix - 1) / kBhRadix);
+            total += len.back();
+        }
+        SHARP_REQUIRE(len.size() <= static_cast<size_t>(kBhMaxLayers), "tsne_bh: too many rows");
+        lay.alloc(std::max<size_t>(1, static_cast<size_t>(total) * dims));
+        L.nl = static_cast<int>(len.size());
+        for (int l = 0; l < L.nl; ++l) {
+            L.len[l] = len[l];
+            L.p[l] = l == 0 ? Ys.p : lay.p + at[l] * dims;
+        }
+        end_bit = dims == 1 ? 63 : (dims == 2 ? 64 : 63);
+        hipLaunchKernelGGL(iota_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, iota.p, n);
+        launch_check("iota_kernel");
+        SHARP_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, key.p, key_s.p, iota.p, perm.p, nn, 0, end_bit, c.stream));
+        sort_tmp.alloc(std::max<size_t>(sort_bytes, 1));
+        SHARP_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, cnt.p, off.p, 0u, nn + 1, rocprim::plus<unsigned>(), c.stream));
+        scan_tmp.alloc(std::max<size_t>(scan_bytes, 1));
+    }
+};
+
 struct Work {
     long long n = 0;
     int dims = 2;
     RepPlan plan;
     DevBuf<double> Y, uY, gains, attr, rep, zrow, kl, part, red, scal, colpart;   // scal: [0] Z, [1] KL sum, [2..] mean
     DevBuf<float> Yf;
-    void init(long long n_, int dims_) {
+    double theta = 0.0;   // > 0: the Barnes-Hut repulsion with this theta instead of the exact one
+    BhTree bh;
+    void init(long long n_, int dims_, double theta_ = 0.0) {
         n = n_;
         dims = dims_;
+        theta = theta_;
         plan = rep_plan(n);
         const size_t ne = static_cast<size_t>(n) * dims;
         Y.alloc(ne); uY.alloc(ne); gains.alloc(ne); attr.alloc(ne); rep.alloc(ne); Yf.alloc(ne);
         zrow.alloc(n); kl.alloc(n);
-        part.alloc(static_cast<size_t>(plan.nc) * plan.rows * 4);
+        if (theta > 0.0) bh.init(n, dims);
+        else part.alloc(static_cast<size_t>(plan.nc) * plan.rows * 4);
         red.alloc(kSumBlocks);
         scal.alloc(8);
     }
 };
+
+// the tree at the current Y (DESIGN.md §10 "Barnes-Hut"): bounding box and mean, keys, stable sort, sorted Y and its layered sums,
+// node counts per run start, their scan, the nodes
+template <int DIMS>
+void bh_build(Work &w) {
+    Ctx &c = ctx();
+    BhTree &t = w.bh;
+    const long long n = w.n;
+    KernelTimer tm("tsne_bh_tree");
+    hipLaunchKernelGGL(bh_bounds_kernel<DIMS>, dim3(t.nslab), dim3(256), 0, c.stream, w.Y.p, n, t.rps, t.part.p);
+    hipLaunchKernelGGL(bh_root_kernel<DIMS>, dim3(1), dim3(64), 0, c.stream, t.part.p, t.nslab, n, t.root.p);
+    hipLaunchKernelGGL(bh_key_kernel<DIMS>, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, w.Y.p, n, t.root.p, t.key.p);
+    launch_check("bh_key_kernel");
+    size_t bytes = t.sort_bytes;
+    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(t.sort_tmp.p, bytes, t.key.p, t.key_s.p, t.iota.p, t.perm.p, static_cast<size_t>(n), 0, t.end_bit,
+                                              c.stream));
+    hipLaunchKernelGGL(bh_gather_kernel<DIMS>, dim3(grid_for(n * DIMS, 256)), dim3(256), 0, c.stream, w.Y.p, t.perm.p, n, t.Ys.p);
+    for (int l = 1; l < t.L.nl; ++l)
+        hipLaunchKernelGGL(bh_layer_kernel<DIMS>, dim3(grid_for(t.L.len[l], 256)), dim3(256), 0, c.stream, t.L.p[l - 1], t.L.len[l - 1],
+                           const_cast<double *>(t.L.p[l]), t.L.len[l]);
+    hipLaunchKernelGGL(bh_count_kernel<DIMS>, dim3(grid_for(n + 1, 256)), dim3(256), 0, c.stream, t.key_s.p, n, t.cnt.p);
+    launch_check("bh_count_kernel");
+    bytes = t.scan_bytes;
+    SHARP_HIP_CHECK(rocprim::exclusive_scan(t.scan_tmp.p, bytes, t.cnt.p, t.off.p, 0u, static_cast<size_t>(n) + 1, rocprim::plus<unsigned>(),
+                                            c.stream));
+    hipLaunchKernelGGL(bh_node_kernel<DIMS>, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, t.key_s.p, t.perm.p, n, t.off.p, t.L, t.meta.p,
+                       t.com.p);
+    launch_check("bh_node_kernel");
+}
 
 template <int DIMS>
 void to_f32(Work &w, bool center) {
@@ -726,6 +1077,15 @@ void gradient_terms(const TsneP &P, Work &w) {
         KernelTimer t("tsne_attr");
         hipLaunchKernelGGL(attr_kernel<DIMS>, dim3(grid_for(w.n, 256)), dim3(256), 0, c.stream, P.row_ptr.p, P.col.p, P.val.p, w.Y.p, w.n, w.attr.p);
         launch_check("attr_kernel");
+    }
+    if (w.theta > 0.0) {
+        bh_build<DIMS>(w);
+        KernelTimer t("tsne_bh_walk");
+        hipLaunchKernelGGL(bh_walk_kernel<DIMS>, dim3(grid_for(w.n, 256)), dim3(256), 0, c.stream, w.bh.Ys.p, w.bh.perm.p, w.n, w.bh.meta.p,
+                           w.bh.com.p, w.bh.root.p, w.theta, w.rep.p, w.zrow.p);
+        launch_check("bh_walk_kernel");
+        sum_fixed(w.zrow.p, w.n, w.red.p, w.scal.p);
+        return;
     }
     KernelTimer t("tsne_rep");
     for (long long r0 = 0; r0 < w.n; r0 += w.plan.rows) {
@@ -992,9 +1352,9 @@ void tsne_affinities(const DevBuf<int> &idx, const DevBuf<double> &dist, long lo
     stream_sync();
 }
 
-void tsne_gradient(const TsneP &P, const double *dY_in, int dims, double *dGrad) {
+void tsne_gradient(const TsneP &P, const double *dY_in, int dims, double *dGrad, double theta, double *Z) {
     Work w;
-    w.init(P.n, dims);
+    w.init(P.n, dims, theta);
     SHARP_HIP_CHECK(hipMemcpyAsync(w.Y.p, dY_in, static_cast<size_t>(P.n) * dims * sizeof(double), hipMemcpyDeviceToDevice, ctx().stream));
     const long long ne = P.n * dims;
     auto run = [&](auto tag) {
@@ -1007,6 +1367,7 @@ void tsne_gradient(const TsneP &P, const double *dY_in, int dims, double *dGrad)
     if (dims == 1) run(std::integral_constant<int, 1>());
     else if (dims == 2) run(std::integral_constant<int, 2>());
     else run(std::integral_constant<int, 3>());
+    if (Z) SHARP_HIP_CHECK(hipMemcpyAsync(Z, w.scal.p, sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
     stream_sync();
 }
 
@@ -1025,18 +1386,12 @@ void check_X(const double *X, long long n, int d, long long ld) {
                 throw sharp::Error(SHARP_ERR_ARG, "Rtsne: the input holds NA / NaN / Inf (row " + std::to_string(i + 1) + ", column " +
                                                       std::to_string(c + 1) + ")");
 }
-}  // namespace
 
-extern "C" {
-
-// R/visualization_SHARP.R:94: Rtsne(x1, check_duplicates = FALSE, pca = flag, ...), with an exact repulsion (theta accepted, unused)
-int sharp_tsne(const double *X, long long n, int d, long long ld, int dims, int initial_dims, int pca, int pca_center, int pca_scale, int normalize,
-               int check_duplicates, double perplexity, double theta, int max_iter, int stop_lying_iter, int mom_switch_iter, double momentum,
-               double final_momentum, double eta, double exaggeration, const double *Y_init, double seed, double *Y, double *itercosts,
-               double *costs) {
-    SHARP_API_BEGIN
-    (void)theta;
-    ctx();
+// Rtsne's body: bh_theta > 0 takes the Barnes-Hut repulsion with that theta, 0 the exact one
+void run_tsne(const double *X, long long n, int d, long long ld, int dims, int initial_dims, int pca, int pca_center, int pca_scale,
+              int normalize, int check_duplicates, double perplexity, double bh_theta, int max_iter, int stop_lying_iter, int mom_switch_iter,
+              double momentum, double final_momentum, double eta, double exaggeration, const double *Y_init, double seed, double *Y,
+              double *itercosts, double *costs) {
     check_X(X, n, d, ld);
     check_dims(dims);
     SHARP_REQUIRE(Y, "sharp_tsne: null Y");
@@ -1064,7 +1419,7 @@ int sharp_tsne(const double *X, long long n, int d, long long ld, int dims, int 
     idx.release();
     dist.release();
     Work w;
-    w.init(n, dims);
+    w.init(n, dims, bh_theta);
     const size_t ne = static_cast<size_t>(n) * dims;
     std::vector<double> y0(ne);
     if (Y_init) {
@@ -1091,6 +1446,37 @@ int sharp_tsne(const double *X, long long n, int d, long long ld, int dims, int 
     else optimise<3>(P, w, la, ic, costs);
     w.Y.download(Y, ne);
     if (itercosts) std::copy(ic.begin(), ic.end(), itercosts);
+}
+
+// Rtsne's own check on theta, as far as it is known here
+void check_bh_theta(double theta) { SHARP_REQUIRE(std::isfinite(theta) && theta >= 0.0 && theta <= 1.0, "Incorrect theta."); }
+}  // namespace
+
+extern "C" {
+
+// R/visualization_SHARP.R:94: Rtsne(x1, check_duplicates = FALSE, pca = flag, ...), with an exact repulsion (theta accepted, unused)
+int sharp_tsne(const double *X, long long n, int d, long long ld, int dims, int initial_dims, int pca, int pca_center, int pca_scale, int normalize,
+               int check_duplicates, double perplexity, double theta, int max_iter, int stop_lying_iter, int mom_switch_iter, double momentum,
+               double final_momentum, double eta, double exaggeration, const double *Y_init, double seed, double *Y, double *itercosts,
+               double *costs) {
+    SHARP_API_BEGIN
+    (void)theta;
+    ctx();
+    run_tsne(X, n, d, ld, dims, initial_dims, pca, pca_center, pca_scale, normalize, check_duplicates, perplexity, 0.0, max_iter, stop_lying_iter,
+             mom_switch_iter, momentum, final_momentum, eta, exaggeration, Y_init, seed, Y, itercosts, costs);
+    SHARP_API_END
+}
+
+// the same with bhtsne's Barnes-Hut repulsion at theta (0 <= theta <= 1; theta == 0: the exact path above, bit for bit)
+int sharp_tsne_bh(const double *X, long long n, int d, long long ld, int dims, int initial_dims, int pca, int pca_center, int pca_scale,
+                  int normalize, int check_duplicates, double perplexity, double theta, int max_iter, int stop_lying_iter, int mom_switch_iter,
+                  double momentum, double final_momentum, double eta, double exaggeration, const double *Y_init, double seed, double *Y,
+                  double *itercosts, double *costs) {
+    SHARP_API_BEGIN
+    ctx();
+    check_bh_theta(theta);
+    run_tsne(X, n, d, ld, dims, initial_dims, pca, pca_center, pca_scale, normalize, check_duplicates, perplexity, theta, max_iter, stop_lying_iter,
+             mom_switch_iter, momentum, final_momentum, eta, exaggeration, Y_init, seed, Y, itercosts, costs);
     SHARP_API_END
 }
 
@@ -1144,9 +1530,11 @@ int sharp_tsne_affinities(const double *X, long long n, int d, long long ld, dou
     SHARP_API_END
 }
 
-int sharp_tsne_gradient(const long long *row_ptr, const int *col, const double *val, long long n, int dims, const double *Y, double *dY) {
-    SHARP_API_BEGIN
-    ctx();
+}  // extern "C"
+
+namespace {
+void gradient_entry(const long long *row_ptr, const int *col, const double *val, long long n, int dims, const double *Y, double theta, double *dY,
+                    double *Z) {
     check_dims(dims);
     SHARP_REQUIRE(row_ptr && col && val && Y && dY && n >= 2, "sharp_tsne_gradient: null argument");
     TsneP P;
@@ -1164,8 +1552,26 @@ int sharp_tsne_gradient(const long long *row_ptr, const int *col, const double *
     for (long long e = 0; e < P.nnz; ++e) SHARP_REQUIRE(col[e] >= 0 && col[e] < n, "sharp_tsne_gradient: a column index out of range");
     DevBuf<double> dYin(ne), dG(ne);
     dYin.upload(Y, ne);
-    tsne_gradient(P, dYin.p, dims, dG.p);
+    tsne_gradient(P, dYin.p, dims, dG.p, theta, Z);
     dG.download(dY, ne);
+}
+}  // namespace
+
+extern "C" {
+
+int sharp_tsne_gradient(const long long *row_ptr, const int *col, const double *val, long long n, int dims, const double *Y, double *dY) {
+    SHARP_API_BEGIN
+    ctx();
+    gradient_entry(row_ptr, col, val, n, dims, Y, 0.0, dY, nullptr);
+    SHARP_API_END
+}
+
+int sharp_tsne_gradient_bh(const long long *row_ptr, const int *col, const double *val, long long n, int dims, const double *Y, double theta,
+                           double *dY, double *Z) {
+    SHARP_API_BEGIN
+    ctx();
+    check_bh_theta(theta);
+    gradient_entry(row_ptr, col, val, n, dims, Y, theta, dY, Z);
     SHARP_API_END
 }
 

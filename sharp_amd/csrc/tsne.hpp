@@ -1,6 +1,6 @@
 // tsne.hpp -- the exact t-SNE embedding behind visualization_SHARP (R/visualization_SHARP.R:94 calls Rtsne there): input preparation
 // (PCA, normalisation), exact k-NN on the f64 MFMA, per-row perplexity calibration, the symmetric P in CSR, and the optimiser loop with
-// an exact O(n^2) repulsion.  The C ABI entries (sharp_tsne*, include/sharp_hip.h) are thin wrappers over these.
+// an exact O(n^2) repulsion or bhtsne's Barnes-Hut one.  The C ABI entries (sharp_tsne*, include/sharp_hip.h) are thin wrappers over these.
 #pragma once
 #include "common.hpp"
 
@@ -23,7 +23,8 @@ void tsne_prepare(const double *X, long long n, int d, long long ld, bool pca, i
 void tsne_knn(const double *dX, long long n, int d, int K, DevBuf<int> &idx, DevBuf<double> &dist);
 // calibration + symmetrisation: P from the k-NN lists
 void tsne_affinities(const DevBuf<int> &idx, const DevBuf<double> &dist, long long n, int K, double perplexity, TsneP &P);
-// dY = sum_j P_ij q_ij (y_i - y_j) - (1/Z) sum_j q_ij^2 (y_i - y_j) at Y (device, n x dims)
-void tsne_gradient(const TsneP &P, const double *dY_in, int dims, double *dGrad);
+// dY = sum_j P_ij q_ij (y_i - y_j) - (1/Z) sum_j q_ij^2 (y_i - y_j) at Y (device, n x dims); theta > 0: the repulsion and Z by
+// Barnes-Hut at that theta; Z (host, may be null) receives Z
+void tsne_gradient(const TsneP &P, const double *dY_in, int dims, double *dGrad, double theta = 0.0, double *Z = nullptr);
 
 }  // namespace sharp

@@ -3,6 +3,10 @@ forview outputs.  One JSON line per size on stdout.
 
     python tools/bench_tsne.py --n 50000 --d 400 --iters 200      # cfg2's x1: ncl + p ~ 400 columns, through PCA to 50
     python tools/bench_tsne.py --n 500000 --d 70 --iters 30       # cfg3's x1: ncl + 50 columns
+    python tools/bench_tsne.py --n 500000 --d 70 --iters 200 --repulsion barnes_hut --theta 0.5
+
+With --repulsion barnes_hut the repulsion is reported as two stages, the tree build (bh_tree_ms_per_iter) and the traversal
+(bh_walk_ms_per_iter); rep_ms_per_iter is their sum.
 
 Stages come from the library's per-kernel HIP-event timers (sharp_profile_*); total_ms is a second, unprofiled call timed on a
 synchronised host clock.  Per-iteration figures are the timer totals over the calls they cover; total_1000_est_ms extrapolates the
@@ -45,35 +49,39 @@ def main():
     ap.add_argument("--ncl", type=int, default=20)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--repulsion", choices=["exact", "barnes_hut"], default="exact")
+    ap.add_argument("--theta", type=float, default=0.5)
     a = ap.parse_args()
     import sharp_amd
 
     sharp_amd.init(0)
     L = sharp_amd.lib()
     X = synth_x1(a.n, a.d, a.ncl, a.seed)
-    kw = dict(perplexity=30, max_iter=a.iters, check_duplicates=False, pca=a.d > 50)
+    kw = dict(perplexity=30, max_iter=a.iters, check_duplicates=False, pca=a.d > 50, theta=a.theta, repulsion=a.repulsion)
     sharp_amd.Rtsne(X[: min(a.n, 2000)], **dict(kw, max_iter=2))       # first call: code objects, allocations
     L.sharp_profile_enable(1)
     L.sharp_profile_reset()
     sharp_amd.Rtsne(X, **kw)
     L.sharp_synchronize()
     st = {k: stat(L, k) for k in ["tsne_pca", "tsne_normalize", "tsne_knn", "tsne_calib", "tsne_sym", "tsne_attr", "tsne_rep", "tsne_update",
-                                  "tsne_kl"]}
+                                  "tsne_kl", "tsne_bh_tree", "tsne_bh_walk"]}
     eig = stat(L, "host:tsne_pca_eigen")
     L.sharp_profile_enable(0)
     t0 = time.perf_counter()
     sharp_amd.Rtsne(X, **kw)
     total = (time.perf_counter() - t0) * 1e3
     per = lambda k: st[k][0] / max(st[k][1], 1)                       # noqa: E731
-    iter_ms = per("tsne_attr") + per("tsne_rep") + per("tsne_update")
+    rep_ms = per("tsne_bh_tree") + per("tsne_bh_walk") if a.repulsion == "barnes_hut" else per("tsne_rep")
+    iter_ms = per("tsne_attr") + rep_ms + per("tsne_update")
     fixed = st["tsne_pca"][0] + st["tsne_normalize"][0] + st["tsne_knn"][0] + st["tsne_calib"][0] + st["tsne_sym"][0]
     loop = total - fixed
-    out = {"n": a.n, "d": a.d, "dims": 2, "perplexity": 30, "iters": a.iters,
+    out = {"n": a.n, "d": a.d, "dims": 2, "perplexity": 30, "iters": a.iters, "repulsion": a.repulsion, "theta": a.theta,
            "pca_ms": round(st["tsne_pca"][0], 3), "pca_eigen_host_ms": round(eig[0], 3), "normalize_ms": round(st["tsne_normalize"][0], 3),
            "knn_ms": round(st["tsne_knn"][0], 3), "calib_ms": round(st["tsne_calib"][0], 3), "sym_ms": round(st["tsne_sym"][0], 3),
-           "attr_ms_per_iter": round(per("tsne_attr"), 4), "rep_ms_per_iter": round(per("tsne_rep"), 4),
+           "attr_ms_per_iter": round(per("tsne_attr"), 4), "rep_ms_per_iter": round(rep_ms, 4),
+           "bh_tree_ms_per_iter": round(per("tsne_bh_tree"), 4), "bh_walk_ms_per_iter": round(per("tsne_bh_walk"), 4),
            "update_ms_per_iter": round(per("tsne_update"), 4), "kl_ms_per_eval": round(per("tsne_kl"), 4),
-           "iter_ms": round(iter_ms, 4), "rep_pairs_per_s": float(f"{a.n * a.n / (per('tsne_rep') * 1e-3):.4g}"),
+           "iter_ms": round(iter_ms, 4), "rep_pairs_per_s": float(f"{a.n * a.n / (rep_ms * 1e-3):.4g}"),
            "knn_pairs_per_s": float(f"{a.n * a.n / (st['tsne_knn'][0] * 1e-3):.4g}"),
            "total_ms": round(total, 2), "loop_ms_per_iter_unprofiled": round(loop / max(a.iters, 1), 4),
            "total_1000_est_ms": round(fixed + 1000 * loop / max(a.iters, 1), 1), "total_1000_is_estimate": a.iters != 1000}
