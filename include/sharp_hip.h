@@ -397,6 +397,27 @@ int sharp_tsne_bh(const double *X, long long n, int d, long long ld, int dims, i
 int sharp_tsne_gradient_bh(const long long *row_ptr, const int *col, const double *val, long long n, int dims, const double *Y, double theta,
                            double *dY, double *Z);
 
+/* ---- dist / hclust as a tree: what pheatmap(cluster_rows = T, cluster_cols = T, clustering_method = "ward.D") computes inside
+ * plot_markers (R/plot_markers.R:214-237), i.e. hclust(dist(sm), "ward.D") over the marker genes and hclust(dist(t(sm)), "ward.D") over up
+ * to ~10 000 cells (:136-143).  DESIGN.md §11.
+ * sharp_dist = stats::dist(x, method, p = minkowski_p): x n x p ROW-major observations (leading dimension ld); d_out the dist object,
+ * n (n - 1) / 2 doubles in R's order (column-wise lower triangle = scipy's pdist order).  method (R's own codes): 1 euclidean, 2 maximum,
+ * 3 manhattan, 6 minkowski -- computed from the differences x_ik - x_jk summed in fp64 in the order k = 0 .. p - 1, so duplicate rows are
+ * at distance exactly 0 --, 7 "correlation" = as.dist(1 - cor(t(x))) (pheatmap's clustering_distance; the fp64-MFMA GEMM of
+ * get_opt_hclust); 4 canberra and 5 binary are refused (SHARP_ERR_ARG), and so is NA / NaN / Inf in x.  2 <= n <= SHARP_DIST_MAX_N: the
+ * full n x n matrix is built in device memory (17 GB at the limit) and the dist vector has at most 2^30 entries. */
+#define SHARP_DIST_MAX_N 46340
+int sharp_dist(const double *x, int n, int p, long long ld, int method, double minkowski_p, double *d_out);
+/* stats::hclust(d, method): d a dist object as above, 2 <= n <= 16384; hmethod as in sharp_get_opt_hclust (1 ward.D .. 8 ward.D2; as in
+ * R, centroid / median take the distances they are given and ward.D2 squares them and reports the root).  Outputs = R's hclust object:
+ * merge (n - 1) x 2 COLUMN-major (observations negative, earlier steps positive; a singleton before a cluster, otherwise ascending:
+ * hclust.f's HCASS2), height n - 1 in R's step order, order n (the dendrogram's leaves from left to right, 1-based). */
+int sharp_hclust_dist(const double *d, int n, int hmethod, int *merge, double *height, int *order);
+/* hclust(dist(x, dist_method, p = minkowski_p), hmethod) with the distance matrix kept in device memory (arguments of sharp_dist and
+ * sharp_hclust_dist; 2 <= n <= 16384).  Bitwise the same tree as sharp_hclust_dist on sharp_dist's output. */
+int sharp_hclust(const double *x, int n, int p, long long ld, int dist_method, double minkowski_p, int hmethod, int *merge, double *height,
+                 int *order);
+
 /* ---- synthetic inputs (bench / tests; not part of the reference) ------------ */
 /* Counter-based generator, value = f(seed, gene, cell): bit-identical to
  * oracle_synth_value().  Fills dX (fp32, m x ncell column-major, leading dim ld). */
@@ -496,6 +517,11 @@ void sharp_C_tsne_bh(double *X, double *n, int *d, int *dims, int *initial_dims,
                      int *check_duplicates, double *perplexity, double *theta, int *max_iter, int *stop_lying_iter, int *mom_switch_iter,
                      double *momentum, double *final_momentum, double *eta, double *exaggeration, int *has_Y_init, double *Y_init, double *seed,
                      double *Y, double *itercosts, double *costs, int *status);
+/* stats::dist / stats::hclust for pheatmap inside plot_markers (R/plot_markers.R:214-237): x = as.double(t(x)) (rows of p values) */
+void sharp_C_dist(double *x, int *n, int *p, int *method, double *minkowski_p, double *d_out, int *status);
+void sharp_C_hclust_dist(double *d, int *n, int *hmethod, int *merge, double *height, int *order, int *status);
+void sharp_C_hclust(double *x, int *n, int *p, int *dist_method, double *minkowski_p, int *hmethod, int *merge, double *height, int *order,
+                    int *status);
 
 #ifdef __cplusplus
 }

@@ -308,3 +308,94 @@ sharp_Rtsne <- function(X, dims = 2, initial_dims = 50, perplexity = 30, theta =
          stop_lying_iter = stop_lying_iter, mom_switch_iter = mom_switch_iter, momentum = momentum, final_momentum = final_momentum,
          eta = eta, exaggeration_factor = exaggeration_factor)
 }
+
+# ---- dist / hclust / plot_markers (R/plot_markers.R:38-242; DESIGN.md 11) ----------------------------------------------------------------
+# pheatmap(cluster_rows = T, cluster_cols = T, clustering_method = "ward.D") at R/plot_markers.R:214-237 computes hclust(dist(sm), "ward.D")
+# over the marker genes and hclust(dist(t(sm)), "ward.D") over up to ~10 000 cells.  sharp_dist / sharp_hclust do that on the GPU;
+# sharp_hclust returns an object of class "hclust", which pheatmap(cluster_rows = , cluster_cols = ) accepts directly.
+.sharp_dist_methods <- c(euclidean = 1L, maximum = 2L, manhattan = 3L, canberra = 4L, binary = 5L, minkowski = 6L, correlation = 7L)
+
+# stats::dist(x, method, p = p) (+ method = "correlation": as.dist(1 - cor(t(x))), pheatmap's clustering_distance)
+sharp_dist <- function(x, method = "euclidean", diag = FALSE, upper = FALSE, p = 2) {
+    if (!method %in% names(.sharp_dist_methods)) stop("invalid distance method")
+    x <- .sharp_dmat(x)
+    n <- nrow(x)
+    r <- .C("sharp_C_dist", as.double(t(x)), n, ncol(x), .sharp_dist_methods[[method]], as.double(p), d = double(n * (n - 1) / 2),
+            status = integer(1))
+    .sharp_check(r$status)
+    structure(r$d, Size = n, Labels = rownames(x), Diag = diag, Upper = upper, method = method, call = match.call(), class = "dist")
+}
+
+# stats::hclust(d, method) for a dist object d, or -- x given -- hclust(dist(x, distance, p = p), method) with the distances kept on the GPU
+sharp_hclust <- function(d = NULL, method = "ward.D", x = NULL, distance = "euclidean", p = 2) {
+    hm <- .sharp_hmethod(method)
+    if (is.null(x)) {
+        n <- as.integer(attr(d, "Size"))
+        r <- .C("sharp_C_hclust_dist", as.double(d), n, hm, merge = integer(2L * (n - 1L)), height = double(n - 1L), order = integer(n),
+                status = integer(1))
+        labels <- attr(d, "Labels"); dm <- attr(d, "method")
+    } else {
+        if (!distance %in% names(.sharp_dist_methods)) stop("invalid distance method")
+        x <- .sharp_dmat(x)
+        n <- nrow(x)
+        r <- .C("sharp_C_hclust", as.double(t(x)), n, ncol(x), .sharp_dist_methods[[distance]], as.double(p), hm,
+                merge = integer(2L * (n - 1L)), height = double(n - 1L), order = integer(n), status = integer(1))
+        labels <- rownames(x); dm <- distance
+    }
+    .sharp_check(r$status)
+    structure(list(merge = matrix(r$merge, ncol = 2L), height = r$height, order = r$order, labels = labels, method = method,
+                   call = match.call(), dist.method = dm), class = "hclust")
+}
+
+# plot_markers (R/plot_markers.R:38): the reference's formals.  Keep :40-213 (selection, file type and name, colours) as they are and call
+# pheatmap at :214-237 with cluster_rows = sharp_hclust(x = sm, method = "ward.D") and cluster_cols = sharp_hclust(x = t(sm), method =
+# "ward.D") in place of cluster_rows = T, cluster_cols = T; `select` stands for those kept lines and returns list(sm, sortmarker, ...).
+sharp_plot_markers <- function(sginfo, label, N.marker, sN.cluster, filename, filetype, nratio, n.cores, width = 900, height = 900, ...) {
+    s <- .sharp_plot_markers_select(sginfo, label, N.marker, sN.cluster, nratio)                     # R/plot_markers.R:46-151
+    if (ncol(s$sm) > 16384L) stop("plot_markers: more than 16384 cells selected: give a smaller nratio")
+    if (missing(filetype)) filetype <- if (s$ncells < 5000) "pdf" else "png"                          # :184-190
+    if (missing(filename)) filename <- paste0("markers_heatmap.", filetype)                          # :193-195
+    if (filetype == "pdf") pdf(filename) else if (filetype == "png") png(filename, width = width, height = height)
+    pheatmap::pheatmap(mat = s$sm, color = gplots::colorpanel(400, "blue", "white", "red"), border_color = NA,
+                       cluster_rows = sharp_hclust(x = s$sm, method = "ward.D"), cluster_cols = sharp_hclust(x = t(s$sm), method = "ward.D"),
+                       show_colnames = FALSE, show_rownames = TRUE, annotation_col = s$mat_col, annotation_colors = s$mat_colors,
+                       drop_levels = TRUE, fontsize = 12, scale = "row", ...)
+    dev.off()
+    cat("Marker-genes heatmap saved into", filename, "\n")
+    s$sortmarker
+}
+
+# R/plot_markers.R:46-181 without the foreach: markers, cells, log2 / z-score, annotation colours
+.sharp_plot_markers_select <- function(sginfo, label, N.marker, sN.cluster, nratio) {
+    if (missing(label)) label <- sginfo$label
+    if (missing(nratio)) nratio <- 1e4 / length(label)
+    mginfo <- sginfo$mginfo
+    d <- cbind(genes = rownames(mginfo), mginfo)
+    d <- d[order(d$icluster, d$pvalue), ]
+    sortmarker <- d[order(d$icluster, -rank(d$auc), d$pvalue), ]
+    if (missing(N.marker)) N.marker <- 10
+    if (missing(sN.cluster)) sN.cluster <- length(unique(mginfo$icluster))
+    kk <- sort(unique(mginfo$icluster))[1:sN.cluster]
+    ssmarker <- do.call(rbind, lapply(kk, function(k) { x <- sortmarker[sortmarker$icluster == k, ]; x[seq_len(min(nrow(x), N.marker)), ] }))
+    cellind <- order(label)
+    newc <- label[cellind]
+    sm <- sginfo$mat[rownames(ssmarker), cellind]
+    scind <- which(newc %in% kk)
+    newc <- newc[scind]; sm <- sm[, scind]
+    if (length(cellind) > 1e4) {
+        kt <- ceiling(table(newc) * nratio)
+        xu <- unique(newc)
+        ki <- unlist(lapply(seq_along(xu), function(i) which(newc == xu[i])[1:kt[i]]))
+        sm <- sm[, ki]; newc <- newc[ki]
+    }
+    my <- if (sginfo$logmark) log2(sm + 1) else sm
+    my <- my[apply(my, 1, function(x) sd(x) != 0), ]
+    sm <- t(scale(t(my)))
+    k0 <- colnames(sm); k1 <- duplicated(k0)
+    if (any(k1)) k0[k1] <- paste0("d", seq_len(sum(k1)))
+    colnames(sm) <- k0
+    mat_col <- data.frame(cell_type = newc, row.names = k0)
+    cols <- RColorBrewer::brewer.pal(length(unique(newc)), "Set1")
+    names(cols) <- unique(newc)
+    list(sm = sm, sortmarker = sortmarker, ncells = length(cellind), mat_col = mat_col, mat_colors = list(cell_type = cols))
+}

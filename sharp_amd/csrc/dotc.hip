@@ -244,4 +244,16 @@ void sharp_C_tsne_bh(double *X, double *n, int *d, int *dims, int *initial_dims,
                             *exaggeration, *has_Y_init ? Y_init : nullptr, *seed, Y, itercosts, costs);
 }
 
+/* ---- dist / hclust (the clustering pheatmap does inside plot_markers, R/plot_markers.R:214-237): x = as.double(t(x)) */
+void sharp_C_dist(double *x, int *n, int *p, int *method, double *minkowski_p, double *d_out, int *status) {
+    *status = sharp_dist(x, *n, *p, static_cast<long long>(*p), *method, *minkowski_p, d_out);
+}
+void sharp_C_hclust_dist(double *d, int *n, int *hmethod, int *merge, double *height, int *order, int *status) {
+    *status = sharp_hclust_dist(d, *n, *hmethod, merge, height, order);
+}
+void sharp_C_hclust(double *x, int *n, int *p, int *dist_method, double *minkowski_p, int *hmethod, int *merge, double *height, int *order,
+                    int *status) {
+    *status = sharp_hclust(x, *n, *p, static_cast<long long>(*p), *dist_method, *minkowski_p, *hmethod, merge, height, order);
+}
+
 }  // extern "C"

@@ -1169,7 +1169,7 @@ __global__ __launch_bounds__(64 * SS_WAVES) void cluster_sums_kernel(const HcMet
 // copy the pristine distances of symmetric tasks (hclust updates D in place)
 __global__ void copy_d_kernel(const HcMeta *__restrict__ metas, const double *__restrict__ Dall, double *__restrict__ D0all) {
     const HcMeta M = metas[blockIdx.y];
-    if (!M.symmetric) return;
+    if (M.symmetric != 1) return;
     const long long tot = static_cast<long long>(M.n) * M.nld;
     const double *D = Dall + M.oD;
     double *D0 = D0all + M.oD0;
@@ -1830,7 +1830,7 @@ void setup_chunk(const std::vector<HcTask> &tasks, ChunkJob &J) {
         SHARP_REQUIRE(tk.n <= kHcMaxN, "get_opt_hclust: more than 16384 observations in one clustering task is not supported");
         SHARP_REQUIRE(tk.prm.hmethod >= 1 && tk.prm.hmethod <= 8, "get_opt_hclust: unknown agglomeration method");
         M.n = tk.n; M.p = tk.symmetric ? tk.n : tk.p; M.nld = static_cast<int>(rup(tk.n, 128));
-        M.method = tk.prm.hmethod; M.symmetric = tk.symmetric ? 1 : 0; M.pad0 = 0;
+        M.method = tk.prm.hmethod; M.symmetric = tk.symmetric ? (tk.distance ? 2 : 1) : 0; M.pad0 = 0;   // 2: a distance matrix as it is (hclust_tree)
         if (tk.prm.N_cluster > 0) {
             SHARP_REQUIRE(tk.prm.N_cluster >= 2, "The given N.cluster is less than 2, which is not suitable for clustering!");
             SHARP_REQUIRE(tk.prm.N_cluster <= tk.n - 1, "N.cluster must be smaller than the number of observations");
@@ -1843,9 +1843,9 @@ void setup_chunk(const std::vector<HcTask> &tasks, ChunkJob &J) {
         M.nk = M.kmax - M.kmin + 1;
         M.kpad = static_cast<int>(rup(M.kmax, 16));
         M.oD = oD; oD += static_cast<long long>(M.nld) * M.nld;
-        M.oD0 = oD0; if (M.symmetric) oD0 += static_cast<long long>(M.nld) * M.nld;
-        M.oCr = oCr; oCr += static_cast<long long>(M.n) * M.p;
-        M.oCt = oCt; oCt += rup(M.p, 16) * M.nld;
+        M.oD0 = oD0; if (M.symmetric == 1) oD0 += static_cast<long long>(M.nld) * M.nld;
+        M.oCr = oCr; if (M.symmetric != 2) oCr += static_cast<long long>(M.n) * M.p;      // (a distance task has no feature rows: no statistics)
+        M.oCt = oCt; if (M.symmetric != 2) oCt += rup(M.p, 16) * M.nld;
         M.oNrm = oN; oN += M.n;
         M.oM = oM; oM += M.n;
         M.oLab = oLab; oLab += static_cast<long long>(M.nk) * M.n;
@@ -1942,7 +1942,7 @@ void setup_chunk(const std::vector<HcTask> &tasks, ChunkJob &J) {
                         g.push_back(GemmTask{W.CSt.p + M.oCSt, W.CSt.p + M.oCSt, W.Q.p + M.oQ, M.kpad, M.kpad, M.p, M.kpad, M.kpad, M.kpad, 0, 0, 0});
                         break;
                     default:  // (symmetric) T^T = H^T D0  (kpad x nld)
-                        if (M.symmetric) g.push_back(GemmTask{W.H.p + M.oH, W.D0.p + M.oD0, W.T.p + M.oT, M.kpad, M.n, M.n, M.kpad, M.nld, M.nld, 0, 0, 0});
+                        if (M.symmetric == 1) g.push_back(GemmTask{W.H.p + M.oH, W.D0.p + M.oD0, W.T.p + M.oT, M.kpad, M.n, M.n, M.kpad, M.nld, M.nld, 0, 0, 0});
                         break;
                 }
             }
@@ -1985,7 +1985,7 @@ void setup_chunk(const std::vector<HcTask> &tasks, ChunkJob &J) {
         J.mlt_off = static_cast<int>(g.size());
         for (int t = 0; t < T; ++t) {                      // (symmetric) T = D0 H  (n x kpad)
             const HcMeta &M = metas[t];
-            if (M.symmetric) g.push_back(GemmTask{W.D0.p + M.oD0, W.H.p + M.oH, W.T.p + M.oT, M.n, M.kpad, M.n, M.nld, M.kpad, M.kpad, 0, 0, 0});
+            if (M.symmetric == 1) g.push_back(GemmTask{W.D0.p + M.oD0, W.H.p + M.oH, W.T.p + M.oT, M.n, M.kpad, M.n, M.nld, M.kpad, M.kpad, 0, 0, 0});
         }
         J.mlt_cnt = static_cast<int>(g.size()) - J.mlt_off;
         W.gemm.ensure(g.size());
@@ -2623,6 +2623,34 @@ void hc_prefetch_finish(HcPrefetch &P, bool want_v, std::vector<HcResult> &out) 
     if (!P.agglo_enqueued) hc_prefetch_agglomerate(P);
     enqueue_chunk(P.J, PH_STATS);
     finish_chunk(P.tasks, P.J, want_v, out);
+}
+
+// stats::hclust alone: one distance task through setup_chunk / enqueue_chunk (rows copied as they are, agglomeration), no statistics
+void hclust_tree(const double *d_dist, long long ld, int n, int hmethod, HcTree &out) {
+    Ctx &c = ctx();
+    SHARP_REQUIRE(d_dist && n >= 3 && n <= kHcMaxN && ld >= n, "hclust: bad arguments");
+    HcTask tk;
+    tk.d_mat = d_dist; tk.ld = ld; tk.n = n; tk.p = n; tk.symmetric = true; tk.distance = true;
+    tk.prm.hmethod = hmethod;
+    tk.prm.N_cluster = 2;                                   // (sizes the unused statistics buffers at their smallest)
+    std::vector<HcTask> tasks{tk};
+    ChunkJob J;
+    J.i0 = 0; J.i1 = 1; J.one_range = true;
+    setup_chunk(tasks, J);
+    enqueue_chunk(J, PH_DIST | PH_AGGLO);
+    Workspace &W = ws(J.slot);
+    out.ia.assign(n - 1, 0); out.ib.assign(n - 1, 0); out.crit.assign(n - 1, 0.0);
+    int st = 1;
+    if (!knobs().hc_seq) W.status.download(&st, 1);
+    out.sequential = st != 0;
+    W.ia.download(out.ia.data(), n - 1);
+    W.ib.download(out.ib.data(), n - 1);
+    W.height.download(out.crit.data(), n - 1);
+    if (c.profiling) c.stats[out.sequential ? "host:hclust_tasks_sequential" : "host:hclust_tasks_bulk_synchronous"].launches += 1;
+    if (static_cast<size_t>(J.metas[0].nld) * J.metas[0].nld > (64u << 20)) {   // three matrices of more than 512 MB each: not kept between calls
+        Workspace &W0 = ws(J.scratch_slot);
+        W.D.release(); W0.S0.release(); W0.S1.release();
+    }
 }
 
 }  // namespace sharp

@@ -47,6 +47,7 @@ struct HcTask {
     long long ld = 0;
     int n = 0, p = 0;
     bool symmetric = false;
+    bool distance = false;    // (with symmetric) d_mat is an n x n symmetric DISTANCE matrix, taken as it is: only hclust_tree sets it
     HcParams prm;             // per-task (sMetaC adjusts minN/maxN per call)
 };
 
@@ -80,6 +81,17 @@ void get_opt_hclust_batch(const std::vector<HcTask> &tasks, bool want_v, std::ve
 // host, right after the LAST chunk's agglomeration has been enqueued; ev is recorded behind that agglomeration.  For work that needs
 // none of the batch's results and should share the chip with the last chunk's statistics rather than with an agglomeration (the
 // ensemble mean of SHARP_large: one HBM-bound pass over E).  Returns through hc_after_last_agglomeration_fired() whether it ran.
+// stats::hclust alone (sharp_hclust / sharp_hclust_dist, dist.hip): the agglomeration of one DEVICE distance matrix (n x n symmetric,
+// leading dimension ld, 3 <= n <= kHcMaxN) by the same pair of kernels as get_opt_hclust_batch -- the bulk-synchronous kernel, and the
+// sequential one in R's order when that reports an exact tie or for centroid / median -- without the statistics phase.  The n - 1
+// (ia, ib, crit) triples of hclust.f (cluster representatives = lowest member, 1-based; in R's step order) come back to the host.
+struct HcTree {
+    std::vector<int> ia, ib;
+    std::vector<double> crit;
+    bool sequential = false;  // the sequential kernel did it
+};
+void hclust_tree(const double *d_dist, long long ld, int n, int hmethod, HcTree &out);
+
 void hc_release_workspaces();   // the clustering workspaces of the calling thread's slot (sharp_trim; the device is idle)
 void hc_set_after_last_agglomeration(std::function<void(hipEvent_t)> fn);
 bool hc_after_last_agglomeration_fired();

@@ -368,6 +368,11 @@ __global__ __launch_bounds__(256) void row_prep_kernel(const RowPrepTask *__rest
     gdp cr = (gdp)t.Cr + static_cast<long long>(row) * t.p;
     const int p = t.p;
     if (fused_rows(t) && skip_fused) return;              // row_prep_t_kernel's
+    if (t.mode == 2) {                                    // a distance matrix taken as it is (hclust_tree): no feature rows, no statistics
+        gdp drow = (gdp)t.D + static_cast<long long>(row) * t.nld;
+        for (int q = lane; q < p; q += 64) drow[q] = q == row ? 0.0 : x[q];
+        return;
+    }
     if (t.mode == 0 && p <= 64 * RP_MAXV) {
         // feature rows of a base-clustering task (p = reduced dimension): the row is read once and kept in registers;
         // the arithmetic and its order are those of the general path below
@@ -433,7 +438,7 @@ __global__ __launch_bounds__(256) void row_prep_kernel(const RowPrepTask *__rest
 // Cr (n x p) -> Ct (p x nld), 32x32 tiles through LDS
 __global__ __launch_bounds__(256) void transpose_kernel(const RowPrepTask *__restrict__ tasks, int skip_fused) {
     const RowPrepTask t = tasks[blockIdx.z];
-    if (fused_rows(t) && skip_fused) return;
+    if ((fused_rows(t) && skip_fused) || t.mode == 2) return;
     __shared__ double tile[32][33];
     const int r0 = blockIdx.y * 32, q0 = blockIdx.x * 32;
     if (r0 >= t.nld || q0 >= t.p_pad) return;

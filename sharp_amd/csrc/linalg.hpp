@@ -36,6 +36,7 @@ void gemm_tn_f64_batched(const GemmTask *d_tasks, int count, int max_M, int max_
 //                          u = c / ||c||  -> Cr (n x p row-major), Ct (p x nld), nrm = 1
 //   mode 1 (symmetric similarity S): c = x - mean (rows of S as features for get_CH),
 //                          Cr, Ct = centred rows, nrm = ||c||;  D = 1 - S is written as well.
+//   mode 2 (symmetric distance matrix, hclust_tree): D = the rows as they are (zero diagonal); Cr, Ct, nrm are not touched.
 struct RowPrepTask {
     const double *src;   // n x p row-major, leading dimension lds
     long long lds;

@@ -113,3 +113,19 @@ def unlimited_sharded(local_blocks, local_block_ids, ncells_per_block, run_block
     for blk_id, pr in zip(local_block_ids, preds):
         out[blk_id] = np.asarray(final_id)[first[blk_id] + pr - 1]
     return out, int(n_final), p
+
+
+# sharp_amd.dist(x, method, p) is also R's dist() on the GPU (sharp_amd/tree.py: plot_markers' dist / hclust).  This module keeps the name
+# it has had, so the module itself is made callable and forwards the call.
+import sys as _sys  # noqa: E402
+import types as _types  # noqa: E402
+
+
+class _CallableModule(_types.ModuleType):
+    def __call__(self, x, method="euclidean", p=2):
+        from .tree import dist as _dist
+
+        return _dist(x, method=method, p=p)
+
+
+_sys.modules[__name__].__class__ = _CallableModule
