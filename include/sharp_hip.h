@@ -418,6 +418,30 @@ int sharp_hclust_dist(const double *d, int n, int hmethod, int *merge, double *h
 int sharp_hclust(const double *x, int n, int p, long long ld, int dist_method, double minkowski_p, int hmethod, int *merge, double *height,
                  int *order);
 
+/* ---- cutree, silhouette, Calinski-Harabasz: what is done with a tree and with a labelling (validity.hip) ---------------------------
+ * stats::cutree(tree, k) as the reference calls it on every tree it builds (R/get_opt_hclust.R:101,132,207): merge as sharp_hclust
+ * writes it ((n - 1) x 2 column-major), k[0 .. nk) numbers of clusters, each between 1 and n; out: n x nk column-major, column q = the
+ * labels of the partition after the first n - k[q] merges, 1-based and numbered by first appearance in observation order (R_cutree:
+ * observation 1 is in cluster 1).  Host only: runs WITHOUT a device context, O(n) per k.  (cutree(tree, h = ) is k = n + 1 - the first
+ * index where c(height, Inf) > h; sharp_amd.cutree and R's own cutree do that step.) */
+int sharp_cutree(const int *merge, int n, const int *k, int nk, int *out);
+/* cluster::silhouette(x, dist) (its C code sildist(); R/get_opt_hclust.R:103,134-137 take the median of column 3): cl = the cluster codes
+ * 1 .. k of the n observations (every code occurs, 2 <= k <= n - 1), d = R's dist vector as sharp_dist returns it (3 <= n <=
+ * SHARP_DIST_MAX_N).  neighbor[i] = the code of the nearest other cluster -- the first smallest mean distance in code order on an exact
+ * tie --, width[i] = (b - a) / max(a, b) with a(i) over the n_c - 1 other members of the own cluster and b(i) the smallest mean over
+ * another cluster; 0 when a == b and for an observation alone in its cluster.  Deterministic: the same input gives the same bits. */
+int sharp_silhouette_dist(const double *d, int n, const int *cl, int k, int *neighbor, double *width);
+/* The same from the observations (x: n rows of p features, leading dimension ld; dist_method / minkowski_p as in sharp_dist), MATRIX-FREE:
+ * no n x n and no n x k array; device memory: n p doubles, 24 bytes per observation and 12 more per observation and workgroup part (at
+ * most 32 parts).  Any 2 <= k <= n - 1, 3 <= n <= 16777216.  The four difference metrics give bitwise sharp_dist's distances (duplicates at exactly 0); the
+ * correlation distance is 1 - the dot product of the centred unit rows.  Deterministic as above. */
+int sharp_silhouette(const double *x, long long n, int p, long long ld, int dist_method, double minkowski_p, const int *cl, int k,
+                     int *neighbor, double *width);
+/* kind 0: clusterCrit::intCriteria(x, cl, "Calinski_Harabasz") = [B / (k - 1)] / [W / (n - k)] with squared Euclidean between / within
+ * sums (R/get_opt_hclust.R:105); kind 1: clues::get_CH(x, cl, disMethod = "1-corr") (R/get_opt_hclust.R:144; d = 1 - Pearson
+ * correlation in both sums).  O(n p), 3 <= n <= 16777216, 2 <= k <= n - 1; W == 0 gives +Inf as in R. */
+int sharp_calinski_harabasz(const double *x, long long n, int p, long long ld, const int *cl, int k, int kind, double *out);
+
 /* ---- synthetic inputs (bench / tests; not part of the reference) ------------ */
 /* Counter-based generator, value = f(seed, gene, cell): bit-identical to
  * oracle_synth_value().  Fills dX (fp32, m x ncell column-major, leading dim ld). */
@@ -522,6 +546,12 @@ void sharp_C_dist(double *x, int *n, int *p, int *method, double *minkowski_p, d
 void sharp_C_hclust_dist(double *d, int *n, int *hmethod, int *merge, double *height, int *order, int *status);
 void sharp_C_hclust(double *x, int *n, int *p, int *dist_method, double *minkowski_p, int *hmethod, int *merge, double *height, int *order,
                     int *status);
+/* cluster::silhouette / Calinski-Harabasz (sharp_silhouette_dist, sharp_silhouette, sharp_calinski_harabasz): x = as.double(t(x)),
+ * n as double, cl = as.integer(factor(labels)) */
+void sharp_C_silhouette_dist(double *d, int *n, int *cl, int *k, int *neighbor, double *width, int *status);
+void sharp_C_silhouette(double *x, double *n, int *p, int *dist_method, double *minkowski_p, int *cl, int *k, int *neighbor, double *width,
+                        int *status);
+void sharp_C_calinski_harabasz(double *x, double *n, int *p, int *cl, int *k, int *kind, double *out, int *status);
 
 #ifdef __cplusplus
 }

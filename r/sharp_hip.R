@@ -399,3 +399,47 @@ sharp_plot_markers <- function(sginfo, label, N.marker, sN.cluster, filename, fi
     names(cols) <- unique(newc)
     list(sm = sm, sortmarker = sortmarker, ncells = length(cellind), mat_col = mat_col, mat_colors = list(cell_type = cols))
 }
+
+# ---- silhouette / Calinski-Harabasz on any labelling (R/get_opt_hclust.R:103-105,134-144; DESIGN.md 12) ---------------------------------
+# cluster::silhouette(x, dist): x = integer labels (or a SHARP result: its pred_clusters).  Either `dist` (a dist object, at most 46340
+# observations) or `data` (observations in rows: matrix-free on the GPU, no n x n matrix, any number of cells).  Returns an object of
+# class "silhouette" (columns cluster, neighbor, sil_width) as cluster::silhouette does, NA with fewer than 2 or more than n - 1 clusters.
+# (A tree from sharp_hclust is cut with R's own cutree.)
+sharp_silhouette <- function(x, dist = NULL, data = NULL, distance = "euclidean", p = 2) {
+    if (is.list(x)) x <- x$pred_clusters
+    if (is.null(dist) == is.null(data)) stop("give either dist (a dist object) or data (observations in rows)")
+    n <- length(x)
+    if (!all(x == round(x))) stop("'x' must only have integer codes")
+    f <- factor(x)
+    k <- nlevels(f)
+    if (k <= 1 || k >= n) return(NA)
+    cl <- as.integer(f)
+    if (!is.null(dist)) {
+        if (as.integer(attr(dist, "Size")) != n) stop("clustering 'x' and dissimilarity 'dist' are incompatible")
+        r <- .C("sharp_C_silhouette_dist", as.double(dist), n, cl, k, neighbor = integer(n), width = double(n), status = integer(1))
+    } else {
+        if (!distance %in% names(.sharp_dist_methods)) stop("invalid distance method")
+        data <- .sharp_dmat(data)
+        if (nrow(data) != n) stop("the number of labels differs from the number of observations")
+        r <- .C("sharp_C_silhouette", as.double(t(data)), as.double(n), ncol(data), .sharp_dist_methods[[distance]], as.double(p), cl, k,
+                neighbor = integer(n), width = double(n), status = integer(1))
+    }
+    .sharp_check(r$status)
+    lev <- as.numeric(levels(f))
+    structure(cbind(cluster = lev[cl], neighbor = lev[r$neighbor], sil_width = r$width), Ordered = FALSE, call = match.call(),
+              class = "silhouette")
+}
+
+# clusterCrit::intCriteria(data, labels, "Calinski_Harabasz") (distance = "euclidean", R/get_opt_hclust.R:105) and
+# clues::get_CH(data, labels, disMethod = "1-corr") (distance = "1-corr", R/get_opt_hclust.R:144); observations in rows
+sharp_calinski_harabasz <- function(data, labels, distance = "euclidean") {
+    kind <- match(distance, c("euclidean", "1-corr")) - 1L
+    if (is.na(kind)) stop("distance must be \"euclidean\" or \"1-corr\"")
+    data <- .sharp_dmat(data)
+    f <- factor(labels)
+    if (length(f) != nrow(data)) stop("the number of labels differs from the number of observations")
+    r <- .C("sharp_C_calinski_harabasz", as.double(t(data)), as.double(nrow(data)), ncol(data), as.integer(f), nlevels(f), kind,
+            out = double(1), status = integer(1))
+    .sharp_check(r$status)
+    r$out
+}

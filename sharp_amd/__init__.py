@@ -7,4 +7,5 @@ from ._lib import SharpError, init, lib, reload_options, shutdown, so_path  # no
 from .api import *  # noqa: F401,F403
 from .tsne import Rtsne  # noqa: F401
 from .tree import get_percluster_exp, hclust, plot_markers  # noqa: F401
+from .validity import calinski_harabasz, cutree, silhouette  # noqa: F401
 from . import dist  # noqa: F401,E402  (the multi-GPU module; calling it is R's dist() on the GPU, sharp_amd/tree.py)

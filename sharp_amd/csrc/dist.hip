@@ -12,33 +12,13 @@
 #include <cmath>
 #include <vector>
 
+#include "dist_pairs.hpp"
 #include "hclust.hpp"
 #include "linalg.hpp"
 
 namespace sharp {
 
 namespace {
-
-constexpr int DT = 64;          // pairs tile: DT x DT per workgroup of 256 lanes, a 4 x 4 block of pairs per lane
-constexpr int DK = 32;          // features staged per pass
-constexpr int DLD = DT + 2;     // LDS row stride in doubles: 16-byte aligned rows, transposed staging writes spread over the banks
-
-struct DistEuclid {
-    static __device__ __forceinline__ void acc(double &a, double d, double) { a += d * d; }
-    static __device__ __forceinline__ double fin(double a, double) { return sqrt(a); }
-};
-struct DistMaximum {
-    static __device__ __forceinline__ void acc(double &a, double d, double) { const double f = fabs(d); a = f > a ? f : a; }
-    static __device__ __forceinline__ double fin(double a, double) { return a; }
-};
-struct DistManhattan {
-    static __device__ __forceinline__ void acc(double &a, double d, double) { a += fabs(d); }
-    static __device__ __forceinline__ double fin(double a, double) { return a; }
-};
-struct DistMinkowski {
-    static __device__ __forceinline__ void acc(double &a, double d, double mp) { a += pow(fabs(d), mp); }
-    static __device__ __forceinline__ double fin(double a, double mp) { return pow(a, 1.0 / mp); }
-};
 
 // One workgroup per DT x DT tile of the full matrix (both triangles: |a - b| and (a - b)^2 are exactly symmetric, so the two copies of
 // a pair agree bitwise without a mirrored store).  The k-major LDS panels sA[k][row] / sB[k][col] are read as 16-byte vectors: a lane's
@@ -96,10 +76,6 @@ __global__ __launch_bounds__(256) void dist_kernel(const double *__restrict__ x,
     }
 }
 
-// R's dist vector: pair (i > j) at n j - j (j + 1) / 2 + i - j - 1 (column-wise lower triangle = scipy's pdist order)
-__device__ __forceinline__ long long cond_index(int n, int j, int i) {
-    return static_cast<long long>(n) * j - static_cast<long long>(j) * (j + 1) / 2 + (i - j - 1);
-}
 // cond <- the upper-triangle entries of row blockIdx.y (contiguous in the matrix and in the vector)
 __global__ __launch_bounds__(256) void dist_condense_kernel(const double *__restrict__ D, int n, int nld, double *__restrict__ cond) {
     const int r = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;

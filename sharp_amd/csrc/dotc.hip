@@ -256,4 +256,18 @@ void sharp_C_hclust(double *x, int *n, int *p, int *dist_method, double *minkows
     *status = sharp_hclust(x, *n, *p, static_cast<long long>(*p), *dist_method, *minkowski_p, *hmethod, merge, height, order);
 }
 
+/* ---- cluster::silhouette and the Calinski-Harabasz index on any labelling (validity.hip): x = as.double(t(x)), n as double; cl = the
+ * codes 1 .. k (as.integer(factor(labels))) */
+void sharp_C_silhouette_dist(double *d, int *n, int *cl, int *k, int *neighbor, double *width, int *status) {
+    *status = sharp_silhouette_dist(d, *n, cl, *k, neighbor, width);
+}
+void sharp_C_silhouette(double *x, double *n, int *p, int *dist_method, double *minkowski_p, int *cl, int *k, int *neighbor, double *width,
+                        int *status) {
+    *status = sharp_silhouette(x, as_ll(n), *p, static_cast<long long>(*p), *dist_method, *minkowski_p, cl, *k,
+                               neighbor, width);
+}
+void sharp_C_calinski_harabasz(double *x, double *n, int *p, int *cl, int *k, int *kind, double *out, int *status) {
+    *status = sharp_calinski_harabasz(x, as_ll(n), *p, static_cast<long long>(*p), cl, *k, *kind, out);
+}
+
 }  // extern "C"
