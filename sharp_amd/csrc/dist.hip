@@ -7,6 +7,7 @@
 //   "correlation"      as.dist(1 - cor(t(x))) (pheatmap's clustering_distance = "correlation"): the row preparation and fp64-MFMA GEMM of
 //                      get_opt_hclust (linalg.hip)
 //   condense / expand  R's dist vector (column-wise lower triangle) <-> the full symmetric nld x nld matrix the agglomeration reads
+//                      (hclust_tree, hclust.hip: one distance task through the chunk pipeline, the kernels of hclust_agglo.hip)
 //   HCASS2             hclust.f's conversion of the (ia, ib) merge list into R's merge matrix and leaf order, on the host (n <= 16384)
 #include <algorithm>
 #include <cmath>

@@ -1,4 +1,4 @@
-// a5b, the lane-program form of stats_kernel (included by hclust.hip; same arguments, same grid, same outputs).
+// a5b, the lane-program form of stats_kernel (included by hclust_stats.hip; same arguments, same grid, same outputs).
 //
 // One workgroup per (task, level) as in stats_kernel, and the same arithmetic per cell -- the sums over a level cluster's finest
 // clusters in ascending order, one division per cluster, the same silhouette and within-cluster terms, the same fixed order of the

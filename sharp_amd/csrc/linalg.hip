@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void gemm_tn_f64_kernel(const GemmTask *__rest
 // VGPRs); no bounds checks in the K loop, 16-byte loads, next K tile fetched into registers while the MFMAs run.
 constexpr int FT = 128, FLD = 144;   // 144 doubles per k row: two k rows of a half-wave land 32 banks apart
 
-constexpr double NN_INF = 1.0e300;   // (hclust.hip: HC_INF)
+constexpr double NN_INF = 1.0e300;   // (hclust_task.hpp: HC_INF)
 template <int CTRL>
 __device__ __forceinline__ double min_dpp_step(double x) {
     const int lo = __double2loint(x), hi = __double2hiint(x);

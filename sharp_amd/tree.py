@@ -3,8 +3,8 @@ plot_markers, R/plot_markers.R:38-242) and its small companion get_percluster_ex
 
 plot_markers is not only drawing: pheatmap(cluster_rows = T, cluster_cols = T, clustering_method = "ward.D") computes
 hclust(dist(sm), "ward.D") over the marker genes and hclust(dist(t(sm)), "ward.D") over up to ~10 000 cells.  Both run on the GPU here
-(sharp_dist / sharp_hclust, csrc/dist.hip + the agglomeration kernels of csrc/hclust.hip); the selection of markers and
-cells is host-side numpy and runs without a device."""
+(sharp_dist / sharp_hclust, csrc/dist.hip + the agglomeration kernels of csrc/hclust_agglo.hip behind hclust_tree of csrc/hclust.hip;
+DESIGN.md 11); the selection of markers and cells is host-side numpy and runs without a device."""
 import ctypes as C
 import math
 

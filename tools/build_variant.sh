@@ -1,7 +1,8 @@
 #!/bin/bash
 # tools/build_variant.sh NAME "-DFOO=1 ..." [file.hip | ../../tools/lab/file_lab.hip] [git-rev]: builds sharp_amd/variants/libsharp_hip_NAME.so with one
 # translation unit (default rp2.hip) compiled with extra flags, or taken from another git revision, for A/B runs on one box
-# (tools/bench_rp.py and tools/bench_hc.py load it when SHARP_VARIANT=NAME).
+# (tools/bench_rp.py and tools/bench_hc.py load it when SHARP_VARIANT=NAME).  The agglomeration kernels and their HR_TIMING / HR_ROUNDS /
+# HR_NO_FIRST_STAGE blocks are in hclust_agglo.hip: tools/build_variant.sh hrt "-DHR_TIMING" hclust_agglo.hip
 set -e
 cd "$(dirname "$0")/../sharp_amd/csrc"
 mkdir -p ../variants

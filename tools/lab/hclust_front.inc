@@ -1,5 +1,5 @@
 // hclust_front.inc -- a "lazy front" for the bulk-synchronous agglomeration (SHARP_HC_FRONT=1; an experiment behind a switch, round 5;
-// included by hclust.hip; R/get_opt_hclust.R:76-83, SURVEY.md App. A.4).
+// included by hclust_agglo.hip; R/get_opt_hclust.R:76-83, SURVEY.md App. A.4).
 //
 // hclust_rnn_kernel rewrites the whole distance matrix every round (read n_a^2, write n_b^2) although a round merges only ~10 % of the
 // clusters; the first four rounds of a 2000-observation task are 5.5 of the 10.2 n^2 entries it moves.  This kernel runs those first
@@ -24,18 +24,6 @@
 // the bound read from LDS per lane left waves spinning in the rescan phase -- found with a host-visible progress buffer, not understood.)
 constexpr int HF_THREADS = 1024;
 constexpr uint16_t HF_DEAD = 0, HF_PLAIN = 1;          // column state; 0x8000 | (2 rank + member): a member of this round's pair `rank`
-
-// byte offsets of hclust_rnn_kernel's state image (HR_THREADS = 1024: 16 waves), nal = (n + 3) & ~3
-struct HfImage {
-    int nal;
-    __device__ explicit HfImage(int n) : nal((n + 3) & ~3) {}
-    __device__ size_t dnn() const { return 0; }
-    __device__ size_t cid() const { return 16u * static_cast<size_t>(nal); }
-    __device__ size_t csz() const { return 20u * static_cast<size_t>(nal); }
-    __device__ size_t nn() const { return 24u * static_cast<size_t>(nal); }
-    __device__ size_t ctl() const { return 38u * static_cast<size_t>(nal); }
-    __device__ size_t tie() const { return 38u * static_cast<size_t>(nal) + 64 + 17 * 4; }
-};
 
 // the side area of a task inside its S1 scratch matrix (nld x nld doubles): tails of the n original rows (n x cap), then the new rows
 // (cap x ldnr, ldnr = n + cap): the largest cap (a multiple of 8) with n cap + cap (n + cap) <= nld^2, at most n / 2
@@ -63,8 +51,14 @@ __global__ __launch_bounds__(HF_THREADS) void hclust_front_kernel(const HcMeta *
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int nwave = HF_THREADS / 64;
     unsigned char *img = images + static_cast<long long>(blockIdx.x) * image_stride;
-    const HfImage IM(n);
-    int *ictl = reinterpret_cast<int *>(img + IM.ctl());
+    // hclust_rnn_kernel's state image (HR_THREADS = 1024: 16 waves): the arrays this kernel fills at its end
+    struct Image { double *dnn; uint16_t *cid, *csz, *nn; unsigned char *tie; int *ctl; };
+    const Image IM = [&]() {
+        unsigned char *lds_cursor = img;
+        HR_STATE_ARRAYS(LDS_CARVE, (n + 3) & ~3, 1024 / 64)
+        return Image{dnnA, cidA, cszA, nn, tie, ctl};
+    }();
+    int *ictl = IM.ctl;
     const int cap = hf_cap(n, nld);
     auto abandon = [&]() {                                     // (every thread of the workgroup takes this exit together)
         if (tid == 0) { status[blockIdx.x] = 1; for (int q = 0; q < 16; ++q) ictl[q] = 0; ictl[10] = 1; }
@@ -340,10 +334,10 @@ __global__ __launch_bounds__(HF_THREADS) void hclust_front_kernel(const HcMeta *
         for (int x = lo; x < hi; ++x) { if (alive[x]) { col[x] = static_cast<uint16_t>(pos); plist[pos] = static_cast<uint16_t>(x); ++pos; } else col[x] = 0xffffu; }
         __syncthreads();
     }
-    double *idnn = reinterpret_cast<double *>(img + IM.dnn());
-    uint16_t *icid = reinterpret_cast<uint16_t *>(img + IM.cid()), *icsz = reinterpret_cast<uint16_t *>(img + IM.csz());
-    uint16_t *inn = reinterpret_cast<uint16_t *>(img + IM.nn());
-    unsigned char *itie = img + IM.tie();
+    double *idnn = IM.dnn;
+    uint16_t *icid = IM.cid, *icsz = IM.csz;
+    uint16_t *inn = IM.nn;
+    unsigned char *itie = IM.tie;
     for (int A = wave; A < na; A += nwave) {
         const int c = __builtin_amdgcn_readfirstlane(static_cast<int>(plist[A]));
         const Row rc = rowof(c);

@@ -1,4 +1,4 @@
-// hclust_lazy.inc -- included by hclust.hip (namespace sharp): the bulk-synchronous agglomeration WITHOUT a rewrite of the distance
+// hclust_lazy.inc -- included by hclust_agglo.hip (namespace sharp): the bulk-synchronous agglomeration WITHOUT a rewrite of the distance
 // matrix in every round (row a4 of SURVEY.md 8; R/get_opt_hclust.R:76-83, stats::hclust restated as in hclust_kernel).
 //
 // hclust_rnn_kernel streams the whole matrix into a compacted copy in each of its ~45 rounds although a round merges only ~10 % of

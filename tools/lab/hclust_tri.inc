@@ -1,5 +1,5 @@
 // hclust_tri.inc -- the bulk-synchronous agglomeration of hclust_rnn_kernel (MODE 0: one launch, one workgroup per task) on the UPPER
-// TRIANGLE of the distance matrix: half the bytes per round.  (Included by hclust.hip; R/get_opt_hclust.R:76-83, SURVEY.md App. A.4.)
+// TRIANGLE of the distance matrix: half the bytes per round.  (Included by hclust_agglo.hip; R/get_opt_hclust.R:76-83, SURVEY.md App. A.4.)
 //
 // hclust_rnn_kernel keeps the symmetric matrix in full: every round reads n_a^2 and writes n_b^2 entries, 10.1 n^2 x 8 B per task over
 // the ~45 rounds of a 2000-observation task, and its time is those bytes (4.4 of the 5 TB/s a copy reaches).  Here row A of a scratch
@@ -35,6 +35,32 @@ __device__ __forceinline__ unsigned long long ht_key(unsigned long long ord, int
     return (ord & ~0xffffull) | static_cast<unsigned long long>(static_cast<unsigned int>(idx) & 0xffffu);
 }
 
+// The dynamic LDS of hclust_tri_kernel (a list for LDS_CARVE / LDS_COUNT, hclust_task.hpp): hclust_rnn_kernel's state arrays with the
+// column keys behind dnnA; nal = (n + 3) & ~3
+#define HT_STATE_ARRAYS(X, nal)                                                                                             \
+    X(double, dnnA, 2 * (nal))               /* [2][nal]  NN distance (also the pair's height) */                           \
+    X(unsigned long long, colkey, nal)       /* best (distance, row) offered to a column */                                 \
+    X(uint16_t, cidA, 2 * (nal))             /* [2][nal]  smallest original member */                                       \
+    X(uint16_t, cszA, 2 * (nal))             /* [2][nal]  cluster size */                                                   \
+    X(uint16_t, nn, nal)                                                                                                    \
+    X(uint16_t, partner, nal)                /* old index of the RNN partner or NONE */                                     \
+    X(uint16_t, pseq, nal)                   /* rank of the pair in the round */                                            \
+    X(uint16_t, oldidx, nal)                 /* new index -> old index */                                                   \
+    X(uint16_t, newidx, nal)                 /* old index -> new index */                                                   \
+    X(uint16_t, plist, nal)                  /* first members of the pairs */                                               \
+    X(uint16_t, colmap, nal)                 /* old column -> new column, or 0x8000 | (2 rank + member) */                  \
+    X(int, ctl, 16)                          /* 0 npairs, 1 abort */                                                        \
+    X(int, wsum, HT_THREADS / 64 + 1)                                                                                       \
+    X(unsigned char, tie, nal)
+// the launch: the state (64 unused bytes of slack behind it) or the final sort of the merges in the same memory (16 B per entry), and
+// whatever else the CU has as the waves' stage
+inline size_t hclust_tri_lds(int max_n) {
+    const int nal = (max_n + 3) & ~3;
+    size_t lds_bytes = 0;
+    HT_STATE_ARRAYS(LDS_COUNT, nal)
+    return std::max(std::max((lds_bytes + 64 + 15) / 16 * 16, static_cast<size_t>(hc_npow2(max_n - 1)) * 16), HR_LDS_CU);
+}
+
 __global__ __launch_bounds__(HT_THREADS) void hclust_tri_kernel(const HcMeta *__restrict__ metas, const double *__restrict__ Dall,
                                                                 double *__restrict__ S0all, double *__restrict__ S1all,
                                                                 int *__restrict__ ia_all, int *__restrict__ ib_all,
@@ -53,21 +79,9 @@ __global__ __launch_bounds__(HT_THREADS) void hclust_tri_kernel(const HcMeta *__
     }
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     const int nal = (n + 3) & ~3;
-    double *dnnA = reinterpret_cast<double *>(sm);                          // [2][nal]  NN distance (also the pair's height)
-    unsigned long long *colkey = reinterpret_cast<unsigned long long *>(dnnA + 2 * nal);   // [nal]  best (distance, row) offered to a column
-    uint16_t *cidA = reinterpret_cast<uint16_t *>(colkey + nal);            // [2][nal]  smallest original member
-    uint16_t *cszA = cidA + 2 * nal;                                        // [2][nal]  cluster size
-    uint16_t *nn = cszA + 2 * nal;                                          // [nal]
-    uint16_t *partner = nn + nal;                                           // [nal]     old index of the RNN partner or NONE
-    uint16_t *pseq = partner + nal;                                         // [nal]     rank of the pair in the round
-    uint16_t *oldidx = pseq + nal;                                          // [nal]     new index -> old index
-    uint16_t *newidx = oldidx + nal;                                        // [nal]     old index -> new index
-    uint16_t *plist = newidx + nal;                                         // [nal]     first members of the pairs
-    uint16_t *colmap = plist + nal;                                         // [nal]     old column -> new column, or 0x8000 | (2 rank + member)
-    int *ctl = reinterpret_cast<int *>(colmap + nal);                       // [16]: 0 npairs, 1 abort
-    int *wsum = ctl + 16;                                                   // [nwave + 1]
-    unsigned char *tie = reinterpret_cast<unsigned char *>(wsum + nwave + 1);   // [nal]
-    const int stage_off = static_cast<int>((tie + nal - sm + 15) & ~static_cast<long>(15));
+    unsigned char *lds_cursor = sm;
+    HT_STATE_ARRAYS(LDS_CARVE, nal)                                         // declares dnnA, colkey, cidA, ... tie (the list above)
+    const int stage_off = static_cast<int>((lds_cursor - sm + 15) & ~static_cast<long>(15));
     double *stage = reinterpret_cast<double *>(sm + stage_off);
 
 #ifdef SHARP_LAB_HT_GUARD         // (lab build: every outer loop spends from a budget; an exhausted budget ends the thread with a code in status)
