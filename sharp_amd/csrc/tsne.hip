@@ -2,8 +2,8 @@
 //   input preparation   column means / sd (slab partials), X^T X on the f64 MFMA as slab partials summed in a fixed order, a host
 //                       symmetric eigensolver (Householder tridiagonalisation + implicit QL), the projection X V; centring and division
 //                       by the largest |entry|
-//   exact k-NN          distances ||x_i||^2 + ||x_j||^2 - 2 x_i.x_j on v_mfma_f64_16x16x4_f64 over streamed column tiles, a per-row top-K
-//                       in LDS behind a threshold filter, the chosen K re-ranked by a direct sum (x_i - x_j)^2
+//   exact k-NN          distances ||w_i||^2 + ||w_j||^2 - 2 w_i.w_j of the centred rows w = x - mean on v_mfma_f64_16x16x4_f64 over streamed
+//                       column tiles, a per-row top-K in LDS behind a threshold filter, the chosen K re-ranked by a direct sum (x_i - x_j)^2
 //   calibration         one wave per row, fp64 bisection on beta (bhtsne's rule)
 //   symmetrisation      COO (i, j, p) + (j, i, p), radix sort by (row, col), duplicates merged, normalised by a fixed-order sum -> CSR
 //   optimiser loop      attraction over the CSR rows (fp64); exact repulsion, a workgroup owning 256 rows and streaming every y_j through
@@ -1273,10 +1273,18 @@ void tsne_knn(const double *dX, long long n, int d, int K, DevBuf<int> &idx, Dev
     Ctx &c = ctx();
     SHARP_REQUIRE(K >= 1 && K <= 255 && n - 1 >= K, "tsne_knn: need 1 <= K <= 255 and K < n");
     KernelTimer t("tsne_knn");
+    // The candidates are selected on w = x - column mean (fp64): distances do not change under a translation, but the error of
+    // ||x_i||^2 + ||x_j||^2 - 2 x_i.x_j scales with ||x||^2, and input far from the origin (Rtsne(pca = FALSE, normalize = FALSE),
+    // sharp_tsne_knn) would otherwise lose true neighbours to it.  The merge re-ranks the chosen K on the caller's values.
+    DevBuf<double> Xc(static_cast<size_t>(n) * d), mu(d), mupart;
+    column_stat(dX, n, d, d, nullptr, static_cast<double>(n), mupart, mu.p);
+    hipLaunchKernelGGL(affine_kernel, dim3(grid_for(n * d, 256)), dim3(256), 0, c.stream, dX, n, d, static_cast<long long>(d), mu.p, nullptr, 1.0,
+                       Xc.p);
+    launch_check("affine_kernel");
     DevBuf<double> nrm(n);
     DevBuf<int> bad(1);
     bad.zero();
-    hipLaunchKernelGGL(rownorm_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, dX, n, d, nrm.p);
+    hipLaunchKernelGGL(rownorm_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, Xc.p, n, d, nrm.p);
     hipLaunchKernelGGL(norm_check_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, nrm.p, n, bad.p);
     launch_check("norm_check_kernel");
     int hb = 0;
@@ -1298,7 +1306,7 @@ void tsne_knn(const double *dX, long long n, int d, int K, DevBuf<int> &idx, Dev
     const size_t lds_merge = (sizeof(double) + sizeof(int)) * 4 * K;
     for (long long r0 = 0; r0 < n; r0 += rows) {
         const long long r1 = std::min(n, r0 + rows);
-        hipLaunchKernelGGL(knn_kernel, dim3(grid_for(r1 - r0, KQ), nc), dim3(256), lds, c.stream, dX, nrm.p, n, d, K, r0, r1, cj, pidx.p, pdist.p);
+        hipLaunchKernelGGL(knn_kernel, dim3(grid_for(r1 - r0, KQ), nc), dim3(256), lds, c.stream, Xc.p, nrm.p, n, d, K, r0, r1, cj, pidx.p, pdist.p);
         launch_check("knn_kernel");
         hipLaunchKernelGGL(knn_merge_kernel, dim3(grid_for(r1 - r0, 4)), dim3(256), lds_merge, c.stream, dX, n, d, K, r0, r1 - r0, nc, pidx.p,
                            pdist.p, idx.p, dist.p, bad.p);

@@ -1,6 +1,9 @@
 """numpy fp64 reference of the t-SNE specification in DESIGN.md §10 (test infrastructure only: the product never imports it).
 
 Written straight from the specification, not for speed: brute-force k-NN, vectorised bisection, dense exact repulsion."""
+import os
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 
 FLT_MIN = np.float32(np.finfo(np.float32).tiny).item()
@@ -54,8 +57,10 @@ def knn(X, K, chunk=256):
     return idx, dist
 
 
-def calibrate(dist, perplexity, tol=1e-5, steps=200):
-    """bhtsne's bisection on beta per row (entropy in nats); returns P_cond (n x K)"""
+def calibrate(dist, perplexity, tol=1e-5, steps=200, return_trace=False):
+    """bhtsne's bisection on beta per row (entropy in nats); returns P_cond (n x K).  With return_trace also, per row, the number of
+    steps taken (entropy evaluations, the one that stops included) and the smallest | |Hdiff| - tol | met: the margin of the row's stop
+    decisions.  A row whose margin is far above the rounding error of H takes the same steps under any faithful evaluation."""
     n, K = dist.shape
     logU = np.log(perplexity)
     beta = np.ones(n)
@@ -64,6 +69,8 @@ def calibrate(dist, perplexity, tol=1e-5, steps=200):
     active = np.ones(n, bool)
     P = np.zeros_like(dist)
     sumP = np.full(n, DBL_MIN)
+    taken = np.zeros(n, np.int64)
+    margin = np.full(n, np.inf)
     for _ in range(steps):
         a = np.flatnonzero(active)
         if a.size == 0:
@@ -74,6 +81,8 @@ def calibrate(dist, perplexity, tol=1e-5, steps=200):
         P[a] = Pa
         sumP[a] = s
         Hdiff = H - logU
+        taken[a] += 1
+        margin[a] = np.minimum(margin[a], np.abs(np.abs(Hdiff) - tol))
         done = (Hdiff < tol) & (-Hdiff < tol)
         up = ~done & (Hdiff > 0)
         dn = ~done & ~(Hdiff > 0)
@@ -85,7 +94,8 @@ def calibrate(dist, perplexity, tol=1e-5, steps=200):
         open_dn = (minb[a[dn]] == -DBL_MAX) | (minb[a[dn]] == DBL_MAX)
         beta[a[dn]] = np.where(open_dn, b[dn] / 2.0, (b[dn] + minb[a[dn]]) / 2.0)
         active[a[done]] = False
-    return P / sumP[:, None]
+    Pc = P / sumP[:, None]
+    return (Pc, taken, margin) if return_trace else Pc
 
 
 def joint_p(X, perplexity):
@@ -139,6 +149,51 @@ def kl(P, Y, per_point=False):
     r, c, p = _pairs(P)
     terms = p * np.log((p + FLT_MIN) / (Q[r, c] / Z + FLT_MIN))
     return np.bincount(r, weights=terms, minlength=n) if per_point else terms.sum()
+
+
+def multiset_repulsion(pos, cnt, chunk=32, threads=8):
+    """The exact repulsion of the n = sum(cnt) points Y = pos[assign] in which the distinct position a occurs cnt[a] times, at
+    O(m^2 dims) for m positions instead of O(n^2).  With q_ab = 1 / (1 + |y_a - y_b|^2) it returns, per position,
+        rep[a]  = sum_b c_b q_ab^2 (y_a - y_b)            (the point's own copies add nothing: their difference is 0)
+        z[a]    = sum_b c_b q_ab - 1                      (the self pair taken out; the other c_a - 1 copies stay, at q = 1)
+        A[a, k] = sum_b c_b q_ab^2 |y_a,k - y_b,k|        (the sum of the magnitudes of rep's terms: what a rounding bound scales with)
+    so a point at position a has repulsion rep[a] and row sum z[a], and Z = sum_a c_a z[a].  Plain fp64; the rows go in chunks small
+    enough for the cache, a few chunks at a time on threads (numpy releases the lock; a chunk's result does not depend on the others)."""
+    pos = np.asarray(pos, np.float64)
+    w = np.asarray(cnt, np.float64)
+    m, dims = pos.shape
+    rep = np.zeros((m, dims))
+    A = np.zeros((m, dims))
+    z = np.zeros(m)
+    cols = [np.ascontiguousarray(pos[:, k]) for k in range(dims)]
+
+    def block(r0):
+        r1 = min(m, r0 + chunk)
+        d = [cols[k][r0:r1, None] - cols[k][None, :] for k in range(dims)]
+        t = np.empty_like(d[0])
+        D = np.ones_like(t)
+        for k in range(dims):
+            np.multiply(d[k], d[k], out=t)
+            D += t
+        q = np.divide(w[None, :], D)             # c_b q_ab
+        z[r0:r1] = q.sum(1) - 1.0
+        q /= D                                   # c_b q_ab^2
+        for k in range(dims):
+            np.multiply(q, d[k], out=t)
+            rep[r0:r1, k] = t.sum(1)
+            np.abs(t, out=t)
+            A[r0:r1, k] = t.sum(1)
+
+    with ThreadPoolExecutor(max(1, min(threads, os.cpu_count() or 1))) as ex:
+        list(ex.map(block, range(0, m, chunk)))
+    return rep, z, A
+
+
+def exact_repulsion(Y, chunk=32):
+    """rep (n x dims), z (n) and A (n x dims) of multiset_repulsion for the rows of Y themselves, every row counted once: the dense
+    exact repulsion in row chunks, without an n x n matrix"""
+    Y = np.asarray(Y, np.float64)
+    return multiset_repulsion(Y, np.ones(Y.shape[0]), chunk)
 
 
 def init_y(n, dims, seed, runif):

@@ -52,6 +52,74 @@ def test_reference_gradient_is_the_kl_derivative_over_four():
     np.testing.assert_allclose(g, fd / 4.0, rtol=1e-5, atol=1e-5 * np.abs(fd / 4).max())
 
 
+@pytest.mark.parametrize("dims", [1, 2, 3])
+def test_reference_multiset_and_chunked_repulsion_match_the_dense_gradient(dims):
+    """multiset_repulsion (m distinct positions with multiplicities) and exact_repulsion (row chunks) against ref.gradient's dense
+    n x n pass: with an empty P the gradient is -rep / Z"""
+    import scipy.sparse as sp
+
+    rng = np.random.default_rng(40 + dims)
+    m, n = 37, 900
+    pos = rng.normal(size=(m, dims)) * 3
+    cnt = rng.multinomial(n - m, np.full(m, 1.0 / m)) + 1
+    assign = rng.permutation(np.repeat(np.arange(m), cnt))
+    Y = pos[assign]
+    g, Z = ref.gradient(sp.csr_matrix((n, n)), Y, return_z=True)
+    rep, z, A = ref.multiset_repulsion(pos, cnt)
+    Zm = float(cnt @ z)
+    assert abs(Zm - Z) <= 1e-12 * Z
+    np.testing.assert_allclose(-rep[assign] / Zm, g, rtol=0, atol=1e-12 * np.abs(g).max())
+    # A: the sum of the magnitudes of rep's terms, by the definition
+    d = Y[:, None, :] - Y[None, :, :]
+    q2 = 1.0 / (1.0 + (d ** 2).sum(-1)) ** 2
+    np.testing.assert_allclose(A[assign], (q2[:, :, None] * np.abs(d)).sum(1), rtol=1e-12, atol=0)
+    assert (np.abs(rep) <= A).all()
+    # all rows distinct, n no multiple of the chunk, and a chunk length of its own
+    Yd = rng.normal(size=(333, dims)) * 3
+    gd, Zd = ref.gradient(sp.csr_matrix((333, 333)), Yd, return_z=True)
+    for chunk in (32, 100):
+        rep, z, A = ref.exact_repulsion(Yd, chunk)
+        assert abs(z.sum() - Zd) <= 1e-12 * Zd
+        np.testing.assert_allclose(-rep / z.sum(), gd, rtol=0, atol=1e-12 * np.abs(gd).max())
+    repm, zm, Am = ref.multiset_repulsion(Yd, np.ones(333))
+    assert np.array_equal(repm, ref.exact_repulsion(Yd)[0]) and np.array_equal(Am, ref.exact_repulsion(Yd)[2])
+
+
+def test_reference_calibration_trace_against_a_row_at_a_time_bisection():
+    """calibrate(return_trace=True): the same P as without, and per row the steps and the stop margin of a scalar restatement of
+    bhtsne's loop; rows that double beta for long (a tight clump) and rows that halve it (distances in the hundreds)"""
+    X, _ = _blobs(300, 6, 3, 6)
+    X[50:120] = X[50] + 1e-4 * np.random.default_rng(7).normal(size=(70, 6))
+    X[200:] *= 30.0
+    perp, K = 10, 30
+    _, dist = ref.knn(X, K)
+    P = ref.calibrate(dist, perp)
+    Pt, steps, margin = ref.calibrate(dist, perp, return_trace=True)
+    assert np.array_equal(P, Pt) and steps.shape == margin.shape == (300,)
+    logU = np.log(perp)
+    betas = np.zeros(300)
+    for i in range(300):
+        beta, lo, hi, n_steps, mg = 1.0, -ref.DBL_MAX, ref.DBL_MAX, 0, np.inf
+        for _ in range(200):
+            p = np.exp(-beta * dist[i])
+            s = ref.DBL_MIN + p.sum()
+            Hdiff = (beta * (dist[i] * p)).sum() / s + np.log(s) - logU
+            n_steps += 1
+            mg = min(mg, abs(abs(Hdiff) - 1e-5))
+            if Hdiff < 1e-5 and -Hdiff < 1e-5:
+                break
+            if Hdiff > 0:
+                lo = beta
+                beta = beta * 2.0 if hi == ref.DBL_MAX else (beta + hi) / 2.0
+            else:
+                hi = beta
+                beta = beta / 2.0 if lo == -ref.DBL_MAX else (beta + lo) / 2.0
+        betas[i] = beta
+        assert steps[i] == n_steps and margin[i] == mg, i
+        np.testing.assert_allclose(Pt[i], p / s, rtol=1e-15, atol=0)
+    assert betas[50:120].min() > 2.0 ** 20 and betas[200:].max() < 0.25 and steps.max() < 200
+
+
 def _declared():
     src = open(os.path.join(ROOT, "include", "sharp_hip.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
