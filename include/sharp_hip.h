@@ -396,6 +396,29 @@ int sharp_tsne_bh(const double *X, long long n, int d, long long ld, int dims, i
 /* The gradient stage with that repulsion: dY (n x dims) at Y for P; Z (NULL or one double) receives the normalisation Z it used. */
 int sharp_tsne_gradient_bh(const long long *row_ptr, const int *col, const double *val, long long n, int dims, const double *Y, double theta,
                            double *dY, double *Z);
+/* Rtsne's two other ways in (DESIGN.md §10 "Given neighbours, given distances").  Both skip PCA, normalisation and the duplicate check
+ * and run sharp_tsne's calibration, symmetrisation and optimiser unchanged; repulsion: 0 exact (theta unused), 1 Barnes-Hut (theta
+ * checked as sharp_tsne_bh checks it); Y_init, seed, Y, itercosts, costs as in sharp_tsne.
+ * sharp_tsne_neighbors = Rtsne_neighbors(index, distance, ...): index / distance n x K row-major, index 0-based; 1 <= K <= 255,
+ * K <= n - 1; squared = 0: Euclidean distances, squared on the device; 1: already squared (what sharp_tsne_knn returns).  perplexity
+ * <= K (this library's rule: the entropy of K neighbours cannot pass log K) and n - 1 >= 3 perplexity ("Perplexity is too large.").
+ * A kernel validates the lists before anything dereferences an index: every index in [0, n), none its own row, none twice in a row,
+ * every distance finite and >= 0; the message names the first offending row.  A row's neighbours are used in the caller's order, so
+ * sharp_tsne_knn's lists give sharp_tsne(pca = 0, normalize = 0)'s bits.
+ * sharp_tsne_dist = Rtsne(d, is_distance = TRUE, ...): d = R's dist vector as sharp_dist returns it, every entry finite and >= 0,
+ * 2 <= n <= SHARP_DIST_MAX_N (checked before d is read).  The K = floor(3 perplexity) nearest objects of each (perplexity <= 85) are
+ * selected on the distances as given -- exact comparisons, ties to the lower index, self excluded --, P uses d^2. */
+int sharp_tsne_neighbors(const int *index, const double *distance, long long n, int K, int squared, int repulsion, int dims, double perplexity,
+                         double theta, int max_iter, int stop_lying_iter, int mom_switch_iter, double momentum, double final_momentum, double eta,
+                         double exaggeration_factor, const double *Y_init, double seed, double *Y, double *itercosts, double *costs);
+int sharp_tsne_dist(const double *d, int n, int repulsion, int dims, double perplexity, double theta, int max_iter, int stop_lying_iter,
+                    int mom_switch_iter, double momentum, double final_momentum, double eta, double exaggeration_factor, const double *Y_init,
+                    double seed, double *Y, double *itercosts, double *costs);
+/* Their stages (tests, users who want P).  _knn_dist: idx (n x K, 0-based) and dist2 = d^2 of the K nearest objects, sorted by
+ * (distance, index).  _affinities_nn: sharp_tsne_affinities from given lists (cap >= 2 n K always suffices). */
+int sharp_tsne_knn_dist(const double *d, int n, int K, int *idx, double *dist2);
+int sharp_tsne_affinities_nn(const int *index, const double *distance, long long n, int K, int squared, double perplexity, long long cap,
+                             long long *row_ptr, int *col, double *val, long long *nnz);
 
 /* ---- dist / hclust as a tree: what pheatmap(cluster_rows = T, cluster_cols = T, clustering_method = "ward.D") computes inside
  * plot_markers (R/plot_markers.R:214-237), i.e. hclust(dist(sm), "ward.D") over the marker genes and hclust(dist(t(sm)), "ward.D") over up
@@ -536,6 +559,15 @@ void sharp_C_tsne(double *X, double *n, int *d, int *dims, int *initial_dims, in
                   int *check_duplicates, double *perplexity, double *theta, int *max_iter, int *stop_lying_iter, int *mom_switch_iter,
                   double *momentum, double *final_momentum, double *eta, double *exaggeration, int *has_Y_init, double *Y_init, double *seed,
                   double *Y, double *itercosts, double *costs, int *status);
+/* sharp_tsne_neighbors / sharp_tsne_dist / sharp_tsne_knn in the same convention (index 0-based here too: r/sharp_hip.R subtracts 1) */
+void sharp_C_tsne_neighbors(int *index, double *distance, double *n, int *K, int *squared, int *repulsion, int *dims, double *perplexity,
+                            double *theta, int *max_iter, int *stop_lying_iter, int *mom_switch_iter, double *momentum,
+                            double *final_momentum, double *eta, double *exaggeration, int *has_Y_init, double *Y_init, double *seed, double *Y,
+                            double *itercosts, double *costs, int *status);
+void sharp_C_tsne_dist(double *d, int *n, int *repulsion, int *dims, double *perplexity, double *theta, int *max_iter, int *stop_lying_iter,
+                       int *mom_switch_iter, double *momentum, double *final_momentum, double *eta, double *exaggeration, int *has_Y_init,
+                       double *Y_init, double *seed, double *Y, double *itercosts, double *costs, int *status);
+void sharp_C_tsne_knn(double *X, double *n, int *d, int *K, int *idx, double *dist, int *status);
 /* sharp_tsne_bh in the same convention: sharp_C_tsne's arguments, theta honoured */
 void sharp_C_tsne_bh(double *X, double *n, int *d, int *dims, int *initial_dims, int *pca, int *pca_center, int *pca_scale, int *normalize,
                      int *check_duplicates, double *perplexity, double *theta, int *max_iter, int *stop_lying_iter, int *mom_switch_iter,

@@ -226,6 +226,85 @@ SEXP R_sharp_unlimited_multi(SEXP blocks, SEXP ipar, SEXP seed, SEXP viewflag_, 
     return out;
 }
 
+/* Rtsne_neighbors / Rtsne(is_distance = TRUE) (r/sharp_hip.R::sharp_Rtsne_neighbors, sharp_Rtsne): R's matrices are read in place.
+ *   ipar = squared, repulsion (0 exact, 1 Barnes-Hut), dims, max_iter, stop_lying_iter, mom_switch_iter
+ *   dpar = perplexity, theta, momentum, final_momentum, eta, exaggeration_factor, seed
+ *   Y_init: an n x dims numeric matrix, or numeric(0) for none */
+static SEXP tsne_result(const double *Yrow, SEXP ic, SEXP costs, int n, int dims) {
+    const char *names[] = {"Y", "itercosts", "costs", ""};
+    SEXP out = PROTECT(mkNamed(VECSXP, names));
+    SEXP Y = PROTECT(allocMatrix(REALSXP, n, dims));
+    double *y = REAL(Y);
+    for (int i = 0; i < n; ++i) for (int k = 0; k < dims; ++k) y[(size_t)k * n + i] = Yrow[(size_t)i * dims + k];
+    SET_VECTOR_ELT(out, 0, Y);
+    SET_VECTOR_ELT(out, 1, ic);
+    SET_VECTOR_ELT(out, 2, costs);
+    UNPROTECT(2);
+    return out;
+}
+static int tsne_ncost(int max_iter) {
+    int c = 0;
+    for (int it = 0; it < max_iter; ++it) c += (it > 0 && it % 50 == 0) || it == max_iter - 1;
+    return c;
+}
+/* row-major copy of the n x dims matrix Y_init, or NULL for numeric(0) */
+static const double *tsne_y_init(SEXP Y_init, int n, int dims) {
+    if (XLENGTH(Y_init) == 0) return NULL;
+    if (!isReal(Y_init) || XLENGTH(Y_init) != (R_xlen_t)n * dims) error("Y_init must be an n x dims matrix");
+    double *y0 = (double *)R_alloc((size_t)n * dims, sizeof(double));
+    const double *s = REAL(Y_init);
+    for (int i = 0; i < n; ++i) for (int k = 0; k < dims; ++k) y0[(size_t)i * dims + k] = s[(size_t)k * n + i];
+    return y0;
+}
+
+/* index: R's integer matrix n x K, 1-based; distance: numeric matrix n x K */
+SEXP R_sharp_tsne_neighbors(SEXP index, SEXP distance, SEXP ipar, SEXP dpar, SEXP Y_init) {
+    if (!isReal(distance) || !isInteger(index)) error("index must be an integer matrix and distance a numeric matrix");
+    const int n = nrows(distance), K = ncols(distance), *ip = INTEGER(ipar), dims = ip[2];
+    const double *dp = REAL(dpar);
+    if (XLENGTH(index) != (R_xlen_t)n * K) error("index and distance differ in shape");
+    if (dims < 1 || dims > 3) error("Rtsne: dims must be 1, 2 or 3");
+    /* n x K row-major, 0-based (an NA index, INT_MIN, stays out of range) */
+    int *idx = (int *)R_alloc((size_t)n * K, sizeof(int));
+    double *dist = (double *)R_alloc((size_t)n * K, sizeof(double));
+    const int *si = INTEGER(index);
+    const double *sd = REAL(distance);
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < K; ++k) {
+            const int v = si[(size_t)k * n + i];
+            idx[(size_t)i * K + k] = v > 0 ? v - 1 : -1;
+            dist[(size_t)i * K + k] = sd[(size_t)k * n + i];
+        }
+    const double *y0 = tsne_y_init(Y_init, n, dims);
+    const int nc = tsne_ncost(ip[3]);
+    SEXP ic = PROTECT(allocVector(REALSXP, nc));
+    SEXP costs = PROTECT(allocVector(REALSXP, n));
+    double *Y = (double *)R_alloc((size_t)n * dims, sizeof(double));
+    chk(sharp_tsne_neighbors(idx, dist, n, K, ip[0], ip[1], dims, dp[0], dp[1], ip[3], ip[4], ip[5], dp[2], dp[3], dp[4], dp[5], y0, dp[6], Y,
+                             nc ? REAL(ic) : NULL, REAL(costs)));
+    SEXP out = tsne_result(Y, ic, costs, n, dims);
+    UNPROTECT(2);
+    return out;
+}
+
+/* d: a dist object's vector (n (n - 1) / 2 doubles), read in place; n = attr(d, "Size"); ipar[0] (squared) is unused */
+SEXP R_sharp_tsne_dist(SEXP d, SEXP n_, SEXP ipar, SEXP dpar, SEXP Y_init) {
+    const int n = asInteger(n_), *ip = INTEGER(ipar), dims = ip[2];
+    const double *dp = REAL(dpar);
+    if (!isReal(d) || n < 2 || XLENGTH(d) != (R_xlen_t)n * (n - 1) / 2) error("d must hold the n (n - 1) / 2 distances of a dist object");
+    if (dims < 1 || dims > 3) error("Rtsne: dims must be 1, 2 or 3");
+    const double *y0 = tsne_y_init(Y_init, n, dims);
+    const int nc = tsne_ncost(ip[3]);
+    SEXP ic = PROTECT(allocVector(REALSXP, nc));
+    SEXP costs = PROTECT(allocVector(REALSXP, n));
+    double *Y = (double *)R_alloc((size_t)n * dims, sizeof(double));
+    chk(sharp_tsne_dist(REAL(d), n, ip[1], dims, dp[0], dp[1], ip[3], ip[4], ip[5], dp[2], dp[3], dp[4], dp[5], y0, dp[6], Y,
+                        nc ? REAL(ic) : NULL, REAL(costs)));
+    SEXP out = tsne_result(Y, ic, costs, n, dims);
+    UNPROTECT(2);
+    return out;
+}
+
 static const R_CallMethodDef call_methods[] = {
     {"R_sharp_init", (DL_FUNC)&R_sharp_init, 1},
     {"R_sharp_trim", (DL_FUNC)&R_sharp_trim, 0},
@@ -233,6 +312,8 @@ static const R_CallMethodDef call_methods[] = {
     {"R_sharp_SHARP_csc", (DL_FUNC)&R_sharp_SHARP_csc, 7},
     {"R_sharp_unlimited", (DL_FUNC)&R_sharp_unlimited, 4},
     {"R_sharp_unlimited_multi", (DL_FUNC)&R_sharp_unlimited_multi, 6},
+    {"R_sharp_tsne_neighbors", (DL_FUNC)&R_sharp_tsne_neighbors, 5},
+    {"R_sharp_tsne_dist", (DL_FUNC)&R_sharp_tsne_dist, 5},
     {NULL, NULL, 0}};
 
 void R_init_sharp_glue(DllInfo *dll) {

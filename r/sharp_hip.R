@@ -281,21 +281,62 @@ sharp_last_decisions <- function(cap = 65536L) {
 # Rtsne(x1, ...) as R/visualization_SHARP.R:94 calls it: replace `Rtsne(` there by `sharp_Rtsne(`.  Rtsne's formals and return list;
 # Y drawn from set.seed(seed)'s stream when Y_init is NULL.  repulsion = "exact": the exact repulsion on the GPU (theta accepted and
 # unused, DESIGN.md 10); "barnes_hut": bhtsne's Barnes-Hut repulsion with theta honoured (sharp_C_tsne_bh).
+# is_distance = TRUE: X is a `dist` object (sharp_dist's, stats::dist's) or a square symmetric matrix with finite entries >= 0; the
+# floor(3 perplexity) nearest objects are selected on the distances as given and pca, initial_dims, normalize and check_duplicates
+# are ignored (sharp_C_tsne_dist).
+.sharp_ncost <- function(max_iter) { iters <- seq_len(max_iter) - 1L; sum((iters > 0 & iters %% 50 == 0) | iters == max_iter - 1L) }
+.sharp_repulsion <- function(repulsion, who)
+    switch(repulsion, exact = 0L, barnes_hut = 1L, stop(who, ": repulsion must be \"exact\" or \"barnes_hut\""))
+.sharp_tsne_list <- function(n, Y, costs, itercosts, origD, perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter, momentum,
+                             final_momentum, eta, exaggeration_factor)
+    list(N = n, Y = Y, costs = costs, itercosts = itercosts, origD = origD, perplexity = perplexity, theta = theta, max_iter = max_iter,
+         stop_lying_iter = stop_lying_iter, mom_switch_iter = mom_switch_iter, momentum = momentum, final_momentum = final_momentum,
+         eta = eta, exaggeration_factor = exaggeration_factor)
+# R's dist vector and its size from a dist object or a square matrix (which must equal its transpose exactly; the diagonal is ignored)
+.sharp_as_dist <- function(X) {
+    if (inherits(X, "dist")) return(list(d = as.double(X), n = attr(X, "Size")))
+    X <- .sharp_dmat(X)
+    if (nrow(X) != ncol(X) || nrow(X) < 2) stop("Rtsne: with is_distance = TRUE, X must be a dist object or a square matrix")
+    if (!identical(unname(X), unname(t(X)))) stop("Rtsne: the distance matrix is not symmetric (it must equal its transpose exactly)")
+    list(d = X[lower.tri(X)], n = nrow(X))
+}
 sharp_Rtsne <- function(X, dims = 2, initial_dims = 50, perplexity = 30, theta = 0.5, check_duplicates = TRUE, pca = TRUE,
                         partial_pca = FALSE, max_iter = 1000, verbose = getOption("verbose", FALSE), is_distance = FALSE, Y_init = NULL,
                         pca_center = TRUE, pca_scale = FALSE, normalize = TRUE,
                         stop_lying_iter = ifelse(is.null(Y_init), 250L, 0L), mom_switch_iter = ifelse(is.null(Y_init), 250L, 0L),
                         momentum = 0.5, final_momentum = 0.8, eta = 200, exaggeration_factor = 12, num_threads = 1, seed = 10,
                         repulsion = "exact", ...) {
-    entry <- switch(repulsion, exact = "sharp_C_tsne", barnes_hut = "sharp_C_tsne_bh",
-                    stop("sharp_Rtsne: repulsion must be \"exact\" or \"barnes_hut\""))
-    if (is_distance) stop("sharp_Rtsne: is_distance = TRUE is not supported")
+    rep_code <- .sharp_repulsion(repulsion, "sharp_Rtsne")
+    has_init <- !is.null(Y_init)
+    ncost <- .sharp_ncost(max_iter)
+    if (is_distance) {
+        dd <- .sharp_as_dist(X)
+        n <- dd$n
+        if (n > 46340) stop("Rtsne: more than 46340 objects (the dist vector would pass 2^30 entries) is not supported")
+        if (anyNA(dd$d) || any(!is.finite(dd$d)) || any(dd$d < 0)) stop("Rtsne: the distances hold NA / NaN / Inf or a negative value")
+        if (has_init && !all(dim(Y_init) == c(n, dims))) stop("Y_init must be an n x dims matrix")
+        if (is.loaded("R_sharp_tsne_dist")) {
+            r <- .Call("R_sharp_tsne_dist", dd$d, as.integer(n),
+                       as.integer(c(0L, rep_code, dims, max_iter, stop_lying_iter, mom_switch_iter)),
+                       as.double(c(perplexity, theta, momentum, final_momentum, eta, exaggeration_factor, seed)),
+                       if (has_init) .sharp_dmat(Y_init) else double(0))
+            Y <- r$Y; costs <- r$costs; ic <- r$itercosts
+        } else {
+            r <- .C("sharp_C_tsne_dist", dd$d, as.integer(n), rep_code, as.integer(dims), as.double(perplexity), as.double(theta),
+                    as.integer(max_iter), as.integer(stop_lying_iter), as.integer(mom_switch_iter), as.double(momentum),
+                    as.double(final_momentum), as.double(eta), as.double(exaggeration_factor), as.integer(has_init),
+                    if (has_init) as.double(t(Y_init)) else double(1), as.double(seed),
+                    Y = double(n * dims), itercosts = double(max(ncost, 1)), costs = double(n), status = integer(1))
+            .sharp_check(r$status)
+            Y <- matrix(r$Y, n, dims, byrow = TRUE); costs <- r$costs; ic <- r$itercosts[seq_len(ncost)]
+        }
+        return(.sharp_tsne_list(n, Y, costs, ic, NULL, perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter, momentum,
+                                final_momentum, eta, exaggeration_factor))
+    }
+    entry <- if (rep_code == 1L) "sharp_C_tsne_bh" else "sharp_C_tsne"
     X <- .sharp_dmat(X)
     n <- nrow(X); d <- ncol(X)
-    has_init <- !is.null(Y_init)
     if (has_init && !all(dim(Y_init) == c(n, dims))) stop("Y_init must be an n x dims matrix")
-    iters <- seq_len(max_iter) - 1L
-    ncost <- sum((iters > 0 & iters %% 50 == 0) | iters == max_iter - 1L)
     r <- .C(entry, as.double(t(X)), as.double(n), as.integer(d), as.integer(dims), as.integer(initial_dims), as.integer(pca),
             as.integer(pca_center), as.integer(pca_scale), as.integer(normalize), as.integer(check_duplicates), as.double(perplexity),
             as.double(theta), as.integer(max_iter), as.integer(stop_lying_iter), as.integer(mom_switch_iter), as.double(momentum),
@@ -303,10 +344,58 @@ sharp_Rtsne <- function(X, dims = 2, initial_dims = 50, perplexity = 30, theta =
             if (has_init) as.double(t(Y_init)) else double(1), as.double(seed),
             Y = double(n * dims), itercosts = double(max(ncost, 1)), costs = double(n), status = integer(1))
     .sharp_check(r$status)
-    list(N = n, Y = matrix(r$Y, n, dims, byrow = TRUE), costs = r$costs, itercosts = r$itercosts[seq_len(ncost)],
-         origD = if (pca) min(initial_dims, d) else d, perplexity = perplexity, theta = theta, max_iter = max_iter,
-         stop_lying_iter = stop_lying_iter, mom_switch_iter = mom_switch_iter, momentum = momentum, final_momentum = final_momentum,
-         eta = eta, exaggeration_factor = exaggeration_factor)
+    .sharp_tsne_list(n, matrix(r$Y, n, dims, byrow = TRUE), r$costs, r$itercosts[seq_len(ncost)], if (pca) min(initial_dims, d) else d,
+                     perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta, exaggeration_factor)
+}
+
+# Rtsne_neighbors(index, distance, ...): index an n x K integer matrix of 1-BASED neighbour indices, distance their n x K Euclidean
+# distances (squared = TRUE: already squared, as sharp_knn(X, K, squared = TRUE) returns them).  1 <= K <= 255, K <= n - 1,
+# perplexity <= K.  The library validates the lists on the GPU and uses every row in the caller's order (sharp_C_tsne_neighbors).
+sharp_Rtsne_neighbors <- function(index, distance, dims = 2, perplexity = 30, theta = 0.5, max_iter = 1000,
+                                  verbose = getOption("verbose", FALSE), Y_init = NULL,
+                                  stop_lying_iter = ifelse(is.null(Y_init), 250L, 0L), mom_switch_iter = ifelse(is.null(Y_init), 250L, 0L),
+                                  momentum = 0.5, final_momentum = 0.8, eta = 200, exaggeration_factor = 12, num_threads = 1, seed = 10,
+                                  repulsion = "exact", squared = FALSE, ...) {
+    rep_code <- .sharp_repulsion(repulsion, "sharp_Rtsne_neighbors")
+    distance <- .sharp_dmat(distance)
+    index <- as.matrix(index)
+    if (!all(dim(index) == dim(distance))) stop("Rtsne_neighbors: index and distance differ in shape")
+    storage.mode(index) <- "integer"
+    n <- nrow(distance); K <- ncol(distance)
+    has_init <- !is.null(Y_init)
+    if (has_init && !all(dim(Y_init) == c(n, dims))) stop("Y_init must be an n x dims matrix")
+    ncost <- .sharp_ncost(max_iter)
+    if (is.loaded("R_sharp_tsne_neighbors")) {
+        r <- .Call("R_sharp_tsne_neighbors", index, distance,
+                   as.integer(c(squared, rep_code, dims, max_iter, stop_lying_iter, mom_switch_iter)),
+                   as.double(c(perplexity, theta, momentum, final_momentum, eta, exaggeration_factor, seed)),
+                   if (has_init) .sharp_dmat(Y_init) else double(0))
+        Y <- r$Y; costs <- r$costs; ic <- r$itercosts
+    } else {
+        i0 <- as.integer(t(index)) - 1L
+        i0[is.na(i0)] <- -1L                                    # an NA index is out of range: the library names its row
+        r <- .C("sharp_C_tsne_neighbors", i0, as.double(t(distance)), as.double(n), as.integer(K), as.integer(squared), rep_code,
+                as.integer(dims), as.double(perplexity), as.double(theta), as.integer(max_iter), as.integer(stop_lying_iter),
+                as.integer(mom_switch_iter), as.double(momentum), as.double(final_momentum), as.double(eta),
+                as.double(exaggeration_factor), as.integer(has_init), if (has_init) as.double(t(Y_init)) else double(1),
+                as.double(seed), Y = double(n * dims), itercosts = double(max(ncost, 1)), costs = double(n), status = integer(1), NAOK = TRUE)
+        .sharp_check(r$status)
+        Y <- matrix(r$Y, n, dims, byrow = TRUE); costs <- r$costs; ic <- r$itercosts[seq_len(ncost)]
+    }
+    .sharp_tsne_list(n, Y, costs, ic, NULL, perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta,
+                     exaggeration_factor)
+}
+
+# the exact K nearest neighbours Rtsne itself computes: list(index = n x K, 1-based; distance = n x K Euclidean, or squared), each row
+# sorted by (distance, index), ties to the lower index.  Computed once, they serve every later sharp_Rtsne_neighbors call on the data.
+sharp_knn <- function(X, K, squared = FALSE) {
+    X <- .sharp_dmat(X)
+    n <- nrow(X)
+    r <- .C("sharp_C_tsne_knn", as.double(t(X)), as.double(n), ncol(X), as.integer(K), idx = integer(n * K), dist = double(n * K),
+            status = integer(1))
+    .sharp_check(r$status)
+    d2 <- matrix(r$dist, n, K, byrow = TRUE)
+    list(index = matrix(r$idx, n, K, byrow = TRUE) + 1L, distance = if (squared) d2 else sqrt(d2))
 }
 
 # ---- dist / hclust / plot_markers (R/plot_markers.R:38-242; DESIGN.md 11) ----------------------------------------------------------------

@@ -1012,30 +1012,83 @@ def _draw_sharp_map(Y, label, filename, filetype, legendtitle="Cell Type", width
     fig.savefig(filename, format=filetype, dpi=res, bbox_inches="tight")
 
 
+_PREPARE_ARGS = ("pca", "initial_dims", "pca_center", "pca_scale", "normalize")
+
+
 def visualization_SHARP(y, label=None, w=2, filename=None, filetype=None, n_cores=None, legendtitle="Cell Type", width=9.5, height=8.5,
-                        res=400, plot=True, **tsne_kwargs):
+                        res=400, plot=True, neighbors=None, return_neighbors=False, **tsne_kwargs):
     """R/visualization_SHARP.R:31-177: the 2-D t-SNE map of a SHARP() / SHARP_unlimited() result.
 
     x1 = cbind(w * scale(x0), scale(viE)) (w >= 100: x0 with jitter; w <= 0.01: viE alone) goes to Rtsne(x1, check_duplicates = FALSE,
     pca = ncol(x1) > 50, **tsne_kwargs) on the GPU (sharp_amd.tsne.Rtsne: exact repulsion, O(n^2) per iteration; repulsion="barnes_hut"
     in tsne_kwargs takes bhtsne's Barnes-Hut repulsion at Rtsne's theta = 0.5, O(n log n) per iteration).  The figure (pdf
     below 5000 cells, png otherwise; default name vi_SHARP.<type>) is drawn with matplotlib; plot=False skips it.  n_cores is accepted
-    and ignored.  Returns {"Y", "itercosts", "filename", "time"} (time in minutes, as R reports it)."""
+    and ignored.  Returns {"Y", "itercosts", "filename", "time"} (time in minutes, as R reports it).
+
+    return_neighbors=True runs the same stages one at a time (prepare, knn, Rtsne_neighbors: the same Y bit for bit) and adds
+    "neighbors": {"index", "distance", "squared": True, "w", "n"} to the result: the exact k-NN of the prepared x1, which depends on
+    neither seed, theta, dims, max_iter nor the optimiser's settings.  A later call for another map of the same result passes that dict
+    as neighbors= and skips the preparation and the k-NN, the only O(n^2 d) stage; its perplexity may be anything up to a third of the
+    lists' width (the lists are sorted, so their first floor(3 perplexity) columns are what Rtsne would compute).  A dict whose n or w
+    does not match the call is refused; the preparation's arguments (pca, initial_dims, ...) are then unused."""
     import time as _t
 
-    from .tsne import Rtsne
+    from .tsne import Rtsne, Rtsne_neighbors, _knn, _prepare
 
     t0 = _t.time()
-    x1 = _vis_input(y, w)
+    kw = dict(tsne_kwargs)
+    if neighbors is None:
+        x1 = _vis_input(y, w)
+        n = x1.shape[0]
+    else:
+        for key in ("index", "distance", "squared", "w", "n"):
+            if key not in neighbors:
+                raise SharpError(f"visualization_SHARP: neighbors holds no \"{key}\" (pass what return_neighbors=True returned)")
+        src = y.get("viE") if y.get("viE") is not None else y.get("x0")
+        if src is None:
+            raise SharpError("visualization_SHARP: the result holds no x0 / viE (run SHARP with forview = TRUE)")
+        n = src.shape[0]
+        if neighbors["n"] != n or np.asarray(neighbors["index"]).shape[0] != n:
+            raise SharpError(f"visualization_SHARP: neighbors were computed for {neighbors['n']} cells, this result holds {n}")
+        if neighbors["w"] != w:
+            raise SharpError(f"visualization_SHARP: neighbors were computed with w = {neighbors['w']}, this call has w = {w}")
     if filetype is None:
-        filetype = "pdf" if x1.shape[0] < 5000 else "png"
+        filetype = "pdf" if n < 5000 else "png"
     if filename is None:
         filename = f"vi_SHARP.{filetype}"
-    kw = dict(tsne_kwargs)
-    kw.setdefault("check_duplicates", False)
-    kw.setdefault("pca", x1.shape[1] > 50)
     kw.setdefault("seed", 10)                                         # set.seed(10), R/visualization_SHARP.R:85
-    out = Rtsne(x1, **kw)
+    nb = None
+    if neighbors is None and not return_neighbors:
+        kw.setdefault("check_duplicates", False)
+        kw.setdefault("pca", x1.shape[1] > 50)
+        out = Rtsne(x1, **kw)
+    else:
+        prep = {k: kw.pop(k) for k in _PREPARE_ARGS if k in kw}
+        dup = kw.pop("check_duplicates", False)
+        for k in ("partial_pca", "verbose", "is_distance"):
+            kw.pop(k, None)
+        K = int(np.floor(3 * kw.get("perplexity", 30)))
+        if neighbors is None:
+            if kw.get("perplexity", 30) > 85:
+                raise SharpError("Rtsne: perplexity above 85 is not supported (at most 255 neighbours per row)")
+            if n - 1 < 3 * kw.get("perplexity", 30):
+                raise SharpError("Perplexity is too large.")
+            prep.setdefault("pca", x1.shape[1] > 50)
+            idx, d2 = _knn(_prepare(x1, **prep), K)
+            nb = {"index": idx, "distance": d2, "squared": True, "w": w, "n": n}
+        else:
+            nb = neighbors
+            idx, d2 = np.asarray(nb["index"]), np.asarray(nb["distance"])
+            if idx.ndim != 2 or K > idx.shape[1] or K < 1:
+                raise SharpError(f"visualization_SHARP: perplexity {kw.get('perplexity', 30)} needs {K} neighbours per row, neighbors holds "
+                                 f"{idx.shape[1] if idx.ndim == 2 else 0}")
+            idx, d2 = idx[:, :K], d2[:, :K]
+        if dup and (d2[:, 0] == 0).any():
+            raise SharpError("Remove duplicates before running TSNE.")
+        out = Rtsne_neighbors(idx, d2, squared=bool(nb["squared"]), **kw)
     if plot:
         _draw_sharp_map(out["Y"], label, filename, filetype, legendtitle, width, height, res)
-    return {"Y": out["Y"], "itercosts": out["itercosts"], "filename": filename if plot else None, "time": (_t.time() - t0) / 60.0}
+    r = {"Y": out["Y"], "itercosts": out["itercosts"], "filename": filename if plot else None, "time": (_t.time() - t0) / 60.0}
+    if return_neighbors:
+        r["neighbors"] = nb
+    return r

@@ -190,6 +190,15 @@ void tree_from_full(const DevBuf<double> &D, int n, int hmethod, int *merge, dou
 
 }  // namespace
 
+int dist_nld(int n) { return rup128(n); }
+
+void dist_expand(const double *cond, int n, double *D) {
+    const int nld = rup128(n);
+    KernelTimer tm("dist_expand");
+    hipLaunchKernelGGL(dist_expand_kernel, dim3((nld + 255) / 256, nld), dim3(256), 0, ctx().stream, cond, n, nld, D);
+    launch_check("dist_expand_kernel");
+}
+
 }  // namespace sharp
 
 using namespace sharp;
@@ -217,7 +226,7 @@ int sharp_dist(const double *x, int n, int p, long long ld, int method, double m
 
 int sharp_hclust_dist(const double *d, int n, int hmethod, int *merge, double *height, int *order) {
     SHARP_API_BEGIN
-    Ctx &c = ctx();
+    ctx();
     SHARP_REQUIRE(d, "sharp_hclust_dist: null d");
     SHARP_REQUIRE(n >= 2, "sharp_hclust_dist: must have n >= 2 objects to cluster");
     SHARP_REQUIRE(n <= kHcMaxN, "sharp_hclust_dist: more than 16384 observations is not supported");
@@ -227,11 +236,7 @@ int sharp_hclust_dist(const double *d, int n, int hmethod, int *merge, double *h
     const int nld = rup128(n);
     DevBuf<double> cond(len), D(static_cast<size_t>(nld) * nld);
     cond.upload(d, len);
-    {
-        KernelTimer tm("dist_expand");
-        hipLaunchKernelGGL(dist_expand_kernel, dim3((nld + 255) / 256, nld), dim3(256), 0, c.stream, cond.p, n, nld, D.p);
-        launch_check("dist_expand_kernel");
-    }
+    dist_expand(cond.p, n, D.p);
     tree_from_full(D, n, hmethod, merge, height, order);
     SHARP_API_END
 }

@@ -32,4 +32,9 @@ __device__ __forceinline__ long long cond_index(int n, int j, int i) {
     return static_cast<long long>(n) * j - static_cast<long long>(j) * (j + 1) / 2 + (i - j - 1);
 }
 
+// dist.hip: R's dist vector (device, n (n - 1) / 2) -> the full symmetric matrix D (device, nld x nld with nld = dist_nld(n), n rounded
+// up to 128; the diagonal and the padding are 0), on the library's stream
+int dist_nld(int n);
+void dist_expand(const double *cond, int n, double *D);
+
 }  // namespace sharp

@@ -244,6 +244,26 @@ void sharp_C_tsne_bh(double *X, double *n, int *d, int *dims, int *initial_dims,
                             *exaggeration, *has_Y_init ? Y_init : nullptr, *seed, Y, itercosts, costs);
 }
 
+/* ---- Rtsne_neighbors / Rtsne(is_distance = TRUE) / the exact k-NN (sharp_tsne_neighbors, sharp_tsne_dist, sharp_tsne_knn): index
+ * 0-based, n x K row-major (as.integer(t(index)) - 1L); X = as.double(t(X)) */
+void sharp_C_tsne_neighbors(int *index, double *distance, double *n, int *K, int *squared, int *repulsion, int *dims, double *perplexity,
+                            double *theta, int *max_iter, int *stop_lying_iter, int *mom_switch_iter, double *momentum,
+                            double *final_momentum, double *eta, double *exaggeration, int *has_Y_init, double *Y_init, double *seed, double *Y,
+                            double *itercosts, double *costs, int *status) {
+    *status = sharp_tsne_neighbors(index, distance, as_ll(n), *K, *squared, *repulsion, *dims, *perplexity, *theta, *max_iter, *stop_lying_iter,
+                                   *mom_switch_iter, *momentum, *final_momentum, *eta, *exaggeration, *has_Y_init ? Y_init : nullptr, *seed, Y,
+                                   itercosts, costs);
+}
+void sharp_C_tsne_dist(double *d, int *n, int *repulsion, int *dims, double *perplexity, double *theta, int *max_iter, int *stop_lying_iter,
+                       int *mom_switch_iter, double *momentum, double *final_momentum, double *eta, double *exaggeration, int *has_Y_init,
+                       double *Y_init, double *seed, double *Y, double *itercosts, double *costs, int *status) {
+    *status = sharp_tsne_dist(d, *n, *repulsion, *dims, *perplexity, *theta, *max_iter, *stop_lying_iter, *mom_switch_iter, *momentum,
+                              *final_momentum, *eta, *exaggeration, *has_Y_init ? Y_init : nullptr, *seed, Y, itercosts, costs);
+}
+void sharp_C_tsne_knn(double *X, double *n, int *d, int *K, int *idx, double *dist, int *status) {
+    *status = sharp_tsne_knn(X, as_ll(n), *d, static_cast<long long>(*d), *K, idx, dist);
+}
+
 /* ---- dist / hclust (the clustering pheatmap does inside plot_markers, R/plot_markers.R:214-237): x = as.double(t(x)) */
 void sharp_C_dist(double *x, int *n, int *p, int *method, double *minkowski_p, double *d_out, int *status) {
     *status = sharp_dist(x, *n, *p, static_cast<long long>(*p), *method, *minkowski_p, d_out);

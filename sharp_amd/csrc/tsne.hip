@@ -4,6 +4,9 @@
 //                       by the largest |entry|
 //   exact k-NN          distances ||w_i||^2 + ||w_j||^2 - 2 w_i.w_j of the centred rows w = x - mean on v_mfma_f64_16x16x4_f64 over streamed
 //                       column tiles, a per-row top-K in LDS behind a threshold filter, the chosen K re-ranked by a direct sum (x_i - x_j)^2
+//   given distances     Rtsne(is_distance = TRUE): R's dist vector expanded to the full matrix (dist.hip), one wave per row selecting its K
+//                       smallest entries through the same LDS list; given neighbours (Rtsne_neighbors): a validation kernel, then
+//                       the caller's lists as they are
 //   calibration         one wave per row, fp64 bisection on beta (bhtsne's rule)
 //   symmetrisation      COO (i, j, p) + (j, i, p), radix sort by (row, col), duplicates merged, normalised by a fixed-order sum -> CSR
 //   optimiser loop      attraction over the CSR rows (fp64); exact repulsion, a workgroup owning 256 rows and streaming every y_j through
@@ -24,6 +27,7 @@
 #include <rocprim/device/device_reduce_by_key.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "dist_pairs.hpp"
 #include "linalg.hpp"
 #include "rrng.hpp"
 
@@ -444,6 +448,93 @@ __global__ __launch_bounds__(256) void norm_check_kernel(const double *__restric
 __global__ __launch_bounds__(256) void dup_flag_kernel(const double *__restrict__ dist, long long n, int K, int *__restrict__ flag) {
     const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
     if (i < n && dist[i * K] == 0.0) *flag = 1;   // every writer stores the same value
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// neighbours that are given, or selected from given distances (DESIGN.md §10 "Given neighbours, given distances")
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int NN_RS = 8;     // 64-wide loads in flight per lane before their offers (hclust_agglo.hip's HC_RS idea)
+constexpr unsigned long long NN_OK = ~0ull;
+enum NnKind { NN_RANGE = 1, NN_SELF = 2, NN_TWICE = 3, NN_DIST = 4 };
+
+// One wave per row r of the full symmetric matrix D (nld x nld, as dist_expand_kernel writes it): the K smallest (D[r][c], c) over
+// c < n, c != r, lexicographic (ties to the lower index), through knn_offer on an LDS list; then ranked by (distance, index) and written
+// as idx and dist2 = d * d.  Selection is on the distances as given.  A row left with a sentinel or a square that overflows sets *bad.
+__global__ __launch_bounds__(256) void knn_rows_kernel(const double *__restrict__ D, int n, int nld, int K, int *__restrict__ out_idx,
+                                                       double *__restrict__ out_dist2, int *__restrict__ bad) {
+    extern __shared__ double smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double *Ld = smem + wave * K;                                  // [4][K] doubles, then [4][K] ints
+    int *Li = reinterpret_cast<int *>(smem + 4 * K) + wave * K;
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= n) return;
+    for (int p = lane; p < K; p += 64) { Ld[p] = KNN_INF; Li[p] = INT_MAX; }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    double thr = KNN_INF;
+    int widx = INT_MAX, wpos = 0;
+    const double *row = D + static_cast<long long>(r) * nld;
+    for (int c0 = 0; c0 < n; c0 += 64 * NN_RS) {
+        double v[NN_RS];
+#pragma unroll
+        for (int u = 0; u < NN_RS; ++u) { const int c = c0 + 64 * u + lane; v[u] = c < n ? row[c] : KNN_INF; }
+#pragma unroll
+        for (int u = 0; u < NN_RS; ++u) {
+            const int c = c0 + 64 * u + lane;
+            if (c0 + 64 * u < n) knn_offer(v[u], c, c < n && c != r, Ld, Li, K, lane, thr, widx, wpos);   // (wave-uniform condition)
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int p = lane; p < K; p += 64) {
+        const double dp = Ld[p];
+        const int ip = Li[p];
+        int rank = 0;
+        for (int q = 0; q < K; ++q) rank += lex_less(Ld[q], Li[q], dp, ip) ? 1 : 0;
+        const double d2 = dp * dp;
+        if (ip >= n || !(d2 <= DBL_MAX)) { *bad = 1; continue; }   // every writer stores the same value
+        out_idx[static_cast<long long>(r) * K + rank] = ip;
+        out_dist2[static_cast<long long>(r) * K + rank] = d2;
+    }
+}
+
+// One wave per row of a caller's neighbour lists, before anything dereferences an index: every index in [0, n), none its own row, none
+// twice in a row, every distance finite and >= 0.  *word = min over the offending rows of (row << 3 | kind): the first offending row
+// and its lowest kind, whatever the scheduling.
+__global__ __launch_bounds__(256) void nn_check_kernel(const int *__restrict__ idx, const double *__restrict__ dist, long long n, int K,
+                                                       unsigned long long *__restrict__ word) {
+    extern __shared__ int sidx[];                                  // [4][K]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int *Li = sidx + wave * K;
+    const long long r = static_cast<long long>(blockIdx.x) * 4 + wave;
+    if (r >= n) return;
+    int kind = 8;
+    for (int p = lane; p < K; p += 64) {
+        const int j = idx[r * K + p];
+        const double d = dist[r * K + p];
+        Li[p] = j;
+        if (j < 0 || j >= n) kind = min(kind, static_cast<int>(NN_RANGE));
+        else if (j == r) kind = min(kind, static_cast<int>(NN_SELF));
+        if (!(d >= 0.0 && d <= DBL_MAX)) kind = min(kind, static_cast<int>(NN_DIST));   // (false for NaN too)
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int p = lane; p < K; p += 64) {
+        const int j = Li[p];
+        for (int q = 0; q < p; ++q)
+            if (Li[q] == j) { kind = min(kind, static_cast<int>(NN_TWICE)); break; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) kind = min(kind, __shfl_xor(kind, off));
+    if (lane == 0 && kind < 8) atomicMin(word, (static_cast<unsigned long long>(r) << 3) | static_cast<unsigned long long>(kind));
+}
+
+__global__ __launch_bounds__(256) void square_kernel(double *__restrict__ v, long long n, int *__restrict__ bad) {
+    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= n) return;
+    const double s = v[e] * v[e];
+    if (!(s <= DBL_MAX)) *bad = 1;   // every writer stores the same value
+    v[e] = s;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1360,6 +1451,73 @@ void tsne_affinities(const DevBuf<int> &idx, const DevBuf<double> &dist, long lo
     stream_sync();
 }
 
+void tsne_knn_dist(const double *d, int n, int K, DevBuf<int> &idx, DevBuf<double> &dist2) {
+    Ctx &c = ctx();
+    SHARP_REQUIRE(K >= 1 && K <= 255 && n - 1 >= K, "tsne_knn_dist: need 1 <= K <= 255 and K < n");
+    const size_t len = static_cast<size_t>(n) * (n - 1) / 2;
+    const int nld = dist_nld(n);
+    DevBuf<double> D(static_cast<size_t>(nld) * nld);
+    {
+        DevBuf<double> cond(len);
+        {
+            KernelTimer t("tsne_dist_upload");
+            cond.upload(d, len);
+        }
+        dist_expand(cond.p, n, D.p);
+        stream_sync();   // (the vector goes out of scope)
+    }
+    idx.alloc(static_cast<size_t>(n) * K);
+    dist2.alloc(static_cast<size_t>(n) * K);
+    DevBuf<int> bad(1);
+    bad.zero();
+    {
+        KernelTimer t("tsne_knn_dist");
+        hipLaunchKernelGGL(knn_rows_kernel, dim3(grid_for(n, 4)), dim3(256), (sizeof(double) + sizeof(int)) * 4 * K, c.stream, D.p, n, nld, K, idx.p,
+                           dist2.p, bad.p);
+        launch_check("knn_rows_kernel");
+    }
+    int hb = 0;
+    bad.download(&hb, 1);
+    SHARP_REQUIRE(hb == 0, "Rtsne: the distances are so large that their squares overflow");
+}
+
+void tsne_upload_neighbours(const int *index, const double *distance, long long n, int K, bool squared, DevBuf<int> &idx,
+                            DevBuf<double> &dist2) {
+    Ctx &c = ctx();
+    const size_t ne = static_cast<size_t>(n) * K;
+    idx.alloc(ne);
+    dist2.alloc(ne);
+    idx.upload(index, ne);
+    dist2.upload(distance, ne);
+    DevBuf<unsigned long long> word(1);
+    SHARP_HIP_CHECK(hipMemsetAsync(word.p, 0xFF, sizeof(unsigned long long), c.stream));
+    {
+        KernelTimer t("tsne_nn_check");
+        hipLaunchKernelGGL(nn_check_kernel, dim3(grid_for(n, 4)), dim3(256), sizeof(int) * 4 * K, c.stream, idx.p, dist2.p, n, K, word.p);
+        launch_check("nn_check_kernel");
+    }
+    unsigned long long w = NN_OK;
+    word.download(&w, 1);
+    if (w != NN_OK) {
+        const std::string row = " (row " + std::to_string(w >> 3) + ", counted from 0)";
+        switch (static_cast<int>(w & 7)) {
+            case NN_RANGE: throw Error(SHARP_ERR_ARG, "Rtsne_neighbors: a neighbour index outside [0, n)" + row);
+            case NN_SELF: throw Error(SHARP_ERR_ARG, "Rtsne_neighbors: a row names itself as a neighbour" + row);
+            case NN_TWICE: throw Error(SHARP_ERR_ARG, "Rtsne_neighbors: the same neighbour index twice in a row" + row);
+            default: throw Error(SHARP_ERR_ARG, "Rtsne_neighbors: a distance that is NA / NaN / Inf or negative" + row);
+        }
+    }
+    if (!squared) {
+        DevBuf<int> bad(1);
+        bad.zero();
+        hipLaunchKernelGGL(square_kernel, dim3(grid_for(n * K, 256)), dim3(256), 0, c.stream, dist2.p, n * K, bad.p);
+        launch_check("square_kernel");
+        int hb = 0;
+        bad.download(&hb, 1);
+        SHARP_REQUIRE(hb == 0, "Rtsne_neighbors: the distances are so large that their squares overflow");
+    }
+}
+
 void tsne_gradient(const TsneP &P, const double *dY_in, int dims, double *dGrad, double theta, double *Z) {
     Work w;
     w.init(P.n, dims, theta);
@@ -1395,33 +1553,17 @@ void check_X(const double *X, long long n, int d, long long ld) {
                                                       std::to_string(c + 1) + ")");
 }
 
-// Rtsne's body: bh_theta > 0 takes the Barnes-Hut repulsion with that theta, 0 the exact one
-void run_tsne(const double *X, long long n, int d, long long ld, int dims, int initial_dims, int pca, int pca_center, int pca_scale,
-              int normalize, int check_duplicates, double perplexity, double bh_theta, int max_iter, int stop_lying_iter, int mom_switch_iter,
-              double momentum, double final_momentum, double eta, double exaggeration, const double *Y_init, double seed, double *Y,
-              double *itercosts, double *costs) {
-    check_X(X, n, d, ld);
+void check_loop_args(int dims, int max_iter, double momentum, double final_momentum, double eta, double exaggeration, const double *Y) {
     check_dims(dims);
     SHARP_REQUIRE(Y, "sharp_tsne: null Y");
     SHARP_REQUIRE(max_iter >= 0 && std::isfinite(eta) && std::isfinite(momentum) && std::isfinite(final_momentum), "Rtsne: bad optimiser arguments");
     SHARP_REQUIRE(std::isfinite(exaggeration) && exaggeration > 0, "Rtsne: exaggeration_factor must be positive");
-    const int K = perplexity_K(perplexity);
-    SHARP_REQUIRE(static_cast<double>(n - 1) >= 3.0 * perplexity, "Perplexity is too large.");
-    DevBuf<double> Xp;
-    int dp = 0;
-    tsne_prepare(X, n, d, ld, pca != 0, initial_dims, pca_center != 0, pca_scale != 0, normalize != 0, Xp, &dp);
-    DevBuf<int> idx;
-    DevBuf<double> dist;
-    tsne_knn(Xp.p, n, dp, K, idx, dist);
-    if (check_duplicates) {
-        DevBuf<int> flag(1);
-        flag.zero();
-        hipLaunchKernelGGL(dup_flag_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx().stream, dist.p, n, K, flag.p);
-        int f = 0;
-        flag.download(&f, 1);
-        SHARP_REQUIRE(f == 0, "Remove duplicates before running TSNE.");
-    }
-    Xp.release();
+}
+
+// Everything behind the k-NN: P from the lists (idx, dist2: device, n x K, squared distances; released once P exists), the start, the
+// optimiser loop.  bh_theta > 0 takes the Barnes-Hut repulsion with that theta, 0 the exact one.
+void run_from_neighbours(DevBuf<int> &idx, DevBuf<double> &dist, long long n, int K, int dims, double perplexity, double bh_theta,
+                         const LoopArgs &la, const double *Y_init, double seed, double *Y, double *itercosts, double *costs) {
     TsneP P;
     tsne_affinities(idx, dist, n, K, perplexity, P);
     idx.release();
@@ -1447,13 +1589,41 @@ void run_tsne(const double *X, long long n, int d, long long ld, int dims, int i
         }
     }
     w.Y.upload(y0.data(), ne);
-    const LoopArgs la{max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta, exaggeration};
     std::vector<double> ic;
     if (dims == 1) optimise<1>(P, w, la, ic, costs);
     else if (dims == 2) optimise<2>(P, w, la, ic, costs);
     else optimise<3>(P, w, la, ic, costs);
     w.Y.download(Y, ne);
     if (itercosts) std::copy(ic.begin(), ic.end(), itercosts);
+}
+
+// Rtsne's body: prepare, exact k-NN, the duplicate check, then run_from_neighbours
+void run_tsne(const double *X, long long n, int d, long long ld, int dims, int initial_dims, int pca, int pca_center, int pca_scale,
+              int normalize, int check_duplicates, double perplexity, double bh_theta, int max_iter, int stop_lying_iter, int mom_switch_iter,
+              double momentum, double final_momentum, double eta, double exaggeration, const double *Y_init, double seed, double *Y,
+              double *itercosts, double *costs) {
+    check_X(X, n, d, ld);
+    check_loop_args(dims, max_iter, momentum, final_momentum, eta, exaggeration, Y);
+    const int K = perplexity_K(perplexity);
+    SHARP_REQUIRE(static_cast<double>(n - 1) >= 3.0 * perplexity, "Perplexity is too large.");
+    DevBuf<double> Xp;
+    int dp = 0;
+    tsne_prepare(X, n, d, ld, pca != 0, initial_dims, pca_center != 0, pca_scale != 0, normalize != 0, Xp, &dp);
+    DevBuf<int> idx;
+    DevBuf<double> dist;
+    tsne_knn(Xp.p, n, dp, K, idx, dist);
+    if (check_duplicates) {
+        DevBuf<int> flag(1);
+        flag.zero();
+        hipLaunchKernelGGL(dup_flag_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx().stream, dist.p, n, K, flag.p);
+        int f = 0;
+        flag.download(&f, 1);
+        SHARP_REQUIRE(f == 0, "Remove duplicates before running TSNE.");
+    }
+    Xp.release();
+    run_from_neighbours(idx, dist, n, K, dims, perplexity, bh_theta,
+                        LoopArgs{max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta, exaggeration}, Y_init, seed, Y,
+                        itercosts, costs);
 }
 
 // Rtsne's own check on theta, as far as it is known here
@@ -1532,6 +1702,107 @@ int sharp_tsne_affinities(const double *X, long long n, int d, long long ld, dou
     tsne_affinities(di, dd, n, K, perplexity, P);
     *nnz = P.nnz;
     SHARP_REQUIRE(cap >= P.nnz, "sharp_tsne_affinities: col / val hold fewer than nnz entries (2 n floor(3 perplexity) always suffice)");
+    P.row_ptr.download(row_ptr, static_cast<size_t>(n) + 1);
+    P.col.download(col, static_cast<size_t>(P.nnz));
+    P.val.download(val, static_cast<size_t>(P.nnz));
+    SHARP_API_END
+}
+
+}  // extern "C"
+
+namespace {
+// the arguments every entry on given neighbours checks before it touches the lists
+void check_neighbour_args(const int *index, const double *distance, long long n, int K, double perplexity, const char *who) {
+    const std::string w(who);
+    SHARP_REQUIRE(index && distance, w + ": null index / distance");
+    SHARP_REQUIRE(n >= 2 && n < INT_MAX, w + ": need 2 <= n < 2^31 rows");
+    SHARP_REQUIRE(K >= 1, w + ": need at least one neighbour per row (K >= 1)");
+    SHARP_REQUIRE(K <= 255, w + ": at most 255 neighbours per row");
+    SHARP_REQUIRE(K <= n - 1, w + ": K neighbours per row need K <= n - 1");
+    SHARP_REQUIRE(std::isfinite(perplexity) && perplexity > 0, "Rtsne: perplexity must be positive");
+    SHARP_REQUIRE(perplexity <= static_cast<double>(K), w + ": perplexity above K, the entropy of K neighbours cannot reach it");
+    SHARP_REQUIRE(static_cast<double>(n - 1) >= 3.0 * perplexity, "Perplexity is too large.");
+}
+
+// d: R's dist vector, every entry finite and >= 0, checked on the host before the upload
+void check_dist_vector(const double *d, int n, const char *who) {
+    const std::string w(who);
+    SHARP_REQUIRE(n <= SHARP_DIST_MAX_N, w + ": more than 46340 objects (the dist vector would pass 2^30 entries) is not supported");
+    SHARP_REQUIRE(n >= 2, w + ": need n >= 2 objects");
+    SHARP_REQUIRE(d, w + ": null d");
+    const size_t len = static_cast<size_t>(n) * (n - 1) / 2;
+    for (size_t e = 0; e < len; ++e)
+        SHARP_REQUIRE(d[e] >= 0.0 && d[e] <= DBL_MAX, w + ": d holds NA / NaN / Inf or a negative distance");   // (false for NaN too)
+}
+}  // namespace
+
+extern "C" {
+
+int sharp_tsne_neighbors(const int *index, const double *distance, long long n, int K, int squared, int repulsion, int dims, double perplexity,
+                         double theta, int max_iter, int stop_lying_iter, int mom_switch_iter, double momentum, double final_momentum, double eta,
+                         double exaggeration, const double *Y_init, double seed, double *Y, double *itercosts, double *costs) {
+    SHARP_API_BEGIN
+    ctx();
+    SHARP_REQUIRE(repulsion == 0 || repulsion == 1, "sharp_tsne_neighbors: repulsion must be 0 (exact) or 1 (Barnes-Hut)");
+    if (repulsion) check_bh_theta(theta);
+    check_neighbour_args(index, distance, n, K, perplexity, "sharp_tsne_neighbors");
+    check_loop_args(dims, max_iter, momentum, final_momentum, eta, exaggeration, Y);
+    DevBuf<int> idx;
+    DevBuf<double> dist;
+    tsne_upload_neighbours(index, distance, n, K, squared != 0, idx, dist);
+    run_from_neighbours(idx, dist, n, K, dims, perplexity, repulsion ? theta : 0.0,
+                        LoopArgs{max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta, exaggeration}, Y_init, seed, Y,
+                        itercosts, costs);
+    SHARP_API_END
+}
+
+int sharp_tsne_dist(const double *d, int n, int repulsion, int dims, double perplexity, double theta, int max_iter, int stop_lying_iter,
+                    int mom_switch_iter, double momentum, double final_momentum, double eta, double exaggeration, const double *Y_init,
+                    double seed, double *Y, double *itercosts, double *costs) {
+    SHARP_API_BEGIN
+    ctx();
+    SHARP_REQUIRE(n <= SHARP_DIST_MAX_N, "sharp_tsne_dist: more than 46340 objects (the dist vector would pass 2^30 entries) is not supported");
+    SHARP_REQUIRE(repulsion == 0 || repulsion == 1, "sharp_tsne_dist: repulsion must be 0 (exact) or 1 (Barnes-Hut)");
+    if (repulsion) check_bh_theta(theta);
+    check_loop_args(dims, max_iter, momentum, final_momentum, eta, exaggeration, Y);
+    const int K = perplexity_K(perplexity);
+    SHARP_REQUIRE(static_cast<double>(n - 1) >= 3.0 * perplexity, "Perplexity is too large.");
+    check_dist_vector(d, n, "sharp_tsne_dist");
+    DevBuf<int> idx;
+    DevBuf<double> dist;
+    tsne_knn_dist(d, n, K, idx, dist);
+    run_from_neighbours(idx, dist, n, K, dims, perplexity, repulsion ? theta : 0.0,
+                        LoopArgs{max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta, exaggeration}, Y_init, seed, Y,
+                        itercosts, costs);
+    SHARP_API_END
+}
+
+int sharp_tsne_knn_dist(const double *d, int n, int K, int *idx, double *dist2) {
+    SHARP_API_BEGIN
+    ctx();
+    check_dist_vector(d, n, "sharp_tsne_knn_dist");
+    SHARP_REQUIRE(idx && dist2, "sharp_tsne_knn_dist: null output");
+    DevBuf<int> di;
+    DevBuf<double> dd;
+    tsne_knn_dist(d, n, K, di, dd);
+    di.download(idx, static_cast<size_t>(n) * K);
+    dd.download(dist2, static_cast<size_t>(n) * K);
+    SHARP_API_END
+}
+
+int sharp_tsne_affinities_nn(const int *index, const double *distance, long long n, int K, int squared, double perplexity, long long cap,
+                             long long *row_ptr, int *col, double *val, long long *nnz) {
+    SHARP_API_BEGIN
+    ctx();
+    check_neighbour_args(index, distance, n, K, perplexity, "sharp_tsne_affinities_nn");
+    SHARP_REQUIRE(row_ptr && col && val && nnz, "sharp_tsne_affinities_nn: null output");
+    DevBuf<int> di;
+    DevBuf<double> dd;
+    tsne_upload_neighbours(index, distance, n, K, squared != 0, di, dd);
+    TsneP P;
+    tsne_affinities(di, dd, n, K, perplexity, P);
+    *nnz = P.nnz;
+    SHARP_REQUIRE(cap >= P.nnz, "sharp_tsne_affinities_nn: col / val hold fewer than nnz entries (2 n K always suffice)");
     P.row_ptr.download(row_ptr, static_cast<size_t>(n) + 1);
     P.col.download(col, static_cast<size_t>(P.nnz));
     P.val.download(val, static_cast<size_t>(P.nnz));

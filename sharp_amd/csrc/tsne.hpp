@@ -23,6 +23,15 @@ void tsne_prepare(const double *X, long long n, int d, long long ld, bool pca, i
 void tsne_knn(const double *dX, long long n, int d, int K, DevBuf<int> &idx, DevBuf<double> &dist);
 // calibration + symmetrisation: P from the k-NN lists
 void tsne_affinities(const DevBuf<int> &idx, const DevBuf<double> &dist, long long n, int K, double perplexity, TsneP &P);
+// the K nearest neighbours of every object from R's dist vector d (host, n (n - 1) / 2 entries, finite and >= 0; n <= SHARP_DIST_MAX_N):
+// selected on the distances as given (exact comparisons, ties by the lower index, self excluded), sorted by (distance, index);
+// dist2 = d * d.  The vector and the full matrix are released before it returns.
+void tsne_knn_dist(const double *d, int n, int K, DevBuf<int> &idx, DevBuf<double> &dist2);
+// a caller's neighbour lists (host, n x K; index 0-based) on the device, validated by a kernel before anything dereferences an index
+// (range, self, an index twice in a row, distances finite and >= 0: an Error naming the first offending row); squared == 0: the
+// distances are squared on the device.  The lists keep the caller's order.
+void tsne_upload_neighbours(const int *index, const double *distance, long long n, int K, bool squared, DevBuf<int> &idx,
+                            DevBuf<double> &dist2);
 // dY = sum_j P_ij q_ij (y_i - y_j) - (1/Z) sum_j q_ij^2 (y_i - y_j) at Y (device, n x dims); theta > 0: the repulsion and Z by
 // Barnes-Hut at that theta; Z (host, may be null) receives Z
 void tsne_gradient(const TsneP &P, const double *dY_in, int dims, double *dGrad, double theta = 0.0, double *Z = nullptr);

@@ -2,19 +2,27 @@
 
 Rtsne's interface and defaults, bhtsne's algorithm, computed by libsharp_hip.so (sharp_tsne):
 PCA / normalisation, exact k-NN, per-row perplexity calibration and the optimiser loop all run as HIP kernels.
+Rtsne's two other ways in are here too: Rtsne(d, is_distance=True) on a dist vector or a square matrix (sharp_tsne_dist) and
+Rtsne_neighbors(index, distance) on neighbour lists the caller already has (sharp_tsne_neighbors), with knn() to compute such lists
+once and reuse them for every later map of the same data.
 There is no CPU path: without a device every call raises SharpError."""
 import ctypes as C
+import math
 
 import numpy as np
 
 from . import _lib
 from ._lib import check, lib
 
-__all__ = ["Rtsne"]
+__all__ = ["Rtsne", "Rtsne_neighbors", "knn"]
 
 
 def _dp(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
 
 
 def _rows(X):
@@ -36,6 +44,52 @@ def _check_repulsion(repulsion):
         raise _lib.SharpError(f"Rtsne: repulsion must be one of {_REPULSIONS}, not {repulsion!r}")
 
 
+def _condensed(X, who):
+    """R's dist vector (n (n - 1) / 2 doubles) and n from a dist vector or a square matrix; a matrix must equal its transpose exactly
+    and is condensed on the host, its diagonal ignored.  Entries must be finite and >= 0.  No device is touched."""
+    a = np.asarray(X, dtype=np.float64)
+    if a.ndim == 1:
+        n = (1 + math.isqrt(1 + 8 * a.size)) // 2
+        if n < 2 or n * (n - 1) // 2 != a.size:
+            raise _lib.SharpError(f"{who}: a dist vector holds n (n - 1) / 2 entries; {a.size} is no such length")
+        d = np.ascontiguousarray(a)
+    elif a.ndim == 2 and a.shape[0] == a.shape[1] and a.shape[0] >= 2:
+        n = a.shape[0]
+        if not np.array_equal(a, a.T, equal_nan=True):
+            raise _lib.SharpError(f"{who}: the distance matrix is not symmetric (it must equal its transpose exactly)")
+        d = np.concatenate([a[i, i + 1:] for i in range(n)])          # row-wise upper triangle = column-wise lower triangle
+    else:
+        raise _lib.SharpError(f"{who}: with is_distance, X must be a dist vector or a square matrix")
+    if not (d >= 0).all() or not np.isfinite(d).all():                # (NaN fails the first test)
+        raise _lib.SharpError(f"{who}: the distances hold NA / NaN / Inf or a negative value")
+    if n > 46340:
+        raise _lib.SharpError(f"{who}: more than 46340 objects (the dist vector would pass 2^30 entries) is not supported")
+    return d, n
+
+
+def _loop_args(n, dims, Y_init, stop_lying_iter, mom_switch_iter, who):
+    dims = int(dims)
+    if dims not in (1, 2, 3):
+        raise _lib.SharpError(f"{who}: dims must be 1, 2 or 3")
+    if Y_init is not None:
+        Y_init = np.ascontiguousarray(Y_init, dtype=np.float64)
+        if Y_init.shape != (n, dims):
+            raise _lib.SharpError(f"{who}: Y_init must be an n x dims matrix")
+    if stop_lying_iter is None:
+        stop_lying_iter = 0 if Y_init is not None else 250
+    if mom_switch_iter is None:
+        mom_switch_iter = 0 if Y_init is not None else 250
+    return dims, Y_init, int(stop_lying_iter), int(mom_switch_iter)
+
+
+def _result(Y, ic, costs, n, origD, perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta,
+            exaggeration_factor, pca, normalize):
+    return {"Y": Y, "itercosts": ic[: _n_itercosts(int(max_iter))], "costs": costs, "N": n, "origD": origD, "perplexity": perplexity,
+            "theta": theta, "max_iter": int(max_iter), "stop_lying_iter": int(stop_lying_iter), "mom_switch_iter": int(mom_switch_iter),
+            "momentum": momentum, "final_momentum": final_momentum, "eta": eta, "exaggeration_factor": exaggeration_factor,
+            "pca": bool(pca), "normalize": bool(normalize)}
+
+
 def Rtsne(X, dims=2, initial_dims=50, perplexity=30, theta=0.5, check_duplicates=True, pca=True, partial_pca=False, max_iter=1000,
           verbose=False, is_distance=False, Y_init=None, pca_center=True, pca_scale=False, normalize=True, stop_lying_iter=None,
           mom_switch_iter=None, momentum=0.5, final_momentum=0.8, eta=200.0, exaggeration_factor=12.0, num_threads=1, seed=10,
@@ -51,24 +105,29 @@ def Rtsne(X, dims=2, initial_dims=50, perplexity=30, theta=0.5, check_duplicates
     iteration, O(n log n) work per iteration (DESIGN.md §10 "Barnes-Hut"; README has the measured times).
     Either way the input similarities come from the floor(3 perplexity) exact nearest neighbours (perplexity <= 85), an exact k-NN of
     O(n^2 d).  Without Y_init the start is 1e-4 N(0, 1) drawn from R's set.seed(seed) stream (polar method); two calls with the same
-    input and seed give bitwise-identical Y on the same GPU.  num_threads, verbose and partial_pca are accepted and ignored;
-    is_distance is not supported."""
+    input and seed give bitwise-identical Y on the same GPU.  num_threads, verbose and partial_pca are accepted and ignored.
+
+    is_distance=True: X is a dist vector of length n (n - 1) / 2 (what sharp_amd.dist returns) or an n x n matrix, n <= 46340.  A matrix
+    must equal its transpose exactly; its diagonal is ignored.  Every distance must be finite and >= 0.  The floor(3 perplexity)
+    nearest objects of each are selected on the distances as given (ties to the lower index) and P is built from their squares.
+    pca, initial_dims, normalize and check_duplicates are ignored for a distance input, and origD is None."""
     _check_repulsion(repulsion)
     if is_distance:
-        raise _lib.SharpError("Rtsne: is_distance = TRUE is not supported")
+        d, n = _condensed(X, "Rtsne")
+        dims, Y_init, stop_lying_iter, mom_switch_iter = _loop_args(n, dims, Y_init, stop_lying_iter, mom_switch_iter, "Rtsne")
+        _lib.ensure_init()
+        Y = np.zeros((n, dims))
+        ic = np.zeros(max(1, _n_itercosts(int(max_iter))))
+        costs = np.zeros(n)
+        check(lib().sharp_tsne_dist(_dp(d), int(n), int(repulsion == "barnes_hut"), dims, C.c_double(perplexity), C.c_double(theta),
+                                    int(max_iter), stop_lying_iter, mom_switch_iter, C.c_double(momentum), C.c_double(final_momentum),
+                                    C.c_double(eta), C.c_double(exaggeration_factor), _dp(Y_init), C.c_double(seed), _dp(Y), _dp(ic),
+                                    _dp(costs)))
+        return _result(Y, ic, costs, n, None, perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta,
+                       exaggeration_factor, False, False)
     X = _rows(X)
     n, d = X.shape
-    dims = int(dims)
-    if dims not in (1, 2, 3):
-        raise _lib.SharpError("Rtsne: dims must be 1, 2 or 3")
-    if Y_init is not None:
-        Y_init = np.ascontiguousarray(Y_init, dtype=np.float64)
-        if Y_init.shape != (n, dims):
-            raise _lib.SharpError("Rtsne: Y_init must be an n x dims matrix")
-    if stop_lying_iter is None:
-        stop_lying_iter = 0 if Y_init is not None else 250
-    if mom_switch_iter is None:
-        mom_switch_iter = 0 if Y_init is not None else 250
+    dims, Y_init, stop_lying_iter, mom_switch_iter = _loop_args(n, dims, Y_init, stop_lying_iter, mom_switch_iter, "Rtsne")
     _lib.ensure_init()
     Y = np.zeros((n, dims))
     ic = np.zeros(max(1, _n_itercosts(int(max_iter))))
@@ -78,11 +137,89 @@ def Rtsne(X, dims=2, initial_dims=50, perplexity=30, theta=0.5, check_duplicates
                            int(bool(pca_scale)), int(bool(normalize)), int(bool(check_duplicates)), C.c_double(perplexity), C.c_double(theta),
                            int(max_iter), int(stop_lying_iter), int(mom_switch_iter), C.c_double(momentum), C.c_double(final_momentum),
                            C.c_double(eta), C.c_double(exaggeration_factor), _dp(Y_init), C.c_double(seed), _dp(Y), _dp(ic), _dp(costs)))
-    return {"Y": Y, "itercosts": ic[: _n_itercosts(int(max_iter))], "costs": costs, "N": n,
-            "origD": min(int(initial_dims), d) if pca else d, "perplexity": perplexity, "theta": theta, "max_iter": int(max_iter),
-            "stop_lying_iter": int(stop_lying_iter), "mom_switch_iter": int(mom_switch_iter), "momentum": momentum,
-            "final_momentum": final_momentum, "eta": eta, "exaggeration_factor": exaggeration_factor, "pca": bool(pca),
-            "normalize": bool(normalize)}
+    return _result(Y, ic, costs, n, min(int(initial_dims), d) if pca else d, perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter,
+                   momentum, final_momentum, eta, exaggeration_factor, pca, normalize)
+
+
+def _neighbour_arrays(index, distance, who):
+    """(index int32, distance float64), both n x K and C-contiguous; refusals that need no device"""
+    index = np.asarray(index)
+    distance = np.asarray(distance)
+    if index.ndim != 2 or distance.ndim != 2:
+        raise _lib.SharpError(f"{who}: index and distance must be n x K matrices")
+    if index.shape != distance.shape:
+        raise _lib.SharpError(f"{who}: index {index.shape} and distance {distance.shape} differ in shape")
+    if not np.issubdtype(index.dtype, np.integer):
+        raise _lib.SharpError(f"{who}: index must hold integers, not {index.dtype}")
+    if not (np.issubdtype(distance.dtype, np.floating) or np.issubdtype(distance.dtype, np.integer)):
+        raise _lib.SharpError(f"{who}: distance must hold real numbers, not {distance.dtype}")
+    n, K = index.shape
+    if n < 2:
+        raise _lib.SharpError(f"{who}: need at least 2 rows")
+    if K < 1:
+        raise _lib.SharpError(f"{who}: need at least one neighbour per row (K >= 1)")
+    if K > 255:
+        raise _lib.SharpError(f"{who}: at most 255 neighbours per row")
+    if K > n - 1:
+        raise _lib.SharpError(f"{who}: K neighbours per row need K <= n - 1")
+    if index.dtype != np.int32:
+        # an index that int32 cannot hold is out of range whatever n is: keep it so (the library names its row)
+        index = np.where((index < -1) | (index > 2 ** 31 - 1), -1, index)
+    return np.ascontiguousarray(index, np.int32), np.ascontiguousarray(distance, np.float64)
+
+
+def Rtsne_neighbors(index, distance, dims=2, perplexity=30, theta=0.5, max_iter=1000, Y_init=None, stop_lying_iter=None,
+                    mom_switch_iter=None, momentum=0.5, final_momentum=0.8, eta=200.0, exaggeration_factor=12.0, num_threads=1, seed=10,
+                    repulsion="exact", squared=False):
+    """Rtsne_neighbors(index, distance, ...): the map from neighbour lists the caller already has.  index (n x K, integers, 0-based)
+    names each row's K neighbours and distance (n x K) their Euclidean distances, or their squares with squared=True -- what
+    knn(X, K, squared=True) returns.  1 <= K <= 255, K <= n - 1, perplexity <= K (the entropy of K neighbours cannot pass log K) and
+    n - 1 >= 3 perplexity.  The lists are validated on the GPU before use (every index in [0, n), no row naming itself, no index twice
+    in a row, distances finite and >= 0) and used in the caller's order: knn()'s lists give the bits of
+    Rtsne(X, pca=False, normalize=False, check_duplicates=False).  Everything else is Rtsne's; origD is None."""
+    who = "Rtsne_neighbors"
+    _check_repulsion(repulsion)
+    index, distance = _neighbour_arrays(index, distance, who)
+    n, K = index.shape
+    dims, Y_init, stop_lying_iter, mom_switch_iter = _loop_args(n, dims, Y_init, stop_lying_iter, mom_switch_iter, who)
+    _lib.ensure_init()
+    Y = np.zeros((n, dims))
+    ic = np.zeros(max(1, _n_itercosts(int(max_iter))))
+    costs = np.zeros(n)
+    check(lib().sharp_tsne_neighbors(_ip(index), _dp(distance), C.c_longlong(n), int(K), int(bool(squared)), int(repulsion == "barnes_hut"),
+                                     dims, C.c_double(perplexity), C.c_double(theta), int(max_iter), stop_lying_iter, mom_switch_iter,
+                                     C.c_double(momentum), C.c_double(final_momentum), C.c_double(eta), C.c_double(exaggeration_factor),
+                                     _dp(Y_init), C.c_double(seed), _dp(Y), _dp(ic), _dp(costs)))
+    return _result(Y, ic, costs, n, None, perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta,
+                   exaggeration_factor, False, False)
+
+
+def knn(X, K, squared=False, is_distance=False):
+    """The K exact nearest neighbours of every row: (index (n, K) int32, 0-based; distance (n, K)), self excluded, ties to the lower
+    index, each row sorted by (distance, index).  From the rows of X (the k-NN Rtsne itself runs; Euclidean distances, or their squares
+    sum (x_i - x_j)^2 with squared=True), or with is_distance=True from a dist vector or a square matrix as Rtsne(is_distance=True)
+    takes it: then the selection is on the distances as given, and they are returned as given (squared=True: their squares).
+    1 <= K <= 255, K <= n - 1.  The lists suit every perplexity <= K / 3 of Rtsne_neighbors."""
+    K = int(K)
+    if is_distance:
+        d, n = _condensed(X, "knn")
+        if not 1 <= K <= min(255, n - 1):
+            raise _lib.SharpError("knn: need 1 <= K <= 255 and K <= n - 1")
+        _lib.ensure_init()
+        idx = np.zeros((n, K), np.int32)
+        d2 = np.zeros((n, K))
+        check(lib().sharp_tsne_knn_dist(_dp(d), int(n), K, _ip(idx), _dp(d2)))
+        if squared:
+            return idx, d2
+        # the distances as given, not a root of their squares: entry (i, j) of the dist vector (i < j) sits at n i - i (i + 1) / 2 + j - i - 1
+        i = np.minimum(np.arange(n, dtype=np.int64)[:, None], idx)
+        j = np.maximum(np.arange(n, dtype=np.int64)[:, None], idx)
+        return idx, d[n * i - i * (i + 1) // 2 + j - i - 1]
+    X = _rows(X)
+    if not 1 <= K <= min(255, X.shape[0] - 1):
+        raise _lib.SharpError("knn: need 1 <= K <= 255 and K <= n - 1")
+    idx, d2 = _knn(X, K)
+    return (idx, d2) if squared else (idx, np.sqrt(d2))
 
 
 # ---- the stages one at a time (tests, tools/bench_tsne.py) ----------------------------------------------------------------------------
@@ -105,6 +242,21 @@ def _knn(X, K):
     dist = np.zeros((n, K))
     check(lib().sharp_tsne_knn(_dp(X), C.c_longlong(n), d, C.c_longlong(d), int(K), idx.ctypes.data_as(C.POINTER(C.c_int)), _dp(dist)))
     return idx, dist
+
+
+def _affinities_nn(index, distance, perplexity, squared=False):
+    """P (CSR: row_ptr, col, val) from given neighbour lists (sharp_tsne_affinities_nn)"""
+    index, distance = _neighbour_arrays(index, distance, "affinities")
+    n, K = index.shape
+    _lib.ensure_init()
+    cap = 2 * n * K
+    rp = np.zeros(n + 1, np.int64)
+    col = np.zeros(cap, np.int32)
+    val = np.zeros(cap)
+    nnz = C.c_longlong()
+    check(lib().sharp_tsne_affinities_nn(_ip(index), _dp(distance), C.c_longlong(n), int(K), int(bool(squared)), C.c_double(perplexity),
+                                         C.c_longlong(cap), rp.ctypes.data_as(C.POINTER(C.c_longlong)), _ip(col), _dp(val), C.byref(nnz)))
+    return rp, col[: nnz.value].copy(), val[: nnz.value].copy()
 
 
 def _affinities(X, perplexity):
