@@ -6,6 +6,10 @@ through a CPU path)."""
 import ctypes as C
 import os
 
+import numpy as np
+
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libsharp_hip.so")
 _lib = None
@@ -31,9 +35,44 @@ def lib():
             import torch  # noqa: F401
         except Exception:
             pass
-        _lib = C.CDLL(_SO)
-        _lib.sharp_last_error.restype = C.c_char_p
+        so = C.CDLL(_SO)
+        for name, sig in _abi.SIGNATURES.items():
+            ret, args = sig.split(":")
+            try:
+                fn = getattr(so, name)
+            except AttributeError:                          # (here, not at the first use of that entry)
+                raise SharpError(f"{_SO} does not export {name}, which sharp_amd/_abi.py lists: rebuild the library") from None
+            fn.restype = _abi.RETURN[ret]
+            fn.argtypes = [_abi.ARGUMENT[a] for a in args]
+        _lib = so
     return _lib
+
+
+def ptr(a, dtype):
+    """The address of a numpy array for a pointer argument (None: NULL), after checking that it is what the library will read or write
+    there: exactly `dtype`, and one contiguous block."""
+    if a is None:
+        return None
+    if not (isinstance(a, np.ndarray) and a.dtype == dtype and (a.flags.c_contiguous or a.flags.f_contiguous)):
+        got = type(a).__name__ if not isinstance(a, np.ndarray) else f"{a.dtype}" if a.dtype != dtype else "a non-contiguous view"
+        raise TypeError(f"expected a contiguous numpy array of {np.dtype(dtype).name}, got {got}")
+    return a.ctypes.data
+
+
+def f64(a):
+    return ptr(a, np.float64)
+
+
+def i32(a):
+    return ptr(a, np.int32)
+
+
+def i64(a):
+    return ptr(a, np.int64)
+
+
+def i8(a):
+    return ptr(a, np.int8)
 
 
 def check(rc, allow=0):

@@ -9,20 +9,12 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import SharpError, check, lib
+from ._lib import SharpError, check, f64, i8, i32, i64, lib
 
 __all__ = ["ranM", "ranM2", "RPmat", "Projector", "SharpError", "get_opt_hclust", "getrowColor", "colorL", "HMETHODS",
            "wMetaC", "sMetaC", "SHARP", "SHARP_small", "SHARP_large", "SHARP_unlimited", "SHARP_unlimited2", "SHARP_unlimited3", "run_Mtimes_SHARP", "get_marker_genes", "get_marker_genes_unlimited",
            "get_marker_genes_unlimited2", "testlog", "ARI", "decision_log", "last_decisions", "decision_margins", "DECISION_FIELDS",
            "visualization_SHARP", "vis_colors"]
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _ip(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
 
 
 class Projector:
@@ -32,7 +24,7 @@ class Projector:
         _lib.ensure_init()
         seeds = np.ascontiguousarray(np.atleast_1d(seeds), np.float64)
         h = C.c_int()
-        check(lib().sharp_projector_create(int(m), int(p), int(seeds.size), _dp(seeds), C.byref(h)))
+        check(lib().sharp_projector_create(int(m), int(p), int(seeds.size), f64(seeds), C.byref(h)))
         self.handle = h.value
         self.m, self.p, self.K = int(m), int(p), int(seeds.size)
         self.value = float(np.sqrt(np.sqrt(m)))
@@ -60,8 +52,7 @@ class Projector:
         g = np.empty(nn.value, np.int32)
         c = np.empty(nn.value, np.int32)
         s = np.empty(nn.value, np.int8)
-        check(lib().sharp_projector_triplets(self.handle, int(k), _ip(g), _ip(c), s.ctypes.data_as(C.POINTER(C.c_byte)),
-                                             C.byref(nn)))
+        check(lib().sharp_projector_triplets(self.handle, int(k), i32(g), i32(c), i8(s), C.byref(nn)))
         return g, c, s
 
     def dense(self, k=0):
@@ -76,7 +67,7 @@ class Projector:
         X = np.asfortranarray(X, dtype=np.float64)
         m, n = X.shape
         E = np.empty((n, self.K * self.p), np.float64)
-        check(lib().sharp_project(self.handle, _dp(X), m, n, C.c_longlong(m), int(bool(logflag)), _dp(E)))
+        check(lib().sharp_project(self.handle, f64(X), m, n, m, int(bool(logflag)), f64(E)))
         return E
 
 
@@ -162,9 +153,8 @@ def get_opt_hclust(mat, hmethod=None, N_cluster=None, minN_cluster=None, maxN_cl
     optN = C.c_int()
     nko = C.c_int()
     br = C.c_int()
-    rc = check(lib().sharp_get_opt_hclust(_dp(a), n, p, _hmethod(hmethod, flashmark), Ncl, minN, maxN, C.c_double(sil),
-                                          C.c_double(hN), _ip(f), _ip(v), _dp(msil), _dp(ch), C.byref(maxsil),
-                                          _dp(height), C.byref(optN), C.byref(nko), C.byref(br)), allow=16)
+    rc = check(lib().sharp_get_opt_hclust(f64(a), n, p, _hmethod(hmethod, flashmark), Ncl, minN, maxN, sil, hN, i32(f), i32(v), f64(msil),
+                                          f64(ch), C.byref(maxsil), f64(height), C.byref(optN), C.byref(nko), C.byref(br)), allow=16)
     k = nko.value
     return {"f": f, "v": v[: n * k].reshape(k, n).T.copy(), "maxsil": maxsil.value, "msil": msil[:k], "CHind": ch[:k],
             "height": height[: n - 1], "optN_cluster": optN.value, "branch": br.value, "warn": rc}
@@ -178,10 +168,9 @@ def getrowColor(Emat, hmethod=None, indN_cluster=None, minN_cluster=2, maxN_clus
     n, p = a.shape
     rc_ = np.zeros(n, np.int32)
     maxsil = C.c_double()
-    check(lib().sharp_getrowColor(_dp(a), n, p, _hmethod(hmethod, flashmark), int(indN_cluster or 0), int(minN_cluster),
-                                  int(maxN_cluster), C.c_double(sil_thre),
-                                  C.c_double(1.0 if height_Ntimes is None else height_Ntimes), _ip(rc_), C.byref(maxsil)),
-          allow=16)
+    check(lib().sharp_getrowColor(f64(a), n, p, _hmethod(hmethod, flashmark), int(indN_cluster or 0), int(minN_cluster),
+                                  int(maxN_cluster), sil_thre, 1.0 if height_Ntimes is None else height_Ntimes, i32(rc_),
+                                  C.byref(maxsil)), allow=16)
     return {"rowColor": [colorL[j - 1] for j in rc_], "rowColor_id": rc_, "maxsil": maxsil.value, "mat": Emat}
 
 
@@ -213,10 +202,10 @@ def wMetaC(nC, hmethod=None, enN_cluster=None, minN_cluster=None, maxN_cluster=N
     cap = N * Cc if N * Cc < 4096 else 4096
     S = np.zeros(cap * cap) if debug else None
     tf = np.zeros(cap, np.int32) if debug else None
-    rc = check(lib().sharp_wMetaC(_ip(lab), N, Cc, _hmethod(hmethod), int(enN_cluster or 0), minN, maxN,
-                                  C.c_double(0.0 if sil_thre is None else sil_thre),   # R/wMetaC.R:94-97
-                                  C.c_double(2.0 if height_Ntimes is None else height_Ntimes), _ip(finalC), _dp(x0),
-                                  C.byref(ncl), _dp(w1), _dp(S), C.byref(allC), _ip(tf)), allow=48)
+    rc = check(lib().sharp_wMetaC(i32(lab), N, Cc, _hmethod(hmethod), int(enN_cluster or 0), minN, maxN,
+                                  0.0 if sil_thre is None else sil_thre,   # R/wMetaC.R:94-97
+                                  2.0 if height_Ntimes is None else height_Ntimes, i32(finalC), f64(x0), C.byref(ncl), f64(w1), f64(S),
+                                  C.byref(allC), i32(tf)), allow=48)
     out = {"finalC": finalC, "x0": x0[: N * ncl.value].reshape(ncl.value, N).T.copy(), "warn": rc}
     if debug:
         A = allC.value
@@ -234,9 +223,8 @@ def sMetaC(rerowColor, sE1, folds=None, hmethod=None, finalN_cluster=None, minN_
     fin = np.zeros(n, np.int32)
     tf = np.zeros(n, np.int32)
     nC = C.c_int()
-    rc = check(lib().sharp_sMetaC(_ip(lab), _dp(E), C.c_longlong(n), p, _hmethod(hmethod), int(finalN_cluster or 0),
-                                  int(minN_cluster), int(maxN_cluster), C.c_double(sil_thre), C.c_double(height_Ntimes),
-                                  _ip(fin), _ip(tf), C.byref(nC)), allow=16)
+    rc = check(lib().sharp_sMetaC(i32(lab), f64(E), n, p, _hmethod(hmethod), int(finalN_cluster or 0), int(minN_cluster),
+                                  int(maxN_cluster), sil_thre, height_Ntimes, i32(fin), i32(tf), C.byref(nC)), allow=16)
     return {"finalColor": fin, "tf": tf[: nC.value].copy(), "warn": rc}
 
 
@@ -252,6 +240,14 @@ def _csc_int_slots(blocks):
             raise SharpError("sparse block %d: more than 2^31 - 1 stored entries, rows or columns (the C ABI, like R's dgCMatrix, "
                              "indexes with int): split the block" % (q + 1))
     return ([np.ascontiguousarray(b.indptr, np.int32) for b in blocks], [np.ascontiguousarray(b.indices, np.int32) for b in blocks])
+
+
+def _csc_pointer_lists(cps, ris, vxs):
+    """The const int *const * / const double *const * arguments of the *_csc block-list entries: one pointer per block.  A block without
+    stored entries has empty @i / @x vectors; those go over as an explicit NULL."""
+    B = len(cps)
+    return ((C.c_void_p * B)(*[i32(a) for a in cps]), (C.c_void_p * B)(*[i32(a) if a.size else None for a in ris]),
+            (C.c_void_p * B)(*[f64(a) if a.size else None for a in vxs]))
 
 
 def testlog(scExp, ncells, p, sncells=100, n_cores=None, cells=None):
@@ -270,6 +266,18 @@ def testlog(scExp, ncells, p, sncells=100, n_cores=None, cells=None):
         E1 = pr.project(sE, logflag=(k == 2))
         msil.append(getrowColor(E1, "ward.D", None, 2, 40, 0.0, 2.0)["maxsil"])
     return bool(msil[0] < 0.75 and msil[0] >= 0.95 * msil[1])
+
+
+def _rn_seed(rN_seed, sentinel_ok=False):
+    """rN.seed as every front door checks it (R/SHARP.R:169-179).  None gives 0.5, the reference's "not reproducible" sentinel; only
+    SHARP also takes a 0.5 that is given."""
+    if rN_seed is None:
+        return 0.5
+    if not isinstance(rN_seed, (int, float, np.integer, np.floating)):
+        raise SharpError("The rN.seed should be a numeric!")
+    if rN_seed % 1 != 0 and not (sentinel_ok and rN_seed == 0.5):
+        raise SharpError("The rN.seed should be an integer!")
+    return rN_seed
 
 
 def _enresults(pred, x0, viE, ncells, ngenes, p, K, t0, paras, forview, key="N.pred_cluster", allrpinfo=None):
@@ -295,7 +303,7 @@ def _allrpinfo():
     check(lib().sharp_last_rpinfo(C.byref(n), C.byref(K), C.byref(p), None, None))
     enrp = np.zeros((K.value, n.value), np.int32)
     indE = np.zeros((n.value, K.value * p.value))
-    check(lib().sharp_last_rpinfo(None, None, None, _ip(enrp), _dp(indE)))
+    check(lib().sharp_last_rpinfo(None, None, None, i32(enrp), f64(indE)))
     out = []
     for k in range(K.value):
         rc_ = [colorL[j - 1] for j in enrp[k]]
@@ -323,16 +331,12 @@ def _run_sharp(X, K, p, base_ncells, partition_ncells, hmethod, N_cluster, enpN,
     capc = max(int(maxN or 0), 40, (n + 4999) // 5000) + 2
     x0 = np.zeros(n * capc) if forview else None
     npred, x0c, pu, Ku, path = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    entry = ((lib().sharp_SHARP_csc, (_ip(cp), _ip(ri), _dp(xv), m, C.c_longlong(n))) if sparse else
-             (lib().sharp_SHARP, (_dp(X), m, C.c_longlong(n), C.c_longlong(m))))
-    rc = check(entry[0](*entry[1], int(K or 0), int(p or 0),
-                                 int(base_ncells or 0), int(partition_ncells or 0), _hmethod(hmethod, flashmark), int(N_cluster or 0),
-                                 int(enpN or 0), int(indN or 0), int(minN or 0), int(maxN or 0),
-                                 C.c_double(-1.0 if sil_thre is None else sil_thre),
-                                 C.c_double(0.0 if height_Ntimes is None else height_Ntimes), int(bool(flag)),
-                                 int(rM.handle if isinstance(rM, Projector) else 0), C.c_double(rN_seed), _ip(pred),
-                                 C.byref(npred), _dp(viE), _dp(x0), capc, C.byref(x0c), C.byref(pu), C.byref(Ku),
-                                 C.byref(path)), allow=48)
+    entry, head = (lib().sharp_SHARP_csc, (i32(cp), i32(ri), f64(xv), m, n)) if sparse else (lib().sharp_SHARP, (f64(X), m, n, m))
+    rc = check(entry(*head, int(K or 0), int(p or 0), int(base_ncells or 0), int(partition_ncells or 0), _hmethod(hmethod, flashmark),
+                     int(N_cluster or 0), int(enpN or 0), int(indN or 0), int(minN or 0), int(maxN or 0),
+                     -1.0 if sil_thre is None else sil_thre, 0.0 if height_Ntimes is None else height_Ntimes, int(bool(flag)),
+                     int(rM.handle if isinstance(rM, Projector) else 0), rN_seed, i32(pred), C.byref(npred), f64(viE), f64(x0), capc,
+                     C.byref(x0c), C.byref(pu), C.byref(Ku), C.byref(path)), allow=48)
     x0m = x0[: n * x0c.value].reshape(x0c.value, n).T.copy() if forview else None
     info = _allrpinfo() if forview and path.value == 0 else None          # SHARP_small only (R/SHARP.R:446)
     return pred, x0m, viE, pu.value, Ku.value, path.value, rc, info
@@ -385,13 +389,7 @@ def SHARP(scExp, exp_type=None, ensize_K=None, reduced_ndim=None, base_ncells=No
             X.data = X.data / np.repeat(colsum, np.diff(X.indptr)) * 1e6
         else:
             X = X / X.sum(0, keepdims=True) * 1e6
-    if rN_seed is not None:                                               # :169-179
-        if not isinstance(rN_seed, (int, float, np.integer, np.floating)):
-            raise SharpError("The rN.seed should be a numeric!")
-        if rN_seed % 1 != 0 and rN_seed != 0.5:
-            raise SharpError("The rN.seed should be an integer!")
-    else:
-        rN_seed = 0.5
+    rN_seed = _rn_seed(rN_seed, sentinel_ok=True)                         # :169-179
     p = int(reduced_ndim) if reduced_ndim else int(np.ceil(np.log2(ncells) / 0.04))   # :119-122
     if logflag is None:
         logflag = ncells < 1e4                                            # :202-209
@@ -463,13 +461,7 @@ def SHARP_unlimited(scExp, viewflag=True, n_cores=None, ensize_K=None, N_cluster
     if len(scExp) == 1:                                                   # :47-51
         warnings.warn("SHARP is used instead of SHARP_unlimited because the length of the input is 1!")
         return SHARP(scExp[0])
-    if rN_seed is not None:
-        if not isinstance(rN_seed, (int, float, np.integer, np.floating)):
-            raise SharpError("The rN.seed should be a numeric!")
-        if rN_seed % 1 != 0:
-            raise SharpError("The rN.seed should be an integer!")
-    else:
-        rN_seed = 0.5
+    rN_seed = _rn_seed(rN_seed)
     _lib.ensure_init()
     sparse = all(_is_sparse(b) for b in scExp)                            # a list of dgCMatrix-like blocks (:125-135 hands them on as they are)
     if sparse:
@@ -488,6 +480,9 @@ def SHARP_unlimited(scExp, viewflag=True, n_cores=None, ensize_K=None, N_cluster
     # block on the GPU (sharp_unlimited_view_dim), so that ncells x 50 doubles come back instead of ncells x p
     kdim = 50 if (viewflag and n > 1e5) else 0
     viE = np.zeros((n, kdim if kdim else p)) if viewflag else None
+    B = len(blocks)
+    common = (int(ensize_K or 0), int(N_cluster or 0), int(minN_cluster or 0), int(maxN_cluster or 0), rN_seed)
+    outs = (i32(pred), C.byref(npred), C.byref(pu), f64(viE))
 
     def call(entry, *args):
         # the arm is one-shot and thread-local in the library, taken by the call that follows on this thread; it is set here, after all the
@@ -504,30 +499,17 @@ def SHARP_unlimited(scExp, viewflag=True, n_cores=None, ensize_K=None, N_cluster
         # only the non-zeros of a block cross PCIe, block b + W while block b is clustered (sharp_SHARP_unlimited_csc_multi)
         cps, ris = _csc_int_slots(blocks)
         vxs = [np.ascontiguousarray(b.data, np.float64) for b in blocks]
-        B = len(blocks)
-        cpp = (C.POINTER(C.c_int) * B)(*[_ip(a) for a in cps])
-        rip = (C.POINTER(C.c_int) * B)(*[_ip(a) if a.size else C.cast(None, C.POINTER(C.c_int)) for a in ris])
-        vxp = (C.POINTER(C.c_double) * B)(*[_dp(a) if a.size else C.cast(None, C.POINTER(C.c_double)) for a in vxs])
+        cpp, rip, vxp = _csc_pointer_lists(cps, ris, vxs)
         dv = np.ascontiguousarray(devices if devices is not None else [], np.int32)
-        call(lib().sharp_SHARP_unlimited_csc_multi, cpp, rip, vxp, ncb.ctypes.data_as(C.POINTER(C.c_longlong)), B, m, int(ensize_K or 0),
-             int(N_cluster or 0), int(minN_cluster or 0), int(maxN_cluster or 0), C.c_double(rN_seed),
-             _ip(dv) if dv.size else None, int(dv.size), _ip(pred), C.byref(npred), C.byref(pu), _dp(viE))
-        K = int(ensize_K or 5)
-        out = _enresults(pred, None, None, n, m, pu.value, K, t0, {}, False, key="N.pred_clusters")
-        if viewflag:                                                      # :215-232
-            out["viE"] = viE
-            out["x0"] = _one_hot(pred, npred.value)
-        return out
-    ptrs = (C.POINTER(C.c_double) * len(blocks))(*[_dp(b) for b in blocks])
-    if devices is not None and len(devices) >= 1:
-        dv = np.ascontiguousarray(devices, np.int32)
-        call(lib().sharp_SHARP_unlimited_multi, ptrs, ncb.ctypes.data_as(C.POINTER(C.c_longlong)), len(blocks), m, int(ensize_K or 0),
-             int(N_cluster or 0), int(minN_cluster or 0), int(maxN_cluster or 0),
-             C.c_double(rN_seed), _ip(dv), len(dv), _ip(pred), C.byref(npred), C.byref(pu), _dp(viE))
+        call(lib().sharp_SHARP_unlimited_csc_multi, cpp, rip, vxp, i64(ncb), B, m, *common, i32(dv) if dv.size else None, int(dv.size),
+             *outs)
     else:
-        call(lib().sharp_SHARP_unlimited_view, ptrs, ncb.ctypes.data_as(C.POINTER(C.c_longlong)), len(blocks), m, int(ensize_K or 0),
-             int(N_cluster or 0), int(minN_cluster or 0), int(maxN_cluster or 0),
-             C.c_double(rN_seed), _ip(pred), C.byref(npred), C.byref(pu), _dp(viE))
+        ptrs = (C.c_void_p * B)(*[f64(b) for b in blocks])
+        if devices is not None and len(devices) >= 1:
+            dv = np.ascontiguousarray(devices, np.int32)
+            call(lib().sharp_SHARP_unlimited_multi, ptrs, i64(ncb), B, m, *common, i32(dv), len(dv), *outs)
+        else:
+            call(lib().sharp_SHARP_unlimited_view, ptrs, i64(ncb), B, m, *common, *outs)
     K = int(ensize_K or 5)
     out = _enresults(pred, None, None, n, m, pu.value, K, t0, {}, False, key="N.pred_clusters")
     if viewflag:                                                          # :215-232
@@ -549,13 +531,7 @@ def SHARP_unlimited2(scExp, ensize_K=None, reduced_ndim=None, partition_ncells=N
         raise SharpError("No expression data is provided!")
     if not isinstance(scExp, (list, tuple)):
         raise SharpError("The input should be a LIST of partitioned scRNA-seq expression matrices!")
-    if rN_seed is not None:
-        if not isinstance(rN_seed, (int, float, np.integer, np.floating)):
-            raise SharpError("The rN.seed should be a numeric!")
-        if rN_seed % 1 != 0:
-            raise SharpError("The rN.seed should be an integer!")
-    else:
-        rN_seed = 0.5
+    rN_seed = _rn_seed(rN_seed)
     _lib.ensure_init()
     blocks = [np.asfortranarray(b, dtype=np.float64) for b in scExp]
     m = blocks[0].shape[0]
@@ -568,17 +544,15 @@ def SHARP_unlimited2(scExp, ensize_K=None, reduced_ndim=None, partition_ncells=N
     if logflag:                                                                         # :71-82: testlog on the FIRST block
         nc1 = blocks[0].shape[1]
         flag = testlog(blocks[0], nc1, p, sncells=100, cells=testlog_cells)
-    ptrs = (C.POINTER(C.c_double) * len(blocks))(*[_dp(b) for b in blocks])
+    ptrs = (C.c_void_p * len(blocks))(*[f64(b) for b in blocks])
     pred = np.zeros(n, np.int32)
     npred, pu = C.c_int(), C.c_int()
     viE = np.zeros((n, p)) if forview else None
-    rc = check(lib().sharp_SHARP_unlimited2(ptrs, ncb.ctypes.data_as(C.POINTER(C.c_longlong)), len(blocks), m, int(ensize_K or 0),
-                                            int(reduced_ndim or 0), int(partition_ncells or 0), _hmethod(hmethod),
-                                            int(N_cluster or 0), int(enpN_cluster or 0), int(indN_cluster or 0),
-                                            int(minN_cluster or 0), int(maxN_cluster or 0),
-                                            C.c_double(-1.0 if sil_thre is None else sil_thre),
-                                            C.c_double(0.0 if height_Ntimes is None else height_Ntimes), int(bool(flag)),
-                                            C.c_double(rN_seed), _ip(pred), C.byref(npred), C.byref(pu), _dp(viE)), allow=48)
+    rc = check(lib().sharp_SHARP_unlimited2(ptrs, i64(ncb), len(blocks), m, int(ensize_K or 0), int(reduced_ndim or 0),
+                                            int(partition_ncells or 0), _hmethod(hmethod), int(N_cluster or 0), int(enpN_cluster or 0),
+                                            int(indN_cluster or 0), int(minN_cluster or 0), int(maxN_cluster or 0),
+                                            -1.0 if sil_thre is None else sil_thre, 0.0 if height_Ntimes is None else height_Ntimes,
+                                            int(bool(flag)), rN_seed, i32(pred), C.byref(npred), C.byref(pu), f64(viE)), allow=48)
     K = int(ensize_K or 5)
     paras = {"ensize.K": K, "reduced.ndim": pu.value, "partition.ncells": int(partition_ncells or 2000), "logmark": bool(flag),
              "hmethod": hmethod or "ward.D", "N.cluster": N_cluster, "minN.cluster": int(minN_cluster or 2),
@@ -619,13 +593,7 @@ def SHARP_unlimited3(ndinfo, viewflag=True, n_cores=None, ensize_K=None, rN_seed
     except FileNotFoundError as e:
         raise SharpError(str(e))
     ncells, ngenes = int(ndinfo["ncells"]), int(ndinfo["ngenes"])
-    if rN_seed is not None:
-        if not isinstance(rN_seed, (int, float, np.integer, np.floating)):
-            raise SharpError("The rN.seed should be a numeric!")
-        if rN_seed % 1 != 0:
-            raise SharpError("The rN.seed should be an integer!")
-    else:
-        rN_seed = 0.5
+    rN_seed = _rn_seed(rN_seed)
     K = int(ensize_K or 5)
     p = int(np.ceil(np.log2(ncells) / 0.04))                                       # :66, from ndinfo$ncells
     _lib.ensure_init()
@@ -746,7 +714,7 @@ def get_marker_genes(scExp, y, theta=1e-4, auc=0.7, pvalue=0.01, FC=2, ng=1, n_c
     label = (np.searchsorted(uy, pred) + 1).astype(np.int32)
     G = int(uy.size)
     out = np.zeros((m, 5))
-    check(lib().sharp_marker_genes(_dp(X), m, C.c_longlong(n), C.c_longlong(m), _ip(label), G, C.c_double(theta), int(ng), _dp(out)))
+    check(lib().sharp_marker_genes(f64(X), m, n, m, i32(label), G, theta, int(ng), f64(out)))
     cols = {"gene": names, "auc": out[:, 0], "icluster": out[:, 1].astype(np.int64), "pvalue": out[:, 2].copy(),
             "sparsity": out[:, 3], "FC": out[:, 4]}
     sel = (cols["sparsity"] > theta) & ~np.isnan(cols["pvalue"])          # :158-159
@@ -815,11 +783,8 @@ def get_marker_genes_unlimited(scExp, y, theta=1e-5, auc=0.85, pvalue=0.01, n_co
             b.sum_duplicates()
         cps, ris = _csc_int_slots(blocks)
         vxs = [np.ascontiguousarray(b.data, np.float64) for b in blocks]
-        cpp = (C.POINTER(C.c_int) * B)(*[_ip(v) for v in cps])
-        rip = (C.POINTER(C.c_int) * B)(*[_ip(v) if v.size else C.cast(None, C.POINTER(C.c_int)) for v in ris])
-        vxp = (C.POINTER(C.c_double) * B)(*[_dp(v) if v.size else C.cast(None, C.POINTER(C.c_double)) for v in vxs])
-        check(lib().sharp_marker_genes_blocks_csc(cpp, rip, vxp, ncb.ctypes.data_as(C.POINTER(C.c_longlong)), B, m, _ip(label), G,
-                                                  C.c_double(theta), 1, _dp(out)))
+        cpp, rip, vxp = _csc_pointer_lists(cps, ris, vxs)
+        check(lib().sharp_marker_genes_blocks_csc(cpp, rip, vxp, i64(ncb), B, m, i32(label), G, theta, 1, f64(out)))
     else:
         import torch
 
@@ -827,8 +792,7 @@ def get_marker_genes_unlimited(scExp, y, theta=1e-5, auc=0.85, pvalue=0.01, n_co
         torch.cuda.synchronize()
         ptrs = (C.c_void_p * B)(*[t.data_ptr() for t in dbl])
         ldb = np.array([t.stride(0) for t in dbl], np.int64)
-        check(lib().sharp_marker_genes_blocks_dev(ptrs, ncb.ctypes.data_as(C.POINTER(C.c_longlong)), ldb.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                                  B, m, _ip(label), G, C.c_double(theta), 1, _dp(out)))
+        check(lib().sharp_marker_genes_blocks_dev(ptrs, i64(ncb), i64(ldb), B, m, i32(label), G, theta, 1, f64(out)))
     nonzero = out[:, 3] > 0                                               # :44-57: a gene that is zero in every block is not a row of g5 at all
     s, _gall = _marker_select(out[nonzero], names[nonzero], theta, auc, pvalue)
     rows = np.array([int(np.nonzero(names == nm)[0][0]) for nm in s["gene"].tolist()], dtype=np.int64)
@@ -861,7 +825,7 @@ def get_marker_genes_unlimited2(gdinfo, y, theta=1e-5, auc=0.85, pvalue=0.05, n_
         Xf = np.asfortranarray(X, dtype=np.float64)
         mi = Xf.shape[0]
         o = np.zeros((mi, 5))
-        check(lib().sharp_marker_genes(_dp(Xf), mi, C.c_longlong(n), C.c_longlong(mi), _ip(label), G, C.c_double(theta), rr, _dp(o)))
+        check(lib().sharp_marker_genes(f64(Xf), mi, n, mi, i32(label), G, theta, rr, f64(o)))
         outs.append(o)
         names.extend("%s:%d" % (os.path.basename(f), j) for j in range(mi))
     out = np.concatenate(outs) if outs else np.zeros((0, 5))
@@ -900,7 +864,7 @@ def last_decisions():
     n = C.c_int()
     check(lib().sharp_last_decisions(None, 0, C.byref(n)))
     rows = np.zeros((max(n.value, 1), DECISION_COLS))
-    check(lib().sharp_last_decisions(_dp(rows), rows.shape[0], C.byref(n)))
+    check(lib().sharp_last_decisions(f64(rows), rows.shape[0], C.byref(n)))
     return rows[: n.value]
 
 

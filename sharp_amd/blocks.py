@@ -13,7 +13,6 @@ formats used here (an R maintainer writes them with `writeBin`, INTEGRATION.md);
 While earlier blocks are clustered a reader thread brings the next files into a ring of pinned buffers and enqueues their copies on a
 side stream; the consumer takes the blocks that have arrived -- several at a time when the clustering is the slower side, as one
 pipelined batch (SHARP_unlimited3)."""
-import ctypes as C
 import os
 import re
 import struct
@@ -305,8 +304,8 @@ class BlockStreamer:
         dX = self.dense[slot][: n * ld * (8 if h["f64"] else 4)].view(dt).view(n, ld)
         if h["version"] == 2:
             base = self.stage[slot].data_ptr()
-            check(lib().sharp_csc_packed_expand_dev(C.c_void_p(base), C.c_void_p(base + h["o_idx"]), h["idx_bits"], C.c_void_p(base + h["o_val"]),
-                                                    h["val_bits"], m, C.c_longlong(n), C.c_void_p(dX.data_ptr()), C.c_longlong(ld), int(h["f64"])))
+            check(lib().sharp_csc_packed_expand_dev(base, base + h["o_idx"], h["idx_bits"], base + h["o_val"], h["val_bits"], m, n,
+                                                    dX.data_ptr(), ld, int(h["f64"])))
         self.expand_seconds += time.perf_counter() - t_ex
         return dX[:, :m]
 

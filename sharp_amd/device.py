@@ -6,15 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import SharpError, check, lib
-
-
-def _ip(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+from ._lib import SharpError, check, f64, i32, i64, lib
 
 
 def synth_fill(dX, seed, cell0, G=12, nmark=1000):
@@ -22,14 +14,13 @@ def synth_fill(dX, seed, cell0, G=12, nmark=1000):
     _lib.ensure_init()
     ncell, m = dX.shape
     assert dX.is_contiguous() and str(dX.dtype) == "torch.float32"
-    check(lib().sharp_synth_fill_dev(C.c_uint(seed), m, C.c_longlong(cell0), ncell, G, nmark, C.c_void_p(dX.data_ptr()),
-                                     C.c_longlong(m)))
+    check(lib().sharp_synth_fill_dev(seed, m, cell0, ncell, G, nmark, dX.data_ptr(), m))
     check(lib().sharp_synchronize())
 
 
 def synth_labels(seed, cell0, ncell, G=12):
     out = np.zeros(ncell, np.int32)
-    check(lib().sharp_synth_labels(C.c_uint(seed), C.c_longlong(cell0), ncell, G, _ip(out)))
+    check(lib().sharp_synth_labels(seed, cell0, ncell, G, i32(out)))
     return out
 
 
@@ -51,7 +42,7 @@ def csc_to_dev(sp):
     cp = np.ascontiguousarray(sp.indptr, np.int32)
     ri = np.ascontiguousarray(sp.indices, np.int32)
     xv = np.ascontiguousarray(sp.data, np.float64)
-    check(lib().sharp_csc_to_dense_dev(_ip(cp), _ip(ri), _dp(xv), m, C.c_longlong(n), C.c_void_p(dX.data_ptr()), C.c_longlong(m)))
+    check(lib().sharp_csc_to_dense_dev(i32(cp), i32(ri), f64(xv), m, n, dX.data_ptr(), m))
     return dX
 
 
@@ -76,11 +67,9 @@ def SHARP_dev(dX, ensize_K=0, reduced_ndim=0, base_ncells=0, partition_ncells=0,
             viE = np.empty((n, pmax))
             x0 = np.empty(n * cap)
     entry = lib().sharp_SHARP_dev64 if str(dX.dtype) == "torch.float64" else lib().sharp_SHARP_dev
-    rc = check(entry(C.c_void_p(dX.data_ptr()), m, C.c_longlong(n), C.c_longlong(dX.stride(0)), ensize_K,
-                                     reduced_ndim, base_ncells, partition_ncells, hmethod, N_cluster, enpN_cluster,
-                                     indN_cluster, minN_cluster, maxN_cluster, C.c_double(sil_thre), C.c_double(height_Ntimes),
-                                     int(bool(flag)), projector, C.c_double(rN_seed), _ip(pred), C.byref(npred), _dp(viE), _dp(x0), cap,
-                                     C.byref(x0c), C.byref(pu), C.byref(Ku), C.byref(path)), allow=48)
+    rc = check(entry(dX.data_ptr(), m, n, dX.stride(0), ensize_K, reduced_ndim, base_ncells, partition_ncells, hmethod, N_cluster,
+                     enpN_cluster, indN_cluster, minN_cluster, maxN_cluster, sil_thre, height_Ntimes, int(bool(flag)), projector, rN_seed,
+                     i32(pred), C.byref(npred), f64(viE), f64(x0), cap, C.byref(x0c), C.byref(pu), C.byref(Ku), C.byref(path)), allow=48)
     info = {"N.pred_cluster": npred.value, "reduced.dim": pu.value, "ensize.K": Ku.value,
             "path": "SHARP_large" if path.value else "SHARP_small", "warn": rc}
     if forview:
@@ -102,10 +91,9 @@ def unlimited_block_dev(dX, p, projector, ensize_K, rN_seed, cap_rows=4096, flag
     (sharp_unlimited_next_block_dev)."""
     _lib.ensure_init()
     nb, m = dX.shape
-    f64 = str(dX.dtype) == "torch.float64"
-    if next_block is not None and not f64 and str(next_block.dtype) == "torch.float32":
-        check(lib().sharp_unlimited_next_block_dev(C.c_void_p(next_block.data_ptr()), C.c_longlong(next_block.shape[0]),
-                                                   C.c_longlong(next_block.stride(0))))
+    dbl = str(dX.dtype) == "torch.float64"
+    if next_block is not None and not dbl and str(next_block.dtype) == "torch.float32":
+        check(lib().sharp_unlimited_next_block_dev(next_block.data_ptr(), next_block.shape[0], next_block.stride(0)))
     if viE is not None and view_dim > 0 and view_seed is None:
         if rN_seed == 0.5:
             raise SharpError("unlimited_block_dev: an unseeded run reduced block by block needs view_seed, the one seed of the run's z0")
@@ -114,11 +102,9 @@ def unlimited_block_dev(dX, p, projector, ensize_K, rN_seed, cap_rows=4096, flag
     means = np.empty((cap_rows, p))                 # only the first G rows are written and returned
     counts = np.empty(cap_rows, np.int64)
     G = C.c_int()
-    entry = lib().sharp_unlimited_block_viewk_dev64 if f64 else lib().sharp_unlimited_block_viewk_dev      # (a float64 block: TPM / CPM-like values)
-    check(entry(C.c_void_p(dX.data_ptr()), m, C.c_longlong(nb), C.c_longlong(dX.stride(0)), p,
-                                                projector, ensize_K, C.c_double(rN_seed), int(bool(flag)), _ip(pred), C.byref(G),
-                                                _dp(means), cap_rows, counts.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                                int(view_dim) if viE is not None else 0, C.c_double(view_seed or 0.0), _dp(viE)))
+    entry = lib().sharp_unlimited_block_viewk_dev64 if dbl else lib().sharp_unlimited_block_viewk_dev      # (a float64 block: TPM / CPM-like values)
+    check(entry(dX.data_ptr(), m, nb, dX.stride(0), p, projector, ensize_K, rN_seed, int(bool(flag)), i32(pred), C.byref(G), f64(means),
+                cap_rows, i64(counts), int(view_dim) if viE is not None else 0, view_seed or 0.0, f64(viE)))
     return pred, means[: G.value].copy(), counts[: G.value].copy()
 
 
@@ -132,16 +118,15 @@ def unlimited_blocks_dev(blocks, p, projector, ensize_K, rN_seed, cap_rows=4096)
     B = len(blocks)
     m = blocks[0].shape[1]
     ptrs = (C.c_void_p * B)(*[b.data_ptr() for b in blocks])
-    f64 = np.array([1 if b.dtype == torch.float64 else 0 for b in blocks], np.int32)
+    dbl = np.array([1 if b.dtype == torch.float64 else 0 for b in blocks], np.int32)
     ncb = np.array([b.shape[0] for b in blocks], np.int64)
     ldb = np.array([b.stride(0) for b in blocks], np.int64)
     pred = np.zeros(int(ncb.sum()), np.int32)
     ncl = np.zeros(B, np.int32)
     means = np.empty((cap_rows * B, p))
     counts = np.empty(cap_rows * B, np.int64)
-    check(lib().sharp_unlimited_blocks_dev(ptrs, _ip(f64), ncb.ctypes.data_as(C.POINTER(C.c_longlong)), ldb.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                           B, m, p, projector, ensize_K, C.c_double(rN_seed), _ip(pred), _ip(ncl), _dp(means), cap_rows * B,
-                                           counts.ctypes.data_as(C.POINTER(C.c_longlong))))
+    check(lib().sharp_unlimited_blocks_dev(ptrs, i32(dbl), i64(ncb), i64(ldb), B, m, p, projector, ensize_K, rN_seed, i32(pred), i32(ncl),
+                                           f64(means), cap_rows * B, i64(counts)))
     out, o, r = [], 0, 0
     for b in range(B):
         g = int(ncl[b])
@@ -167,9 +152,9 @@ def unlimited_dev(blocks, ensize_K=0, N_cluster=0, minN_cluster=0, maxN_cluster=
         kdim = int(view_dim) if view_dim is not None else (50 if n > 1e5 else 0)
         cols = kdim if kdim else int(np.ceil(np.log2(n) / 0.04))
         viE = viE_out if viE_out is not None and viE_out.shape == (n, cols) else np.zeros((n, cols))
-    check(lib().sharp_SHARP_unlimited_viewk_dev(ptrs, ncb.ctypes.data_as(C.POINTER(C.c_longlong)), ldb.ctypes.data_as(C.POINTER(C.c_longlong)), B,
-                                                int(blocks[0].shape[1]), int(ensize_K), int(N_cluster), int(minN_cluster), int(maxN_cluster),
-                                                C.c_double(rN_seed), _ip(pred), C.byref(npred), C.byref(pu), kdim, _dp(viE)), allow=48)
+    check(lib().sharp_SHARP_unlimited_viewk_dev(ptrs, i64(ncb), i64(ldb), B, int(blocks[0].shape[1]), int(ensize_K), int(N_cluster),
+                                                int(minN_cluster), int(maxN_cluster), rN_seed, i32(pred), C.byref(npred), C.byref(pu), kdim,
+                                                f64(viE)), allow=48)
     return pred, npred.value, pu.value, viE
 
 
@@ -183,7 +168,7 @@ def unlimited_multi_dev(blocks, device_of_block, devices, ensize_K=0, N_cluster=
     B = len(blocks)
     m = int(blocks[0].shape[1])
     ptrs = (C.c_void_p * B)(*[b.data_ptr() for b in blocks])
-    f64 = np.array([1 if b.dtype == torch.float64 else 0 for b in blocks], np.int32)
+    dbl = np.array([1 if b.dtype == torch.float64 else 0 for b in blocks], np.int32)
     ncb = np.array([b.shape[0] for b in blocks], np.int64)
     ldb = np.array([b.stride(0) for b in blocks], np.int64)
     dob = np.ascontiguousarray(device_of_block, np.int32)
@@ -195,10 +180,9 @@ def unlimited_multi_dev(blocks, device_of_block, devices, ensize_K=0, N_cluster=
     npred, pu = C.c_int(), C.c_int()
     for b in blocks:
         torch.cuda.synchronize(b.device)
-    check(lib().sharp_SHARP_unlimited_multi_dev(ptrs, _ip(f64), ncb.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                                ldb.ctypes.data_as(C.POINTER(C.c_longlong)), _ip(dob), B, m, int(ensize_K), int(N_cluster),
-                                                int(minN_cluster), int(maxN_cluster), C.c_double(rN_seed), _ip(dv), len(dv), _ip(pred),
-                                                C.byref(npred), C.byref(pu), _dp(viE) if viE is not None else None), allow=48)
+    check(lib().sharp_SHARP_unlimited_multi_dev(ptrs, i32(dbl), i64(ncb), i64(ldb), i32(dob), B, m, int(ensize_K), int(N_cluster),
+                                                int(minN_cluster), int(maxN_cluster), rN_seed, i32(dv), len(dv), i32(pred), C.byref(npred),
+                                                C.byref(pu), f64(viE)), allow=48)
     return pred, npred.value, pu.value, viE
 
 
@@ -206,7 +190,7 @@ def multi_timeline(cap=4096):
     """sharp_multi_timeline: rows of (worker, block, upload start, upload end, clustering start, clustering end) of the last multi-device call"""
     rows = np.zeros((cap, 6))
     n = C.c_int()
-    check(lib().sharp_multi_timeline(_dp(rows), cap, C.byref(n)))
+    check(lib().sharp_multi_timeline(f64(rows), cap, C.byref(n)))
     return rows[:min(n.value, cap)]
 
 
@@ -218,8 +202,8 @@ def unlimited_merge(means, counts, ncells, N_cluster=0, minN_cluster=0, maxN_clu
     nC, p = means.shape
     fid = np.zeros(nC, np.int32)
     nf = C.c_int()
-    check(lib().sharp_unlimited_merge(_dp(means), counts.ctypes.data_as(C.POINTER(C.c_longlong)), nC, p, C.c_longlong(ncells),
-                                      N_cluster, minN_cluster, maxN_cluster, _ip(fid), C.byref(nf)))
+    check(lib().sharp_unlimited_merge(f64(means), i64(counts), nC, p, ncells, N_cluster, minN_cluster, maxN_cluster, i32(fid),
+                                      C.byref(nf)))
     return fid, nf.value
 
 
@@ -229,8 +213,7 @@ def marker_genes_dev(dX, labels, n_cluster, theta=1e-4, ng=1):
     n, m = dX.shape
     lab = np.ascontiguousarray(labels, np.int32)
     out = np.zeros((m, 5))
-    check(lib().sharp_marker_genes_dev(C.c_void_p(dX.data_ptr()), m, C.c_longlong(n), C.c_longlong(dX.stride(0)), _ip(lab), int(n_cluster),
-                                       C.c_double(theta), int(ng), _dp(out)))
+    check(lib().sharp_marker_genes_dev(dX.data_ptr(), m, n, dX.stride(0), i32(lab), int(n_cluster), theta, int(ng), f64(out)))
     return out
 
 

@@ -5,14 +5,13 @@ plot_markers is not only drawing: pheatmap(cluster_rows = T, cluster_cols = T, c
 hclust(dist(sm), "ward.D") over the marker genes and hclust(dist(t(sm)), "ward.D") over up to ~10 000 cells.  Both run on the GPU here
 (sharp_dist / sharp_hclust, csrc/dist.hip + the agglomeration kernels of csrc/hclust_agglo.hip behind hclust_tree of csrc/hclust.hip;
 DESIGN.md 11); the selection of markers and cells is host-side numpy and runs without a device."""
-import ctypes as C
 import math
 
 import numpy as np
 
 from . import _lib
-from ._lib import SharpError, check, lib
-from .api import HMETHODS, _dense, _dp, _ip, _is_sparse
+from ._lib import SharpError, check, f64, i32, lib
+from .api import HMETHODS, _dense, _is_sparse
 
 __all__ = ["hclust", "plot_markers", "get_percluster_exp", "DIST_METHODS", "set1_colors"]
 
@@ -49,7 +48,7 @@ def dist(x, method="euclidean", p=2):
         raise SharpError("dist: more than 46340 observations (the dist vector would pass 2^30 entries) is not supported")
     _lib.ensure_init()
     out = np.empty(n * (n - 1) // 2, np.float64)
-    check(lib().sharp_dist(_dp(a), n, d, C.c_longlong(d), code, C.c_double(float(p)), _dp(out)))
+    check(lib().sharp_dist(f64(a), n, d, d, code, float(p), f64(out)))
     return out
 
 
@@ -77,10 +76,10 @@ def hclust(d=None, x=None, method="ward.D", distance="euclidean", p=2):
     height = np.zeros(n - 1)
     order = np.zeros(n, np.int32)
     if d is not None:
-        check(lib().sharp_hclust_dist(_dp(dv), n, HMETHODS[method], _ip(merge), _dp(height), _ip(order)))
+        check(lib().sharp_hclust_dist(f64(dv), n, HMETHODS[method], i32(merge), f64(height), i32(order)))
     else:
-        check(lib().sharp_hclust(_dp(a), n, a.shape[1], C.c_longlong(a.shape[1]), code, C.c_double(float(p)), HMETHODS[method],
-                                 _ip(merge), _dp(height), _ip(order)))
+        check(lib().sharp_hclust(f64(a), n, a.shape[1], a.shape[1], code, float(p), HMETHODS[method], i32(merge), f64(height),
+                                 i32(order)))
     return {"merge": merge.T.copy(), "height": height, "order": order, "method": method, "dist_method": dist_method, "n": n}
 
 

@@ -12,17 +12,9 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import check, f64, i32, i64, lib
 
 __all__ = ["Rtsne", "Rtsne_neighbors", "knn"]
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _ip(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int))
 
 
 def _rows(X):
@@ -82,10 +74,18 @@ def _loop_args(n, dims, Y_init, stop_lying_iter, mom_switch_iter, who):
     return dims, Y_init, int(stop_lying_iter), int(mom_switch_iter)
 
 
-def _result(Y, ic, costs, n, origD, perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta,
-            exaggeration_factor, pca, normalize):
+def _optimise(entry, head, n, dims, origD, pca, normalize, perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter, momentum,
+              final_momentum, eta, exaggeration_factor, Y_init, seed):
+    """One run of an optimiser entry (sharp_tsne / sharp_tsne_bh, sharp_tsne_dist, sharp_tsne_neighbors) -> Rtsne's list.  head: the
+    entry's own leading arguments, up to where all of them go on alike: perplexity .. seed, then the outputs Y, itercosts, costs."""
+    _lib.ensure_init()
+    Y = np.zeros((n, dims))
+    ic = np.zeros(max(1, _n_itercosts(int(max_iter))))
+    costs = np.zeros(n)
+    check(entry(*head, perplexity, theta, int(max_iter), stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta, exaggeration_factor,
+                f64(Y_init), seed, f64(Y), f64(ic), f64(costs)))
     return {"Y": Y, "itercosts": ic[: _n_itercosts(int(max_iter))], "costs": costs, "N": n, "origD": origD, "perplexity": perplexity,
-            "theta": theta, "max_iter": int(max_iter), "stop_lying_iter": int(stop_lying_iter), "mom_switch_iter": int(mom_switch_iter),
+            "theta": theta, "max_iter": int(max_iter), "stop_lying_iter": stop_lying_iter, "mom_switch_iter": mom_switch_iter,
             "momentum": momentum, "final_momentum": final_momentum, "eta": eta, "exaggeration_factor": exaggeration_factor,
             "pca": bool(pca), "normalize": bool(normalize)}
 
@@ -114,31 +114,17 @@ def Rtsne(X, dims=2, initial_dims=50, perplexity=30, theta=0.5, check_duplicates
     _check_repulsion(repulsion)
     if is_distance:
         d, n = _condensed(X, "Rtsne")
-        dims, Y_init, stop_lying_iter, mom_switch_iter = _loop_args(n, dims, Y_init, stop_lying_iter, mom_switch_iter, "Rtsne")
-        _lib.ensure_init()
-        Y = np.zeros((n, dims))
-        ic = np.zeros(max(1, _n_itercosts(int(max_iter))))
-        costs = np.zeros(n)
-        check(lib().sharp_tsne_dist(_dp(d), int(n), int(repulsion == "barnes_hut"), dims, C.c_double(perplexity), C.c_double(theta),
-                                    int(max_iter), stop_lying_iter, mom_switch_iter, C.c_double(momentum), C.c_double(final_momentum),
-                                    C.c_double(eta), C.c_double(exaggeration_factor), _dp(Y_init), C.c_double(seed), _dp(Y), _dp(ic),
-                                    _dp(costs)))
-        return _result(Y, ic, costs, n, None, perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta,
-                       exaggeration_factor, False, False)
-    X = _rows(X)
-    n, d = X.shape
+    else:
+        X = _rows(X)
+        n, d = X.shape
     dims, Y_init, stop_lying_iter, mom_switch_iter = _loop_args(n, dims, Y_init, stop_lying_iter, mom_switch_iter, "Rtsne")
-    _lib.ensure_init()
-    Y = np.zeros((n, dims))
-    ic = np.zeros(max(1, _n_itercosts(int(max_iter))))
-    costs = np.zeros(n)
-    entry = lib().sharp_tsne_bh if repulsion == "barnes_hut" else lib().sharp_tsne
-    check(entry(_dp(X), C.c_longlong(n), int(d), C.c_longlong(d), dims, int(initial_dims), int(bool(pca)), int(bool(pca_center)),
-                           int(bool(pca_scale)), int(bool(normalize)), int(bool(check_duplicates)), C.c_double(perplexity), C.c_double(theta),
-                           int(max_iter), int(stop_lying_iter), int(mom_switch_iter), C.c_double(momentum), C.c_double(final_momentum),
-                           C.c_double(eta), C.c_double(exaggeration_factor), _dp(Y_init), C.c_double(seed), _dp(Y), _dp(ic), _dp(costs)))
-    return _result(Y, ic, costs, n, min(int(initial_dims), d) if pca else d, perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter,
-                   momentum, final_momentum, eta, exaggeration_factor, pca, normalize)
+    loop = (perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta, exaggeration_factor, Y_init, seed)
+    if is_distance:
+        return _optimise(lib().sharp_tsne_dist, (f64(d), int(n), int(repulsion == "barnes_hut"), dims), n, dims, None, False, False, *loop)
+    head = (f64(X), n, int(d), d, dims, int(initial_dims), int(bool(pca)), int(bool(pca_center)), int(bool(pca_scale)), int(bool(normalize)),
+            int(bool(check_duplicates)))
+    return _optimise(lib().sharp_tsne_bh if repulsion == "barnes_hut" else lib().sharp_tsne, head, n, dims,
+                     min(int(initial_dims), d) if pca else d, pca, normalize, *loop)
 
 
 def _neighbour_arrays(index, distance, who):
@@ -182,16 +168,9 @@ def Rtsne_neighbors(index, distance, dims=2, perplexity=30, theta=0.5, max_iter=
     index, distance = _neighbour_arrays(index, distance, who)
     n, K = index.shape
     dims, Y_init, stop_lying_iter, mom_switch_iter = _loop_args(n, dims, Y_init, stop_lying_iter, mom_switch_iter, who)
-    _lib.ensure_init()
-    Y = np.zeros((n, dims))
-    ic = np.zeros(max(1, _n_itercosts(int(max_iter))))
-    costs = np.zeros(n)
-    check(lib().sharp_tsne_neighbors(_ip(index), _dp(distance), C.c_longlong(n), int(K), int(bool(squared)), int(repulsion == "barnes_hut"),
-                                     dims, C.c_double(perplexity), C.c_double(theta), int(max_iter), stop_lying_iter, mom_switch_iter,
-                                     C.c_double(momentum), C.c_double(final_momentum), C.c_double(eta), C.c_double(exaggeration_factor),
-                                     _dp(Y_init), C.c_double(seed), _dp(Y), _dp(ic), _dp(costs)))
-    return _result(Y, ic, costs, n, None, perplexity, theta, max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta,
-                   exaggeration_factor, False, False)
+    head = (i32(index), f64(distance), n, int(K), int(bool(squared)), int(repulsion == "barnes_hut"), dims)
+    return _optimise(lib().sharp_tsne_neighbors, head, n, dims, None, False, False, perplexity, theta, max_iter, stop_lying_iter,
+                     mom_switch_iter, momentum, final_momentum, eta, exaggeration_factor, Y_init, seed)
 
 
 def knn(X, K, squared=False, is_distance=False):
@@ -208,7 +187,7 @@ def knn(X, K, squared=False, is_distance=False):
         _lib.ensure_init()
         idx = np.zeros((n, K), np.int32)
         d2 = np.zeros((n, K))
-        check(lib().sharp_tsne_knn_dist(_dp(d), int(n), K, _ip(idx), _dp(d2)))
+        check(lib().sharp_tsne_knn_dist(f64(d), int(n), K, i32(idx), f64(d2)))
         if squared:
             return idx, d2
         # the distances as given, not a root of their squares: entry (i, j) of the dist vector (i < j) sits at n i - i (i + 1) / 2 + j - i - 1
@@ -229,8 +208,8 @@ def _prepare(X, pca=True, initial_dims=50, pca_center=True, pca_scale=False, nor
     _lib.ensure_init()
     out = np.zeros((n, d))
     dd = C.c_int()
-    check(lib().sharp_tsne_prepare(_dp(X), C.c_longlong(n), d, C.c_longlong(d), int(pca), int(initial_dims), int(pca_center),
-                                   int(pca_scale), int(normalize), _dp(out), C.byref(dd)))
+    check(lib().sharp_tsne_prepare(f64(X), n, d, d, int(pca), int(initial_dims), int(pca_center), int(pca_scale), int(normalize), f64(out),
+                                   C.byref(dd)))
     return np.ascontiguousarray(out.reshape(-1)[: n * dd.value].reshape(n, dd.value))
 
 
@@ -240,7 +219,7 @@ def _knn(X, K):
     _lib.ensure_init()
     idx = np.zeros((n, K), np.int32)
     dist = np.zeros((n, K))
-    check(lib().sharp_tsne_knn(_dp(X), C.c_longlong(n), d, C.c_longlong(d), int(K), idx.ctypes.data_as(C.POINTER(C.c_int)), _dp(dist)))
+    check(lib().sharp_tsne_knn(f64(X), n, d, d, int(K), i32(idx), f64(dist)))
     return idx, dist
 
 
@@ -254,8 +233,8 @@ def _affinities_nn(index, distance, perplexity, squared=False):
     col = np.zeros(cap, np.int32)
     val = np.zeros(cap)
     nnz = C.c_longlong()
-    check(lib().sharp_tsne_affinities_nn(_ip(index), _dp(distance), C.c_longlong(n), int(K), int(bool(squared)), C.c_double(perplexity),
-                                         C.c_longlong(cap), rp.ctypes.data_as(C.POINTER(C.c_longlong)), _ip(col), _dp(val), C.byref(nnz)))
+    check(lib().sharp_tsne_affinities_nn(i32(index), f64(distance), n, int(K), int(bool(squared)), perplexity, cap, i64(rp), i32(col),
+                                         f64(val), C.byref(nnz)))
     return rp, col[: nnz.value].copy(), val[: nnz.value].copy()
 
 
@@ -269,8 +248,7 @@ def _affinities(X, perplexity):
     col = np.zeros(max(cap, 1), np.int32)
     val = np.zeros(max(cap, 1))
     nnz = C.c_longlong()
-    check(lib().sharp_tsne_affinities(_dp(X), C.c_longlong(n), d, C.c_longlong(d), C.c_double(perplexity), C.c_longlong(cap),
-                                      rp.ctypes.data_as(C.POINTER(C.c_longlong)), col.ctypes.data_as(C.POINTER(C.c_int)), _dp(val), C.byref(nnz)))
+    check(lib().sharp_tsne_affinities(f64(X), n, d, d, perplexity, cap, i64(rp), i32(col), f64(val), C.byref(nnz)))
     return rp, col[: nnz.value].copy(), val[: nnz.value].copy()
 
 
@@ -282,8 +260,7 @@ def _gradient(row_ptr, col, val, Y):
     cc = np.ascontiguousarray(col, np.int32)
     vv = np.ascontiguousarray(val, np.float64)
     dY = np.zeros_like(Y)
-    check(lib().sharp_tsne_gradient(rp.ctypes.data_as(C.POINTER(C.c_longlong)), cc.ctypes.data_as(C.POINTER(C.c_int)), _dp(vv),
-                                    C.c_longlong(n), dims, _dp(Y), _dp(dY)))
+    check(lib().sharp_tsne_gradient(i64(rp), i32(cc), f64(vv), n, dims, f64(Y), f64(dY)))
     return dY
 
 
@@ -297,6 +274,5 @@ def _gradient_bh(row_ptr, col, val, Y, theta=0.5):
     vv = np.ascontiguousarray(val, np.float64)
     dY = np.zeros_like(Y)
     Z = C.c_double()
-    check(lib().sharp_tsne_gradient_bh(rp.ctypes.data_as(C.POINTER(C.c_longlong)), cc.ctypes.data_as(C.POINTER(C.c_int)), _dp(vv),
-                                       C.c_longlong(n), dims, _dp(Y), C.c_double(theta), _dp(dY), C.byref(Z)))
+    check(lib().sharp_tsne_gradient_bh(i64(rp), i32(cc), f64(vv), n, dims, f64(Y), theta, f64(dY), C.byref(Z)))
     return dY, Z.value

@@ -11,8 +11,8 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import SharpError, check, lib
-from .api import _dense, _dp, _ip
+from ._lib import SharpError, check, f64, i32, lib
+from .api import _dense
 from .tree import _dist_code
 
 __all__ = ["cutree", "silhouette", "calinski_harabasz"]
@@ -49,7 +49,7 @@ def cutree(tree, k=None, h=None):
     kv = np.ascontiguousarray(kv, np.int32)
     mcol = np.ascontiguousarray(merge.T, np.int32)                                  # (n - 1) x 2 column-major, as sharp_hclust writes it
     out = np.zeros((kv.size, n), np.int32)
-    check(lib().sharp_cutree(_ip(mcol), n, _ip(kv), int(kv.size), _ip(out)))       # (no device context needed)
+    check(lib().sharp_cutree(i32(mcol), n, i32(kv), int(kv.size), i32(out)))       # (no device context needed)
     return out[0].copy() if scalar else np.ascontiguousarray(out.T)
 
 
@@ -111,10 +111,9 @@ def silhouette(x, d=None, data=None, distance="euclidean", p=2):
     neighbor = np.zeros(n, np.int32)
     width = np.zeros(n, np.float64)
     if d is not None:
-        check(lib().sharp_silhouette_dist(_dp(dv), n, _ip(cl), k, _ip(neighbor), _dp(width)))
+        check(lib().sharp_silhouette_dist(f64(dv), n, i32(cl), k, i32(neighbor), f64(width)))
     else:
-        check(lib().sharp_silhouette(_dp(a), C.c_longlong(n), a.shape[1], C.c_longlong(a.shape[1]), code, C.c_double(float(p)), _ip(cl), k,
-                                     _ip(neighbor), _dp(width)))
+        check(lib().sharp_silhouette(f64(a), n, a.shape[1], a.shape[1], code, float(p), i32(cl), k, i32(neighbor), f64(width)))
     sizes = np.bincount(cl - 1, minlength=k)
     return {"cluster": levels[cl - 1], "neighbor": levels[neighbor - 1], "sil_width": width, "clusters": levels, "clus_sizes": sizes,
             "clus_avg_widths": np.bincount(cl - 1, weights=width, minlength=k) / sizes, "avg_width": float(width.mean())}
@@ -141,6 +140,5 @@ def calinski_harabasz(data, labels, distance="euclidean"):
         raise SharpError("calinski_harabasz: the number of clusters must be between 2 and n - 1")
     _lib.ensure_init()
     out = C.c_double()
-    check(lib().sharp_calinski_harabasz(_dp(a), C.c_longlong(n), a.shape[1], C.c_longlong(a.shape[1]), _ip(cl), k, kinds[distance],
-                                        C.byref(out)))
+    check(lib().sharp_calinski_harabasz(f64(a), n, a.shape[1], a.shape[1], i32(cl), k, kinds[distance], C.byref(out)))
     return out.value
