@@ -420,6 +420,35 @@ int sharp_tsne_knn_dist(const double *d, int n, int K, int *idx, double *dist2);
 int sharp_tsne_affinities_nn(const int *index, const double *distance, long long n, int K, int squared, double perplexity, long long cap,
                              long long *row_ptr, int *col, double *val, long long *nnz);
 
+/* ---- UMAP beside t-SNE (uwot::umap's arguments; DESIGN.md §13 is the specification: this project's, modelled on umap-learn's algorithm
+ * and uwot's batch = TRUE mode, with no bit parity claimed).  Euclidean metric, set_op_mix_ratio = local_connectivity = bandwidth = 1.
+ * sharp_umap_ab: a, b minimising sum (1 / (1 + a x^(2b)) - y(x))^2 over x = linspace(0, 3 spread, 300), y = 1 below min_dist, else
+ * exp(-(x - min_dist) / spread); a host Levenberg-Marquardt in fp64, NO device needed.  spread > 0, 0 <= min_dist < 3 spread, finite.
+ * sharp_umap: X n rows of d values (leading dimension ld, finite); n_neighbors in 2 .. 256 and <= n - 1 (it counts the point itself:
+ * the lists hold K = n_neighbors - 1 others); dims 1 .. 3; n_epochs < 0: 500 if n <= 10000 else 200; ab: two doubles, in and out --
+ * both positive: used as given, else fitted from (spread, min_dist) and written back; negative_sample_rate 0 .. 64; init: 0 the first
+ * dims principal components of the prepared input, 1 runif(-10, 10) from R's set.seed(seed) stream (row by row), 2 Y_init (n x dims);
+ * in every case each coordinate is then mapped affinely onto [0, 10].  pca: 0, or that many components through sharp_tsne_prepare's PCA
+ * (centred when pca_center) before the k-NN.  Y: n x dims.  nn_index / nn_distance: both NULL, or n x (n_neighbors - 1) buffers that
+ * receive the k-NN lists (0-based, Euclidean distances, sorted by (distance, index)).  Two calls with the same input and seed give
+ * bitwise-identical Y on the same GPU.
+ * sharp_umap_neighbors: the same from lists the caller has (index / distance n x K row-major, 0-based, n_neighbors = K + 1; squared =
+ * 1: squared distances, as sharp_tsne_knn returns them), validated as sharp_tsne_neighbors validates them; init 1 or 2 only.
+ * Stages: sharp_umap_graph: lists -> the fuzzy graph W = A + A^T - A o A^T as a CSR with rows sorted by column (cap >= 2 n K always
+ * suffices), rho and sigma (n each).  sharp_umap_epochs: epochs [ep0, ep1) of n_epochs on Y (n x dims, in and out) for a CSR whose
+ * mirrored entries carry equal weights; the schedule is stateless, so [0, e) then [e, n_epochs) gives the bits of [0, n_epochs). */
+int sharp_umap_ab(double spread, double min_dist, double *a, double *b);
+int sharp_umap(const double *X, long long n, int d, long long ld, int n_neighbors, int dims, int n_epochs, double learning_rate, double min_dist,
+               double spread, double *ab, int negative_sample_rate, double repulsion_strength, int init, const double *Y_init, int pca,
+               int pca_center, double seed, double *Y, int *nn_index, double *nn_distance);
+int sharp_umap_neighbors(const int *index, const double *distance, long long n, int K, int squared, int dims, int n_epochs, double learning_rate,
+                         double min_dist, double spread, double *ab, int negative_sample_rate, double repulsion_strength, int init,
+                         const double *Y_init, double seed, double *Y);
+int sharp_umap_graph(const int *index, const double *distance, long long n, int K, int squared, long long cap, long long *row_ptr, int *col,
+                     double *val, long long *nnz, double *rho, double *sigma);
+int sharp_umap_epochs(const long long *row_ptr, const int *col, const double *val, long long n, int dims, double *Y, int n_epochs, int ep0,
+                      int ep1, double learning_rate, double a, double b, int negative_sample_rate, double repulsion_strength, double seed);
+
 /* ---- dist / hclust as a tree: what pheatmap(cluster_rows = T, cluster_cols = T, clustering_method = "ward.D") computes inside
  * plot_markers (R/plot_markers.R:214-237), i.e. hclust(dist(sm), "ward.D") over the marker genes and hclust(dist(t(sm)), "ward.D") over up
  * to ~10 000 cells (:136-143).  DESIGN.md §11.
@@ -573,6 +602,16 @@ void sharp_C_tsne_bh(double *X, double *n, int *d, int *dims, int *initial_dims,
                      int *check_duplicates, double *perplexity, double *theta, int *max_iter, int *stop_lying_iter, int *mom_switch_iter,
                      double *momentum, double *final_momentum, double *eta, double *exaggeration, int *has_Y_init, double *Y_init, double *seed,
                      double *Y, double *itercosts, double *costs, int *status);
+/* sharp_umap / sharp_umap_neighbors / sharp_umap_ab in the same convention: X = as.double(t(X)), n as double, index 0-based; ab: a
+ * numeric(2), c(0, 0) to have it fitted; Y_init is read with init = 2 only (else a buffer of length >= 1); want_nn = 0: nn_index / nn_distance
+ * are buffers of length >= 1 that are left alone */
+void sharp_C_umap(double *X, double *n, int *d, int *n_neighbors, int *dims, int *n_epochs, double *learning_rate, double *min_dist,
+                  double *spread, double *ab, int *negative_sample_rate, double *repulsion_strength, int *init, double *Y_init, int *pca,
+                  int *pca_center, double *seed, double *Y, int *want_nn, int *nn_index, double *nn_distance, int *status);
+void sharp_C_umap_neighbors(int *index, double *distance, double *n, int *K, int *squared, int *dims, int *n_epochs, double *learning_rate,
+                            double *min_dist, double *spread, double *ab, int *negative_sample_rate, double *repulsion_strength, int *init,
+                            double *Y_init, double *seed, double *Y, int *status);
+void sharp_C_umap_ab(double *spread, double *min_dist, double *a, double *b, int *status);
 /* stats::dist / stats::hclust for pheatmap inside plot_markers (R/plot_markers.R:214-237): x = as.double(t(x)) (rows of p values) */
 void sharp_C_dist(double *x, int *n, int *p, int *method, double *minkowski_p, double *d_out, int *status);
 void sharp_C_hclust_dist(double *d, int *n, int *hmethod, int *merge, double *height, int *order, int *status);

@@ -398,6 +398,76 @@ sharp_knn <- function(X, K, squared = FALSE) {
     list(index = matrix(r$idx, n, K, byrow = TRUE) + 1L, distance = if (squared) d2 else sqrt(d2))
 }
 
+# ---- uwot::umap beside Rtsne (DESIGN.md 13) -------------------------------------------------------------------------------------------------
+# uwot's argument names and defaults; the algorithm is this project's specification (modelled on umap-learn's and on uwot's batch = TRUE
+# mode; no bit parity with either).  Only metric = "euclidean" and set_op_mix_ratio = local_connectivity = bandwidth = 1 are built.
+# n_threads, n_sgd_threads, verbose and batch are accepted and ignored.  Returns the n x n_components matrix, or with ret_nn = TRUE
+# list(embedding =, nn = list(euclidean = list(idx = n x n_neighbors, dist =))) in uwot's layout (column 1 is the point itself).
+.sharp_umap_refuse <- function(metric, set_op_mix_ratio, local_connectivity, bandwidth) {
+    if (!identical(metric, "euclidean")) stop("umap: metric '", metric, "' is not supported (only \"euclidean\")")
+    if (set_op_mix_ratio != 1) stop("umap: set_op_mix_ratio other than 1 is not supported")
+    if (local_connectivity != 1) stop("umap: local_connectivity other than 1 is not supported")
+    if (bandwidth != 1) stop("umap: bandwidth other than 1 is not supported")
+}
+.sharp_umap_init <- function(init, n, dims, allow_pca) {
+    if (is.character(init)) {
+        code <- match(init, c("pca", "random")) - 1L
+        if (is.na(code)) stop("umap: init must be \"pca\", \"random\" or an n x n_components matrix")
+        if (code == 0L && !allow_pca) stop("umap_neighbors: init = \"pca\" needs the data; give \"random\" or a matrix")
+        return(list(code = code, Y = double(1)))
+    }
+    init <- .sharp_dmat(init)
+    if (!all(dim(init) == c(n, dims))) stop("umap: init must be \"pca\", \"random\" or an n x n_components matrix")
+    list(code = 2L, Y = as.double(t(init)))
+}
+sharp_umap_ab <- function(spread = 1, min_dist = 0.01) {
+    r <- .C("sharp_C_umap_ab", as.double(spread), as.double(min_dist), a = double(1), b = double(1), status = integer(1))
+    .sharp_check(r$status)
+    c(a = r$a, b = r$b)
+}
+sharp_umap <- function(X, n_neighbors = 15, n_components = 2, metric = "euclidean", n_epochs = NULL, learning_rate = 1, init = "pca",
+                       spread = 1, min_dist = 0.01, set_op_mix_ratio = 1, local_connectivity = 1, bandwidth = 1, repulsion_strength = 1,
+                       negative_sample_rate = 5, a = NULL, b = NULL, pca = NULL, pca_center = TRUE, seed = 10, ret_nn = FALSE,
+                       n_threads = NULL, n_sgd_threads = 0, verbose = FALSE, batch = TRUE, ...) {
+    .sharp_umap_refuse(metric, set_op_mix_ratio, local_connectivity, bandwidth)
+    X <- .sharp_dmat(X)
+    n <- nrow(X); dims <- as.integer(n_components); K <- as.integer(n_neighbors) - 1L
+    if (is.null(a) != is.null(b)) stop("umap: give both a and b, or neither")
+    ini <- .sharp_umap_init(init, n, dims, TRUE)
+    r <- .C("sharp_C_umap", as.double(t(X)), as.double(n), ncol(X), as.integer(n_neighbors), dims,
+            as.integer(if (is.null(n_epochs)) -1L else n_epochs), as.double(learning_rate), as.double(min_dist), as.double(spread),
+            ab = as.double(if (is.null(a)) c(0, 0) else c(a, b)), as.integer(negative_sample_rate), as.double(repulsion_strength), ini$code,
+            ini$Y, as.integer(if (is.null(pca)) 0L else pca), as.integer(pca_center), as.double(seed), Y = double(n * dims),
+            as.integer(ret_nn), idx = integer(if (ret_nn) n * K else 1L), dist = double(if (ret_nn) n * K else 1L), status = integer(1))
+    .sharp_check(r$status)
+    Y <- matrix(r$Y, n, dims, byrow = TRUE)
+    if (!ret_nn) return(Y)
+    list(embedding = Y, nn = list(euclidean = list(idx = cbind(seq_len(n), matrix(r$idx, n, K, byrow = TRUE) + 1L),
+                                                   dist = cbind(0, matrix(r$dist, n, K, byrow = TRUE)))))
+}
+# umap from neighbour lists the caller has: index n x K, 1-BASED, self excluded (what sharp_knn returns); distance their Euclidean
+# distances, or squares with squared = TRUE.  n_neighbors is K + 1.  init: "random" or a matrix.
+sharp_umap_neighbors <- function(index, distance, squared = FALSE, n_components = 2, n_epochs = NULL, learning_rate = 1, init = "random",
+                                 spread = 1, min_dist = 0.01, repulsion_strength = 1, negative_sample_rate = 5, a = NULL, b = NULL,
+                                 seed = 10, metric = "euclidean", set_op_mix_ratio = 1, local_connectivity = 1, bandwidth = 1, ...) {
+    .sharp_umap_refuse(metric, set_op_mix_ratio, local_connectivity, bandwidth)
+    distance <- .sharp_dmat(distance)
+    index <- as.matrix(index)
+    if (!all(dim(index) == dim(distance))) stop("umap_neighbors: index and distance differ in shape")
+    storage.mode(index) <- "integer"
+    n <- nrow(distance); K <- ncol(distance); dims <- as.integer(n_components)
+    if (is.null(a) != is.null(b)) stop("umap: give both a and b, or neither")
+    ini <- .sharp_umap_init(init, n, dims, FALSE)
+    i0 <- as.integer(t(index)) - 1L
+    i0[is.na(i0)] <- -1L                                        # an NA index is out of range: the library names its row
+    r <- .C("sharp_C_umap_neighbors", i0, as.double(t(distance)), as.double(n), as.integer(K), as.integer(squared), dims,
+            as.integer(if (is.null(n_epochs)) -1L else n_epochs), as.double(learning_rate), as.double(min_dist), as.double(spread),
+            ab = as.double(if (is.null(a)) c(0, 0) else c(a, b)), as.integer(negative_sample_rate), as.double(repulsion_strength), ini$code,
+            ini$Y, as.double(seed), Y = double(n * dims), status = integer(1), NAOK = TRUE)
+    .sharp_check(r$status)
+    matrix(r$Y, n, dims, byrow = TRUE)
+}
+
 # ---- dist / hclust / plot_markers (R/plot_markers.R:38-242; DESIGN.md 11) ----------------------------------------------------------------
 # pheatmap(cluster_rows = T, cluster_cols = T, clustering_method = "ward.D") at R/plot_markers.R:214-237 computes hclust(dist(sm), "ward.D")
 # over the marker genes and hclust(dist(t(sm)), "ward.D") over up to ~10 000 cells.  sharp_dist / sharp_hclust do that on the GPU;

@@ -979,8 +979,79 @@ def _draw_sharp_map(Y, label, filename, filetype, legendtitle="Cell Type", width
 _PREPARE_ARGS = ("pca", "initial_dims", "pca_center", "pca_scale", "normalize")
 
 
+def _vis_neighbors_n(y, neighbors, w):
+    """the number of cells of the result y, after checking that the neighbors dict of an earlier call belongs to it and to w"""
+    for key in ("index", "distance", "squared", "w", "n"):
+        if key not in neighbors:
+            raise SharpError(f"visualization_SHARP: neighbors holds no \"{key}\" (pass what return_neighbors=True returned)")
+    src = y.get("viE") if y.get("viE") is not None else y.get("x0")
+    if src is None:
+        raise SharpError("visualization_SHARP: the result holds no x0 / viE (run SHARP with forview = TRUE)")
+    n = src.shape[0]
+    if neighbors["n"] != n or np.asarray(neighbors["index"]).shape[0] != n:
+        raise SharpError(f"visualization_SHARP: neighbors were computed for {neighbors['n']} cells, this result holds {n}")
+    if neighbors["w"] != w:
+        raise SharpError(f"visualization_SHARP: neighbors were computed with w = {neighbors['w']}, this call has w = {w}")
+    return n
+
+
+def _vis_umap(y, label, w, filename, filetype, legendtitle, width, height, res, plot, neighbors, return_neighbors, kwargs):
+    """visualization_SHARP(method="umap"): x1 prepared as for Rtsne, then umap() on it, or umap_neighbors() on the first
+    n_neighbors - 1 columns of given lists; the start is the PCA of the prepared x1 either way unless init says otherwise"""
+    import time as _t
+
+    from .tsne import _prepare
+    from .umap import umap, umap_neighbors
+
+    t0 = _t.time()
+    kw = dict(kwargs)
+    kw.setdefault("seed", 10)
+    pca = kw.pop("pca", None)
+    pca_center = kw.pop("pca_center", True)
+    dims = int(kw.get("n_components", 2))
+    if dims not in (1, 2, 3):
+        raise SharpError("umap: n_components must be 1, 2 or 3")
+    n_neighbors = int(kw.pop("n_neighbors", 15))
+    pca_start = isinstance(kw.get("init", "pca"), str) and kw.get("init", "pca") == "pca"
+    n = _vis_neighbors_n(y, neighbors, w) if neighbors is not None else None
+    xp = None
+    if neighbors is None or pca_start:                               # (given lists and a given start need no x1 at all)
+        x1 = _vis_input(y, w)
+        n = x1.shape[0]
+        prep = {"pca": x1.shape[1] > 50} if pca is None else {"pca": True, "initial_dims": int(pca)}
+        xp = _prepare(x1, pca_center=pca_center, **prep)
+    if filetype is None:
+        filetype = "pdf" if n < 5000 else "png"
+    if filename is None:
+        filename = f"vi_SHARP.{filetype}"
+    if pca_start:
+        if xp.shape[1] < dims:
+            raise SharpError("umap: init = \"pca\" needs at least n_components columns")
+        kw["init"] = _prepare(xp, pca=True, initial_dims=dims, pca_center=True, pca_scale=False, normalize=False)
+    nb = None
+    if neighbors is None:
+        out = umap(xp, n_neighbors=n_neighbors, ret_nn=return_neighbors, **kw)
+        if return_neighbors:
+            nb = {"index": out["nn"]["index"], "distance": out["nn"]["distance"], "squared": False, "w": w, "n": n}
+    else:
+        nb = neighbors
+        idx, dd = np.asarray(nb["index"]), np.asarray(nb["distance"])
+        K = n_neighbors - 1
+        if idx.ndim != 2 or K > idx.shape[1] or K < 1:
+            raise SharpError(f"visualization_SHARP: n_neighbors {n_neighbors} needs {K} neighbours per row, neighbors holds "
+                             f"{idx.shape[1] if idx.ndim == 2 else 0}")
+        out = umap_neighbors(idx[:, :K], dd[:, :K], squared=bool(nb["squared"]), **kw)
+    if plot:
+        _draw_sharp_map(out["Y"], label, filename, filetype, legendtitle, width, height, res)
+    r = {"Y": out["Y"], "a": out["a"], "b": out["b"], "n_epochs": out["n_epochs"], "filename": filename if plot else None,
+         "time": (_t.time() - t0) / 60.0}
+    if return_neighbors:
+        r["neighbors"] = nb
+    return r
+
+
 def visualization_SHARP(y, label=None, w=2, filename=None, filetype=None, n_cores=None, legendtitle="Cell Type", width=9.5, height=8.5,
-                        res=400, plot=True, neighbors=None, return_neighbors=False, **tsne_kwargs):
+                        res=400, plot=True, neighbors=None, return_neighbors=False, method="tsne", **tsne_kwargs):
     """R/visualization_SHARP.R:31-177: the 2-D t-SNE map of a SHARP() / SHARP_unlimited() result.
 
     x1 = cbind(w * scale(x0), scale(viE)) (w >= 100: x0 with jitter; w <= 0.01: viE alone) goes to Rtsne(x1, check_duplicates = FALSE,
@@ -994,28 +1065,27 @@ def visualization_SHARP(y, label=None, w=2, filename=None, filetype=None, n_core
     neither seed, theta, dims, max_iter nor the optimiser's settings.  A later call for another map of the same result passes that dict
     as neighbors= and skips the preparation and the k-NN, the only O(n^2 d) stage; its perplexity may be anything up to a third of the
     lists' width (the lists are sorted, so their first floor(3 perplexity) columns are what Rtsne would compute).  A dict whose n or w
-    does not match the call is refused; the preparation's arguments (pca, initial_dims, ...) are then unused."""
+    does not match the call is refused; the preparation's arguments (pca, initial_dims, ...) are then unused.
+
+    method="umap" draws the same figure from sharp_amd.umap.umap instead (the keyword arguments are then umap's): the same x1, prepared
+    as for Rtsne (pca = 50 when ncol(x1) > 50), "Y", "a", "b" and "n_epochs" in the result, no "itercosts".  neighbors= /
+    return_neighbors= work alike, and the lists do not depend on the method: those a t-SNE call returned serve a UMAP map (their first
+    n_neighbors - 1 columns) and the other way round, as far as they are wide enough."""
     import time as _t
 
     from .tsne import Rtsne, Rtsne_neighbors, _knn, _prepare
 
+    if method == "umap":
+        return _vis_umap(y, label, w, filename, filetype, legendtitle, width, height, res, plot, neighbors, return_neighbors, tsne_kwargs)
+    if method != "tsne":
+        raise SharpError(f"visualization_SHARP: method must be \"tsne\" or \"umap\", not {method!r}")
     t0 = _t.time()
     kw = dict(tsne_kwargs)
     if neighbors is None:
         x1 = _vis_input(y, w)
         n = x1.shape[0]
     else:
-        for key in ("index", "distance", "squared", "w", "n"):
-            if key not in neighbors:
-                raise SharpError(f"visualization_SHARP: neighbors holds no \"{key}\" (pass what return_neighbors=True returned)")
-        src = y.get("viE") if y.get("viE") is not None else y.get("x0")
-        if src is None:
-            raise SharpError("visualization_SHARP: the result holds no x0 / viE (run SHARP with forview = TRUE)")
-        n = src.shape[0]
-        if neighbors["n"] != n or np.asarray(neighbors["index"]).shape[0] != n:
-            raise SharpError(f"visualization_SHARP: neighbors were computed for {neighbors['n']} cells, this result holds {n}")
-        if neighbors["w"] != w:
-            raise SharpError(f"visualization_SHARP: neighbors were computed with w = {neighbors['w']}, this call has w = {w}")
+        n = _vis_neighbors_n(y, neighbors, w)
     if filetype is None:
         filetype = "pdf" if n < 5000 else "png"
     if filename is None:

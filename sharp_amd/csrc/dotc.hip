@@ -264,6 +264,22 @@ void sharp_C_tsne_knn(double *X, double *n, int *d, int *K, int *idx, double *di
     *status = sharp_tsne_knn(X, as_ll(n), *d, static_cast<long long>(*d), *K, idx, dist);
 }
 
+/* ---- uwot::umap beside Rtsne (sharp_umap, sharp_umap_neighbors, sharp_umap_ab): X = as.double(t(X)); index 0-based, n x K row-major */
+void sharp_C_umap(double *X, double *n, int *d, int *n_neighbors, int *dims, int *n_epochs, double *learning_rate, double *min_dist,
+                  double *spread, double *ab, int *negative_sample_rate, double *repulsion_strength, int *init, double *Y_init, int *pca,
+                  int *pca_center, double *seed, double *Y, int *want_nn, int *nn_index, double *nn_distance, int *status) {
+    *status = sharp_umap(X, as_ll(n), *d, static_cast<long long>(*d), *n_neighbors, *dims, *n_epochs, *learning_rate, *min_dist, *spread, ab,
+                         *negative_sample_rate, *repulsion_strength, *init, *init == 2 ? Y_init : nullptr, *pca, *pca_center, *seed, Y,
+                         *want_nn ? nn_index : nullptr, *want_nn ? nn_distance : nullptr);
+}
+void sharp_C_umap_neighbors(int *index, double *distance, double *n, int *K, int *squared, int *dims, int *n_epochs, double *learning_rate,
+                            double *min_dist, double *spread, double *ab, int *negative_sample_rate, double *repulsion_strength, int *init,
+                            double *Y_init, double *seed, double *Y, int *status) {
+    *status = sharp_umap_neighbors(index, distance, as_ll(n), *K, *squared, *dims, *n_epochs, *learning_rate, *min_dist, *spread, ab,
+                                   *negative_sample_rate, *repulsion_strength, *init, *init == 2 ? Y_init : nullptr, *seed, Y);
+}
+void sharp_C_umap_ab(double *spread, double *min_dist, double *a, double *b, int *status) { *status = sharp_umap_ab(*spread, *min_dist, a, b); }
+
 /* ---- dist / hclust (the clustering pheatmap does inside plot_markers, R/plot_markers.R:214-237): x = as.double(t(x)) */
 void sharp_C_dist(double *x, int *n, int *p, int *method, double *minkowski_p, double *d_out, int *status) {
     *status = sharp_dist(x, *n, *p, static_cast<long long>(*p), *method, *minkowski_p, d_out);
