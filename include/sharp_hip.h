@@ -449,6 +449,32 @@ int sharp_umap_graph(const int *index, const double *distance, long long n, int 
 int sharp_umap_epochs(const long long *row_ptr, const int *col, const double *val, long long n, int dims, double *Y, int n_epochs, int ep0,
                       int ep1, double learning_rate, double a, double b, int negative_sample_rate, double repulsion_strength, double seed);
 
+/* ---- umap_transform: new rows placed in a fitted UMAP map (DESIGN.md §14 is the specification: this project's, modelled on umap-learn's
+ * transform and uwot's umap_transform, with no bit parity claimed).
+ * sharp_umap_model_create: a device-resident model of the calling context: X_ref n_ref rows of d values (leading dimension ld,
+ * finite, squared norms that do not overflow), Y_ref n_ref x dims (dims 1 .. 3, finite) its fitted map, n_neighbors in 1 .. 255 and
+ * <= n_ref (the K of a transform's lists), a, b > 0 the curve, n_epochs >= 0 the fit's epochs.  *handle receives the model;
+ * sharp_umap_model_free releases it, sharp_shutdown releases what is left.  A handle is refused in any other context and once freed.
+ * sharp_umap_transform: Xq nq rows of the model's d values (leading dimension ld) -> Yq nq x dims.  n_epochs < 0: a third of the
+ * fit's (rounded down); 0 returns the start (the weighted mean of the neighbours' positions).  negative_sample_rate 0 .. 64.
+ * row_offset >= 0 numbers the rows for the negative-sample draw: a long table transformed block by block with each block's first row
+ * as row_offset gives the bits of one call.  nn_index / nn_distance: both NULL, or nq x n_neighbors buffers that receive the lists
+ * (0-based into the reference, Euclidean, sorted by (distance, index)).  A row's result depends on that row, the model, the arguments
+ * and row_offset + its number alone; two calls give bitwise-identical results on the same GPU.
+ * Stages: sharp_knn_cross: the K nearest reference rows of every query row (any K in 1 .. 255, <= n_ref; max_rows_per_launch 0: the
+ * library's choice, else the rows of one launch, rounded down to a multiple of 16, at least 16 -- the lists do not depend on it).
+ * sharp_umap_transform_weights: lists -> sigma (nq), w (nq x K) and the start Y0 (nq x dims).  sharp_umap_transform_epochs: epochs
+ * [ep0, ep1) of n_epochs on Yq (in and out); [0, e) then [e, n_epochs) gives the bits of [0, n_epochs). */
+int sharp_umap_model_create(const double *X_ref, long long n_ref, int d, long long ld, const double *Y_ref, int dims, int n_neighbors, double a,
+                            double b, int n_epochs, int *handle);
+int sharp_umap_model_free(int handle);
+int sharp_umap_transform(int handle, const double *Xq, long long nq, long long ld, int n_epochs, double learning_rate, int negative_sample_rate,
+                         double repulsion_strength, double seed, long long row_offset, double *Yq, int *nn_index, double *nn_distance);
+int sharp_knn_cross(int handle, const double *Xq, long long nq, long long ld, int K, int max_rows_per_launch, int *idx, double *dist);
+int sharp_umap_transform_weights(int handle, const int *idx, const double *dist, long long nq, int K, double *sigma, double *w, double *Y0);
+int sharp_umap_transform_epochs(int handle, const int *idx, const double *w, long long nq, int K, double *Yq, int n_epochs, int ep0, int ep1,
+                                double learning_rate, int negative_sample_rate, double repulsion_strength, double seed, long long row_offset);
+
 /* ---- dist / hclust as a tree: what pheatmap(cluster_rows = T, cluster_cols = T, clustering_method = "ward.D") computes inside
  * plot_markers (R/plot_markers.R:214-237), i.e. hclust(dist(sm), "ward.D") over the marker genes and hclust(dist(t(sm)), "ward.D") over up
  * to ~10 000 cells (:136-143).  DESIGN.md §11.
@@ -612,6 +638,14 @@ void sharp_C_umap_neighbors(int *index, double *distance, double *n, int *K, int
                             double *min_dist, double *spread, double *ab, int *negative_sample_rate, double *repulsion_strength, int *init,
                             double *Y_init, double *seed, double *Y, int *status);
 void sharp_C_umap_ab(double *spread, double *min_dist, double *a, double *b, int *status);
+/* sharp_umap_model_create / _free / sharp_umap_transform in the same convention: X_ref / Xq = as.double(t(X)) (rows of d values), n_ref,
+ * nq and row_offset as double; want_nn = 0: nn_index / nn_distance are buffers of length >= 1 that are left alone */
+void sharp_C_umap_model_create(double *X_ref, double *n_ref, int *d, double *Y_ref, int *dims, int *n_neighbors, double *a, double *b,
+                               int *n_epochs, int *handle, int *status);
+void sharp_C_umap_model_free(int *handle, int *status);
+void sharp_C_umap_transform(int *handle, double *Xq, double *nq, int *d, int *n_epochs, double *learning_rate, int *negative_sample_rate,
+                            double *repulsion_strength, double *seed, double *row_offset, double *Yq, int *want_nn, int *nn_index,
+                            double *nn_distance, int *status);
 /* stats::dist / stats::hclust for pheatmap inside plot_markers (R/plot_markers.R:214-237): x = as.double(t(x)) (rows of p values) */
 void sharp_C_dist(double *x, int *n, int *p, int *method, double *minkowski_p, double *d_out, int *status);
 void sharp_C_hclust_dist(double *d, int *n, int *hmethod, int *merge, double *height, int *order, int *status);

@@ -468,6 +468,47 @@ sharp_umap_neighbors <- function(index, distance, squared = FALSE, n_components 
     matrix(r$Y, n, dims, byrow = TRUE)
 }
 
+# ---- uwot::umap_transform: new rows placed in a fitted map (DESIGN.md 14) -----------------------------------------------------------------
+# sharp_umap_model(X, embedding, ...) keeps the reference rows and their map on the device and returns a handle (class "sharp_umap_model");
+# n_neighbors (1 .. 255, <= nrow(X)) counts the reference rows a new row is placed by; a, b: the fit's curve (sharp_umap_ab), n_epochs the
+# fit's epochs.  sharp_umap_transform(X_new, model) returns the nrow(X_new) x n_components matrix, or with ret_nn = TRUE
+# list(embedding =, nn = list(euclidean = list(idx =, dist =))) with 1-BASED indices into the reference.  n_epochs NULL: a third of the
+# fit's; row_offset: the number of the block's first row (0-based) when a long table is transformed block by block, which then gives the
+# bits of one call.  sharp_umap_model_free(model) releases the handle (sharp_shutdown releases what is left).
+sharp_umap_model <- function(X, embedding, n_neighbors = 15, a = NULL, b = NULL, n_epochs = 500, spread = 1, min_dist = 0.01) {
+    X <- .sharp_dmat(X)
+    embedding <- .sharp_dmat(embedding)
+    if (nrow(embedding) != nrow(X)) stop("umap_model: embedding must have one row per row of X")
+    if (is.null(a) != is.null(b)) stop("umap_model: give both a and b, or neither")
+    ab <- if (is.null(a)) sharp_umap_ab(spread, min_dist) else c(a = a, b = b)
+    r <- .C("sharp_C_umap_model_create", as.double(t(X)), as.double(nrow(X)), ncol(X), as.double(t(embedding)), ncol(embedding),
+            as.integer(n_neighbors), as.double(ab[["a"]]), as.double(ab[["b"]]), as.integer(n_epochs), handle = integer(1),
+            status = integer(1))
+    .sharp_check(r$status)
+    structure(list(handle = r$handle, n_ref = nrow(X), d = ncol(X), n_components = ncol(embedding), n_neighbors = as.integer(n_neighbors),
+                   a = ab[["a"]], b = ab[["b"]], n_epochs = as.integer(n_epochs)), class = "sharp_umap_model")
+}
+sharp_umap_model_free <- function(model) {
+    r <- .C("sharp_C_umap_model_free", as.integer(model$handle), status = integer(1))
+    .sharp_check(r$status)
+    invisible(NULL)
+}
+sharp_umap_transform <- function(X_new, model, n_epochs = NULL, learning_rate = 1, negative_sample_rate = 5, repulsion_strength = 1,
+                                 seed = 10, row_offset = 0, ret_nn = FALSE, ...) {
+    if (!inherits(model, "sharp_umap_model")) stop("umap_transform: model must come from sharp_umap_model")
+    X_new <- .sharp_dmat(X_new)
+    if (ncol(X_new) != model$d) stop("umap_transform: X_new must have the model's ", model$d, " columns")
+    n <- nrow(X_new); dims <- model$n_components; K <- model$n_neighbors
+    r <- .C("sharp_C_umap_transform", as.integer(model$handle), as.double(t(X_new)), as.double(n), as.integer(model$d),
+            as.integer(if (is.null(n_epochs)) -1L else n_epochs), as.double(learning_rate), as.integer(negative_sample_rate),
+            as.double(repulsion_strength), as.double(seed), as.double(row_offset), Y = double(n * dims), as.integer(ret_nn),
+            idx = integer(if (ret_nn) n * K else 1L), dist = double(if (ret_nn) n * K else 1L), status = integer(1))
+    .sharp_check(r$status)
+    Y <- matrix(r$Y, n, dims, byrow = TRUE)
+    if (!ret_nn) return(Y)
+    list(embedding = Y, nn = list(euclidean = list(idx = matrix(r$idx, n, K, byrow = TRUE) + 1L, dist = matrix(r$dist, n, K, byrow = TRUE))))
+}
+
 # ---- dist / hclust / plot_markers (R/plot_markers.R:38-242; DESIGN.md 11) ----------------------------------------------------------------
 # pheatmap(cluster_rows = T, cluster_cols = T, clustering_method = "ward.D") at R/plot_markers.R:214-237 computes hclust(dist(sm), "ward.D")
 # over the marker genes and hclust(dist(t(sm)), "ward.D") over up to ~10 000 cells.  sharp_dist / sharp_hclust do that on the GPU;

@@ -265,6 +265,8 @@ struct StreamScope {
 // driver.hip: the side streams of the block pipeline (next block's front, ensemble mean) and the front prepared for the next call
 void drain_side_streams();
 void drop_pending_front();
+// umap_transform.hip: frees the UMAP models that a slot's context made (sharp_shutdown)
+void umap_models_drop_slot(int slot);
 
 inline void stream_sync() { SHARP_HIP_CHECK(hipStreamSynchronize(ctx().stream)); }
 

@@ -279,6 +279,19 @@ void sharp_C_umap_neighbors(int *index, double *distance, double *n, int *K, int
                                    *negative_sample_rate, *repulsion_strength, *init, *init == 2 ? Y_init : nullptr, *seed, Y);
 }
 void sharp_C_umap_ab(double *spread, double *min_dist, double *a, double *b, int *status) { *status = sharp_umap_ab(*spread, *min_dist, a, b); }
+/* umap_transform (sharp_umap_model_create, sharp_umap_model_free, sharp_umap_transform): X_ref / Xq = as.double(t(X)) */
+void sharp_C_umap_model_create(double *X_ref, double *n_ref, int *d, double *Y_ref, int *dims, int *n_neighbors, double *a, double *b,
+                               int *n_epochs, int *handle, int *status) {
+    *status = sharp_umap_model_create(X_ref, as_ll(n_ref), *d, static_cast<long long>(*d), Y_ref, *dims, *n_neighbors, *a, *b, *n_epochs, handle);
+}
+void sharp_C_umap_model_free(int *handle, int *status) { *status = sharp_umap_model_free(*handle); }
+void sharp_C_umap_transform(int *handle, double *Xq, double *nq, int *d, int *n_epochs, double *learning_rate, int *negative_sample_rate,
+                            double *repulsion_strength, double *seed, double *row_offset, double *Yq, int *want_nn, int *nn_index,
+                            double *nn_distance, int *status) {
+    *status = sharp_umap_transform(*handle, Xq, as_ll(nq), static_cast<long long>(*d), *n_epochs, *learning_rate, *negative_sample_rate,
+                                   *repulsion_strength, *seed, as_ll(row_offset), Yq, *want_nn ? nn_index : nullptr,
+                                   *want_nn ? nn_distance : nullptr);
+}
 
 /* ---- dist / hclust (the clustering pheatmap does inside plot_markers, R/plot_markers.R:214-237): x = as.double(t(x)) */
 void sharp_C_dist(double *x, int *n, int *p, int *method, double *minkowski_p, double *d_out, int *status) {

@@ -508,6 +508,7 @@ int sharp_shutdown(void) {
         (void)hipStreamSynchronize(c.stream);
         drop_pending_front();
         drain_side_streams();
+        umap_models_drop_slot(cur_slot());
         for (auto &p : c.pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
         c.pending.clear();
         for (auto e : c.event_pool) (void)hipEventDestroy(e);

@@ -4,8 +4,11 @@ uwot's argument names and defaults; the algorithm is this project's specificatio
 uwot's batch = TRUE mode -- no bit parity with either is claimed.  Computed by libsharp_hip.so (sharp_umap): the optional PCA and the
 exact k-NN are Rtsne's own stages, the fuzzy graph and the epoch optimiser are HIP kernels, the a / b curve is fitted on the host.
 umap_neighbors() takes neighbour lists the caller already has -- what knn() returns -- so lists computed once serve both maps.
+umap_transform() places new rows in a fitted map: a UmapModel keeps the reference rows and their map on the device,
+and every new row is placed by its nearest reference rows, block after block; knn_query() returns those lists alone.
 There is no CPU path: without a device every call but umap_ab raises SharpError."""
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -13,7 +16,7 @@ from . import _lib
 from ._lib import check, f64, i32, i64, lib
 from .tsne import _neighbour_arrays
 
-__all__ = ["umap", "umap_neighbors", "umap_ab"]
+__all__ = ["umap", "umap_neighbors", "umap_ab", "umap_transform", "UmapModel", "knn_query"]
 
 _INITS = ("pca", "random")
 
@@ -73,9 +76,10 @@ def _common(who, n, n_components, n_epochs, init, a, b, allow_pca):
 
 def umap(X, n_neighbors=15, n_components=2, metric="euclidean", n_epochs=None, learning_rate=1.0, init="pca", spread=1.0, min_dist=0.01,
          set_op_mix_ratio=1.0, local_connectivity=1.0, bandwidth=1.0, repulsion_strength=1.0, negative_sample_rate=5, a=None, b=None,
-         pca=None, pca_center=True, seed=10, ret_nn=False, n_threads=None, n_sgd_threads=0, verbose=False, batch=True):
+         pca=None, pca_center=True, seed=10, ret_nn=False, n_threads=None, n_sgd_threads=0, verbose=False, batch=True, ret_model=False):
     """umap(X, ...) with uwot's arguments and defaults; returns {"Y", "a", "b", "n_epochs", "n_neighbors", "N"} and, with ret_nn,
-    "nn": {"index", "distance"} (the exact k-NN lists: n x (n_neighbors - 1), 0-based, Euclidean, self excluded).
+    "nn": {"index", "distance"} (the exact k-NN lists: n x (n_neighbors - 1), 0-based, Euclidean, self excluded); with ret_model,
+    "model": a UmapModel of (X, Y) for umap_transform (n_neighbors up to 255; not together with pca).
 
     n_neighbors counts the point itself (2 .. 256, below n); n_components is 1, 2 or 3; n_epochs None: 500 up to 10 000 rows, else 200;
     init "pca" (the first n_components principal components of the prepared input), "random" (runif(-10, 10) from R's set.seed(seed)
@@ -97,6 +101,11 @@ def umap(X, n_neighbors=15, n_components=2, metric="euclidean", n_epochs=None, l
     pca = 0 if pca is None else int(pca)
     if pca < 0:
         raise _lib.SharpError(f"{who}: pca must be None or a positive number of components")
+    if ret_model and pca:
+        raise _lib.SharpError(f"{who}: ret_model is not built together with pca (the PCA's rotation is not kept, so new rows could not be "
+                              "brought into the model's space): reduce the data first and give pca = None")
+    if ret_model and n_neighbors > 255:
+        raise _lib.SharpError(f"{who}: ret_model needs n_neighbors <= 255 (a model's lists hold n_neighbors reference rows)")
     if code == 0 and (min(pca, d) if pca else d) < dims:
         raise _lib.SharpError(f"{who}: init = \"pca\" needs at least n_components columns")
     _lib.ensure_init()
@@ -110,7 +119,162 @@ def umap(X, n_neighbors=15, n_components=2, metric="euclidean", n_epochs=None, l
     out = {"Y": Y, "a": float(ab[0]), "b": float(ab[1]), "n_epochs": n_epochs, "n_neighbors": n_neighbors, "N": n}
     if ret_nn:
         out["nn"] = {"index": nn_i, "distance": nn_d}
+    if ret_model:
+        out["model"] = UmapModel(X, Y, n_neighbors, out["a"], out["b"], n_epochs)
     return out
+
+
+# ---- new rows in a fitted map -----------------------------------------------------------------------------------------
+def _free_model(handle):
+    if _lib._initialised_device is not None:     # (after shutdown() the library has freed it already)
+        lib().sharp_umap_model_free(handle)
+
+
+class UmapModel:
+    """A fitted map on the device (sharp_umap_model_create): the reference rows X_ref (n_ref x d), their map Y_ref (n_ref x 1 .. 3),
+    n_neighbors (1 .. 255, <= n_ref: the number of reference rows a new row is placed by), the curve's a and b, and the fit's n_epochs
+    (a transform runs a third of them by default).  umap(..., ret_model=True) returns one.  close() frees it; it is a context manager
+    and is freed when collected; shutdown() frees what is left.  X_ref and Y_ref must be finite."""
+
+    def __init__(self, X_ref, Y_ref, n_neighbors, a, b, n_epochs):
+        who = "UmapModel"
+        X_ref = _rows(X_ref, who)
+        Y_ref = np.ascontiguousarray(Y_ref, dtype=np.float64)
+        n, d = X_ref.shape
+        if Y_ref.ndim != 2 or Y_ref.shape[0] != n or Y_ref.shape[1] not in (1, 2, 3):
+            raise _lib.SharpError(f"{who}: Y_ref must be an n_ref x (1, 2 or 3) matrix, not of shape {Y_ref.shape}")
+        n_neighbors = int(n_neighbors)
+        if not 1 <= n_neighbors <= 255:
+            raise _lib.SharpError(f"{who}: n_neighbors must be in 1 .. 255")
+        if n_neighbors > n:
+            raise _lib.SharpError(f"{who}: n_neighbors must not exceed the number of reference rows")
+        if not (a > 0 and b > 0 and np.isfinite(a) and np.isfinite(b)):
+            raise _lib.SharpError(f"{who}: a and b must be positive")
+        if int(n_epochs) < 0:
+            raise _lib.SharpError(f"{who}: n_epochs must be >= 0")
+        _lib.ensure_init()
+        h = C.c_int(0)
+        check(lib().sharp_umap_model_create(f64(X_ref), n, int(d), d, f64(Y_ref), int(Y_ref.shape[1]), n_neighbors, float(a), float(b),
+                                            int(n_epochs), C.byref(h)))
+        self.handle = h.value
+        self.n_ref, self.d, self.dims = n, int(d), int(Y_ref.shape[1])
+        self.n_neighbors, self.a, self.b, self.n_epochs = n_neighbors, float(a), float(b), int(n_epochs)
+        self._finalizer = weakref.finalize(self, _free_model, self.handle)
+
+    def close(self):
+        if self._finalizer.detach():
+            check(lib().sharp_umap_model_free(self.handle))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def _queries(X_new, model, who):
+    if not isinstance(model, UmapModel):
+        raise _lib.SharpError(f"{who}: model must be a UmapModel (umap(..., ret_model=True)[\"model\"])")
+    X_new = _rows(X_new, who)
+    if X_new.shape[0] < 1 or X_new.shape[1] != model.d:
+        raise _lib.SharpError(f"{who}: X_new must hold at least one row of the model's {model.d} columns, not shape {X_new.shape}")
+    return X_new
+
+
+def umap_transform(X_new, model, n_epochs=None, learning_rate=1.0, negative_sample_rate=5, repulsion_strength=1.0, seed=10, row_offset=0,
+                   ret_nn=False):
+    """umap_transform(X_new, model, ...): the rows of X_new placed in the model's map; returns {"Y", "n_epochs", "N"} and, with ret_nn,
+    "nn": {"index", "distance"} (each row's model.n_neighbors nearest reference rows: 0-based, Euclidean, sorted by (distance, index)).
+
+    Every row starts at the weighted mean of its neighbours' positions and is then moved for n_epochs epochs (None: a third of the
+    fit's, rounded down; 0 returns the start) by the attraction of its neighbours and negative_sample_rate (0 .. 64) drawn reference
+    rows per firing neighbour; the reference map does not move.  A row's result depends on that row, the model, the arguments and
+    row_offset + its row number alone: a long table transformed block by block, with row_offset = the block's first row, gives the bits
+    of one call.  Input NA / NaN / Inf is refused."""
+    who = "umap_transform"
+    X_new = _queries(X_new, model, who)
+    n = X_new.shape[0]
+    E = model.n_epochs // 3 if n_epochs is None else int(n_epochs)
+    if E < 0:
+        raise _lib.SharpError(f"{who}: n_epochs must be >= 0")
+    if int(row_offset) < 0:
+        raise _lib.SharpError(f"{who}: row_offset must be >= 0")
+    if not 0 <= int(negative_sample_rate) <= 64:
+        raise _lib.SharpError(f"{who}: negative_sample_rate must be in 0 .. 64")
+    _lib.ensure_init()
+    K = model.n_neighbors
+    Y = np.zeros((n, model.dims))
+    nn_i = np.zeros((n, K), np.int32) if ret_nn else None
+    nn_d = np.zeros((n, K)) if ret_nn else None
+    check(lib().sharp_umap_transform(model.handle, f64(X_new), n, model.d, E, float(learning_rate), int(negative_sample_rate),
+                                     float(repulsion_strength), float(seed), int(row_offset), f64(Y), i32(nn_i), f64(nn_d)))
+    out = {"Y": Y, "n_epochs": E, "N": n}
+    if ret_nn:
+        out["nn"] = {"index": nn_i, "distance": nn_d}
+    return out
+
+
+def knn_query(model_or_X_ref, X_new, K, max_rows_per_launch=0):
+    """The K exact nearest rows of a reference for every row of X_new: (index (n_new, K) int32, 0-based into the reference; distance
+    (n_new, K) Euclidean), ties to the lower index, each row sorted by (distance, index) -- a label transfer needs no more.  The
+    reference is a UmapModel, or a matrix X_ref (a model is then made for the call and freed).  1 <= K <= 255, K <= n_ref.
+    max_rows_per_launch (0: the library's choice) only cuts the work into launches; the lists do not depend on it."""
+    who = "knn_query"
+    K = int(K)
+    if not 1 <= K <= 255:
+        raise _lib.SharpError(f"{who}: K must be in 1 .. 255")
+    if isinstance(model_or_X_ref, UmapModel):
+        return _knn_cross(model_or_X_ref, X_new, K, max_rows_per_launch, who)
+    X_ref = _rows(model_or_X_ref, who)
+    if K > X_ref.shape[0]:
+        raise _lib.SharpError(f"{who}: K must not exceed the number of reference rows")
+    with UmapModel(X_ref, np.zeros((X_ref.shape[0], 1)), K, 1.0, 1.0, 0) as m:
+        return _knn_cross(m, X_new, K, max_rows_per_launch, who)
+
+
+def _knn_cross(model, X_new, K, max_rows_per_launch=0, who="knn_query"):
+    """sharp_knn_cross"""
+    X_new = _queries(X_new, model, who)
+    if K > model.n_ref:
+        raise _lib.SharpError(f"{who}: K must not exceed the number of reference rows")
+    if int(max_rows_per_launch) < 0:
+        raise _lib.SharpError(f"{who}: max_rows_per_launch must be >= 0")
+    _lib.ensure_init()
+    n = X_new.shape[0]
+    idx = np.zeros((n, K), np.int32)
+    dist = np.zeros((n, K))
+    check(lib().sharp_knn_cross(model.handle, f64(X_new), n, model.d, int(K), int(max_rows_per_launch), i32(idx), f64(dist)))
+    return idx, dist
+
+
+def _transform_weights(model, index, distance):
+    """(sigma, w, Y0) from a query's lists (sharp_umap_transform_weights)"""
+    index = np.ascontiguousarray(index, np.int32)
+    distance = np.ascontiguousarray(distance, np.float64)
+    if index.ndim != 2 or index.shape != distance.shape:
+        raise _lib.SharpError("umap_transform weights: index and distance must be matrices of one shape")
+    n, K = index.shape
+    _lib.ensure_init()
+    sigma, w, Y0 = np.zeros(n), np.zeros((n, K)), np.zeros((n, model.dims))
+    check(lib().sharp_umap_transform_weights(model.handle, i32(index), f64(distance), n, int(K), f64(sigma), f64(w), f64(Y0)))
+    return sigma, w, Y0
+
+
+def _transform_epochs(model, index, w, Y, n_epochs, ep0, ep1, learning_rate=1.0, negative_sample_rate=5, repulsion_strength=1.0, seed=10,
+                      row_offset=0):
+    """Y after epochs [ep0, ep1) of n_epochs from the given Y (sharp_umap_transform_epochs)"""
+    index = np.ascontiguousarray(index, np.int32)
+    w = np.ascontiguousarray(w, np.float64)
+    Y = np.array(Y, dtype=np.float64, order="C")
+    if index.ndim != 2 or index.shape != w.shape or Y.shape != (index.shape[0], model.dims):
+        raise _lib.SharpError("umap_transform epochs: index and w must be matrices of one shape, Y nq x the model's dims")
+    n, K = index.shape
+    _lib.ensure_init()
+    check(lib().sharp_umap_transform_epochs(model.handle, i32(index), f64(w), n, int(K), f64(Y), int(n_epochs), int(ep0), int(ep1),
+                                            float(learning_rate), int(negative_sample_rate), float(repulsion_strength), float(seed),
+                                            int(row_offset)))
+    return Y
 
 
 def umap_neighbors(index, distance, squared=False, n_components=2, n_epochs=None, learning_rate=1.0, init="random", spread=1.0,
