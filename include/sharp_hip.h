@@ -433,7 +433,7 @@ int sharp_tsne_affinities_nn(const int *index, const double *distance, long long
  * receive the k-NN lists (0-based, Euclidean distances, sorted by (distance, index)).  Two calls with the same input and seed give
  * bitwise-identical Y on the same GPU.
  * sharp_umap_neighbors: the same from lists the caller has (index / distance n x K row-major, 0-based, n_neighbors = K + 1; squared =
- * 1: squared distances, as sharp_tsne_knn returns them), validated as sharp_tsne_neighbors validates them; init 1 or 2 only.
+ * 1: squared distances, as sharp_tsne_knn returns them), validated as sharp_tsne_neighbors validates them; init 1, 2 or 3 (below).
  * Stages: sharp_umap_graph: lists -> the fuzzy graph W = A + A^T - A o A^T as a CSR with rows sorted by column (cap >= 2 n K always
  * suffices), rho and sigma (n each).  sharp_umap_epochs: epochs [ep0, ep1) of n_epochs on Y (n x dims, in and out) for a CSR whose
  * mirrored entries carry equal weights; the schedule is stateless, so [0, e) then [e, n_epochs) gives the bits of [0, n_epochs). */
@@ -448,6 +448,27 @@ int sharp_umap_graph(const int *index, const double *distance, long long n, int 
                      double *val, long long *nnz, double *rho, double *sigma);
 int sharp_umap_epochs(const long long *row_ptr, const int *col, const double *val, long long n, int dims, double *Y, int n_epochs, int ep0,
                       int ep1, double learning_rate, double a, double b, int negative_sample_rate, double repulsion_strength, double seed);
+
+/* ---- UMAP's spectral start, init = 3 "normlaplacian" (DESIGN.md §15 is the specification: uwot's "normlaplacian" -- its "spectral"
+ * without the noise -- with no bit parity claimed).  sharp_umap and sharp_umap_neighbors accept init = 3: after the graph stage the
+ * bottom eigenvectors of the graph's normalised Laplacian are the start (through the same mapping onto [0, 10] as a given Y_init);
+ * where the graph is not connected or the solve does not converge, sharp_umap falls back to init = 0 and sharp_umap_neighbors to
+ * init = 1, each exactly as that code would have run.  sharp_umap_init_info tells which: the calling context's last sharp_umap /
+ * sharp_umap_neighbors call asked for *requested and started from *used (0 .. 3; -1: no call yet); *components, *steps and *residual
+ * (the largest true residual, or the last estimate on a fallback) are the spectral stage's, 0 where it did not run.
+ * Stages.  sharp_umap_components: the connected components of a CSR pattern (row_ptr n + 1, col; an edge counts in both directions):
+ * label[i] = the smallest vertex of i's component, *count = their number; an empty row is a component of its own.
+ * sharp_umap_spectral: for a symmetric CSR W (weights >= 0, finite, every non-empty row's sum positive) the dims (1 .. 3, n >= dims +
+ * 2) largest eigenvalues theta of M = D^-1/2 W D^-1/2 below the trivial 1 -- the smallest non-zero ones of L = I - M -- and their unit
+ * eigenvectors V (n x dims row-major, each vector's largest |component| positive, ties to the lowest index), by Lanczos with full
+ * reorthogonalisation on the complement of sqrt(deg).  tol <= 0 / max_steps <= 0: the defaults, 1e-6 and 400; max_steps is capped at
+ * n - 2.  *outcome: 0 converged (every true residual ||M v - theta v|| <= tol, in residual), 1 not connected (nothing is solved; V,
+ * theta, residual untouched), 2 not converged after *steps steps (residual: the last estimates; V, theta untouched).  Neither 1 nor 2 is
+ * an error status.  Two calls give the same bits. */
+int sharp_umap_components(const long long *row_ptr, const int *col, long long n, int *label, long long *count);
+int sharp_umap_spectral(const long long *row_ptr, const int *col, const double *val, long long n, int dims, double tol, int max_steps, double *V,
+                        double *theta, double *residual, int *steps, long long *components, int *outcome);
+int sharp_umap_init_info(int *requested, int *used, long long *components, int *steps, double *residual);
 
 /* ---- umap_transform: new rows placed in a fitted UMAP map (DESIGN.md §14 is the specification: this project's, modelled on umap-learn's
  * transform and uwot's umap_transform, with no bit parity claimed).
@@ -646,6 +667,12 @@ void sharp_C_umap_model_free(int *handle, int *status);
 void sharp_C_umap_transform(int *handle, double *Xq, double *nq, int *d, int *n_epochs, double *learning_rate, int *negative_sample_rate,
                             double *repulsion_strength, double *seed, double *row_offset, double *Yq, int *want_nn, int *nn_index,
                             double *nn_distance, int *status);
+/* sharp_umap_components / sharp_umap_spectral / sharp_umap_init_info in the same convention: row_ptr (n + 1 values), n, count and
+ * components as double; col 0-based */
+void sharp_C_umap_components(double *row_ptr, int *col, double *n, int *label, double *count, int *status);
+void sharp_C_umap_spectral(double *row_ptr, int *col, double *val, double *n, int *dims, double *tol, int *max_steps, double *V, double *theta,
+                           double *residual, int *steps, double *components, int *outcome, int *status);
+void sharp_C_umap_init_info(int *requested, int *used, double *components, int *steps, double *residual, int *status);
 /* stats::dist / stats::hclust for pheatmap inside plot_markers (R/plot_markers.R:214-237): x = as.double(t(x)) (rows of p values) */
 void sharp_C_dist(double *x, int *n, int *p, int *method, double *minkowski_p, double *d_out, int *status);
 void sharp_C_hclust_dist(double *d, int *n, int *hmethod, int *merge, double *height, int *order, int *status);

@@ -411,14 +411,30 @@ sharp_knn <- function(X, K, squared = FALSE) {
 }
 .sharp_umap_init <- function(init, n, dims, allow_pca) {
     if (is.character(init)) {
-        code <- match(init, c("pca", "random")) - 1L
-        if (is.na(code)) stop("umap: init must be \"pca\", \"random\" or an n x n_components matrix")
-        if (code == 0L && !allow_pca) stop("umap_neighbors: init = \"pca\" needs the data; give \"random\" or a matrix")
+        code <- match(init, c("pca", "random", NA, "normlaplacian")) - 1L    # ("normlaplacian" is code 3; 2 is a matrix)
+        if (is.na(init) || is.na(code)) stop("umap: init must be one of \"pca\", \"random\", \"normlaplacian\" or an n x n_components matrix")
+        if (code == 0L && !allow_pca) stop("umap_neighbors: init = \"pca\" needs the data; give \"random\", \"normlaplacian\" or a matrix")
+        if (code == 3L && n < dims + 2L) stop("umap: init = \"normlaplacian\" needs at least n_components + 2 rows")
         return(list(code = code, Y = double(1)))
     }
     init <- .sharp_dmat(init)
     if (!all(dim(init) == c(n, dims))) stop("umap: init must be \"pca\", \"random\" or an n x n_components matrix")
     list(code = 2L, Y = as.double(t(init)))
+}
+# What the last sharp_umap / sharp_umap_neighbors call of this session started from (DESIGN.md 15): list(requested =, used =, components =,
+# steps =, residual =).  init = "normlaplacian" is the spectral start (uwot's "normlaplacian"); where the graph is in pieces or the
+# eigensolver does not converge the call falls back ("pca" with the data, "random" with lists alone) and warns.
+.sharp_umap_init_info <- function(who) {
+    r <- .C("sharp_C_umap_init_info", requested = integer(1), used = integer(1), components = double(1), steps = integer(1),
+            residual = double(1), status = integer(1))
+    .sharp_check(r$status)
+    nm <- c("pca", "random", "matrix", "normlaplacian")
+    info <- list(requested = nm[r$requested + 1L], used = nm[r$used + 1L], components = r$components, steps = r$steps, residual = r$residual)
+    if (r$used != r$requested)
+        warning(who, ": init = \"", info$requested, "\" fell back to \"", info$used, "\": ",
+                if (r$components != 1) paste0("the graph has ", r$components, " connected components")
+                else paste0("the eigensolver did not converge in ", r$steps, " steps (residual estimate ", signif(r$residual, 3), ")"))
+    info
 }
 sharp_umap_ab <- function(spread = 1, min_dist = 0.01) {
     r <- .C("sharp_C_umap_ab", as.double(spread), as.double(min_dist), a = double(1), b = double(1), status = integer(1))
@@ -441,12 +457,16 @@ sharp_umap <- function(X, n_neighbors = 15, n_components = 2, metric = "euclidea
             as.integer(ret_nn), idx = integer(if (ret_nn) n * K else 1L), dist = double(if (ret_nn) n * K else 1L), status = integer(1))
     .sharp_check(r$status)
     Y <- matrix(r$Y, n, dims, byrow = TRUE)
-    if (!ret_nn) return(Y)
-    list(embedding = Y, nn = list(euclidean = list(idx = cbind(seq_len(n), matrix(r$idx, n, K, byrow = TRUE) + 1L),
-                                                   dist = cbind(0, matrix(r$dist, n, K, byrow = TRUE)))))
+    info <- if (ini$code == 3L) .sharp_umap_init_info("umap") else NULL     # (attr(Y, "init"), or $init beside the lists)
+    if (!ret_nn) { attr(Y, "init") <- info; return(Y) }
+    out <- list(embedding = Y, nn = list(euclidean = list(idx = cbind(seq_len(n), matrix(r$idx, n, K, byrow = TRUE) + 1L),
+                                                          dist = cbind(0, matrix(r$dist, n, K, byrow = TRUE)))))
+    out$init <- info
+    out
 }
 # umap from neighbour lists the caller has: index n x K, 1-BASED, self excluded (what sharp_knn returns); distance their Euclidean
-# distances, or squares with squared = TRUE.  n_neighbors is K + 1.  init: "random" or a matrix.
+# distances, or squares with squared = TRUE.  n_neighbors is K + 1.  init: "random", "normlaplacian" (then attr(, "init") tells what the
+# map started from) or a matrix.
 sharp_umap_neighbors <- function(index, distance, squared = FALSE, n_components = 2, n_epochs = NULL, learning_rate = 1, init = "random",
                                  spread = 1, min_dist = 0.01, repulsion_strength = 1, negative_sample_rate = 5, a = NULL, b = NULL,
                                  seed = 10, metric = "euclidean", set_op_mix_ratio = 1, local_connectivity = 1, bandwidth = 1, ...) {
@@ -465,7 +485,9 @@ sharp_umap_neighbors <- function(index, distance, squared = FALSE, n_components 
             ab = as.double(if (is.null(a)) c(0, 0) else c(a, b)), as.integer(negative_sample_rate), as.double(repulsion_strength), ini$code,
             ini$Y, as.double(seed), Y = double(n * dims), status = integer(1), NAOK = TRUE)
     .sharp_check(r$status)
-    matrix(r$Y, n, dims, byrow = TRUE)
+    Y <- matrix(r$Y, n, dims, byrow = TRUE)
+    if (ini$code == 3L) attr(Y, "init") <- .sharp_umap_init_info("umap_neighbors")
+    Y
 }
 
 # ---- uwot::umap_transform: new rows placed in a fitted map (DESIGN.md 14) -----------------------------------------------------------------

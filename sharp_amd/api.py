@@ -1045,6 +1045,8 @@ def _vis_umap(y, label, w, filename, filetype, legendtitle, width, height, res, 
         _draw_sharp_map(out["Y"], label, filename, filetype, legendtitle, width, height, res)
     r = {"Y": out["Y"], "a": out["a"], "b": out["b"], "n_epochs": out["n_epochs"], "filename": filename if plot else None,
          "time": (_t.time() - t0) / 60.0}
+    if "init" in out:                                                # (init = "normlaplacian": what the map started from)
+        r["init"] = out["init"]
     if return_neighbors:
         r["neighbors"] = nb
     return r

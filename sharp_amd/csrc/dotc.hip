@@ -10,6 +10,7 @@
 //   - *status receives what the plain entry point returns (0, warning bits, or an error code: then sharp_C_last_error()
 //     gives the text for R's stop()).
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -291,6 +292,33 @@ void sharp_C_umap_transform(int *handle, double *Xq, double *nq, int *d, int *n_
     *status = sharp_umap_transform(*handle, Xq, as_ll(nq), static_cast<long long>(*d), *n_epochs, *learning_rate, *negative_sample_rate,
                                    *repulsion_strength, *seed, as_ll(row_offset), Yq, *want_nn ? nn_index : nullptr,
                                    *want_nn ? nn_distance : nullptr);
+}
+
+/* the spectral start's stages (sharp_umap_components, sharp_umap_spectral, sharp_umap_init_info): row_ptr, n and the counts as double */
+static std::vector<long long> row_ptr_ll(const double *row_ptr, long long n) {   // (an n the library refuses: nothing is read)
+    std::vector<long long> rp(n >= 1 && n < INT_MAX ? static_cast<size_t>(n) + 1 : 1, 0);
+    for (size_t i = 0; rp.size() > 1 && i < rp.size(); ++i) rp[i] = as_ll(row_ptr + i);
+    return rp;
+}
+void sharp_C_umap_components(double *row_ptr, int *col, double *n, int *label, double *count, int *status) {
+    const long long nn = as_ll(n);
+    const std::vector<long long> rp = row_ptr_ll(row_ptr, nn);
+    long long k = 0;
+    *status = sharp_umap_components(rp.data(), col, nn, label, &k);
+    *count = static_cast<double>(k);
+}
+void sharp_C_umap_spectral(double *row_ptr, int *col, double *val, double *n, int *dims, double *tol, int *max_steps, double *V, double *theta,
+                           double *residual, int *steps, double *components, int *outcome, int *status) {
+    const long long nn = as_ll(n);
+    const std::vector<long long> rp = row_ptr_ll(row_ptr, nn);
+    long long k = 0;
+    *status = sharp_umap_spectral(rp.data(), col, val, nn, *dims, *tol, *max_steps, V, theta, residual, steps, &k, outcome);
+    *components = static_cast<double>(k);
+}
+void sharp_C_umap_init_info(int *requested, int *used, double *components, int *steps, double *residual, int *status) {
+    long long k = 0;
+    *status = sharp_umap_init_info(requested, used, &k, steps, residual);
+    *components = static_cast<double>(k);
 }
 
 /* ---- dist / hclust (the clustering pheatmap does inside plot_markers, R/plot_markers.R:214-237): x = as.double(t(x)) */

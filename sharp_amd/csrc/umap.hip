@@ -423,7 +423,7 @@ struct UmapArgs {
     double *ab;
     int negative_sample_rate;
     double repulsion_strength;
-    int init;                  // 0 "pca", 1 "random", 2 Y_init
+    int init;                  // 0 "pca", 1 "random", 2 Y_init, 3 "normlaplacian" 
     const double *Y_init;
     double seed;
 };
@@ -431,7 +431,8 @@ struct UmapArgs {
 void check_umap_args(long long n, const UmapArgs &u, const double *Y) {
     SHARP_REQUIRE(u.dims >= 1 && u.dims <= 3, "umap: n_components must be 1, 2 or 3");
     SHARP_REQUIRE(Y && u.ab, "umap: null Y / ab");
-    SHARP_REQUIRE(u.init >= 0 && u.init <= 2, "umap: init must be 0 (pca), 1 (random) or 2 (Y_init)");
+    SHARP_REQUIRE(u.init >= 0 && u.init <= 3, "umap: init must be 0 (pca), 1 (random), 2 (Y_init) or 3 (normlaplacian)");
+    SHARP_REQUIRE(u.init != 3 || n >= u.dims + 2, "umap: init = \"normlaplacian\" needs at least n_components + 2 rows");
     SHARP_REQUIRE(u.init != 2 || u.Y_init, "umap: init = 2 needs Y_init");
     SHARP_REQUIRE(u.negative_sample_rate >= 0 && u.negative_sample_rate <= 64, "umap: negative_sample_rate must be in 0 .. 64");
     SHARP_REQUIRE(std::isfinite(u.learning_rate) && std::isfinite(u.repulsion_strength), "umap: learning_rate and repulsion_strength must be finite");
@@ -461,17 +462,18 @@ void scale_start(std::vector<double> &y, long long n, int dims) {
 }
 
 // Everything behind the neighbour lists (idx, dist: device, n x K, Euclidean; released once the graph exists).  Xp: the prepared input
-// on the device (n x dp) for init = 0, else null.
+// on the device (n x dp) for init = 0 and for init = 3 (whose fallback is the PCA start), else null.
 void run_from_lists(DevBuf<int> &idx, DevBuf<double> &dist, long long n, int K, const DevBuf<double> *Xp, int dp, const UmapArgs &u, double *Y) {
     resolve_ab(u);
     const int n_epochs = resolve_epochs(n, u.n_epochs);
     const size_t ne = static_cast<size_t>(n) * u.dims;
     std::vector<double> y0(ne);
-    {
+    // the start of code 0, 1 or 2, mapped onto [0, 10]
+    auto start_from = [&](int code) {
         HostTimer ht("umap_init");
-        if (u.init == 2) {
+        if (code == 2) {
             std::copy(u.Y_init, u.Y_init + ne, y0.begin());
-        } else if (u.init == 1) {
+        } else if (code == 1) {
             RRng rng(static_cast<uint32_t>(static_cast<long long>(u.seed)));   // runif(-10, 10) from set.seed(seed), row by row
             for (size_t e = 0; e < ne; ++e) y0[e] = -10.0 + 20.0 * rng.unif();
         } else {
@@ -486,11 +488,32 @@ void run_from_lists(DevBuf<int> &idx, DevBuf<double> &dist, long long n, int K, 
             pc.download(y0.data(), ne);
         }
         scale_start(y0, n, u.dims);
-    }
+    };
+    UmapInitInfo &info = umap_init_info();
+    info = UmapInitInfo();
+    info.requested = info.used = u.init;
+    if (u.init != 3) start_from(u.init);
     UmapGraph G;
     umap_graph(idx, dist, n, K, G);
     idx.release();
     dist.release();
+    if (u.init == 3) {
+        // the bottom eigenvectors of the graph's normalised Laplacian; a graph in pieces or a solve that does not converge falls back
+        // as uwot does: to the PCA start where the data are at hand, else to the random one
+        UmapSpectral S;
+        umap_spectral(G, u.dims, 0.0, 0, S);
+        info.components = S.components;
+        info.steps = S.steps;
+        info.residual = S.outcome == 1 ? 0.0 : *std::max_element(S.residual, S.residual + u.dims);
+        if (S.outcome == 0) {
+            HostTimer ht("umap_init");
+            y0 = S.V;
+            scale_start(y0, n, u.dims);
+        } else {
+            info.used = Xp ? 0 : 1;
+            start_from(info.used);
+        }
+    }
     DevBuf<double> dY(ne);
     dY.upload(y0.data(), ne);
     umap_epochs(G, dY.p, u.dims, n_epochs, 0, n_epochs, u.learning_rate, u.ab[0], u.ab[1], u.negative_sample_rate, u.repulsion_strength,
@@ -555,8 +578,9 @@ int sharp_umap(const double *X, long long n, int d, long long ld, int n_neighbor
         idx.download(nn_index, static_cast<size_t>(n) * K);
         dist.download(nn_distance, static_cast<size_t>(n) * K);
     }
-    if (init != 0) Xp.release();
-    run_from_lists(idx, dist, n, K, init == 0 ? &Xp : nullptr, dp, u, Y);
+    const bool keep_x = init == 0 || init == 3;   // (the spectral start falls back to the PCA one)
+    if (!keep_x) Xp.release();
+    run_from_lists(idx, dist, n, K, keep_x ? &Xp : nullptr, dp, u, Y);
     SHARP_API_END
 }
 

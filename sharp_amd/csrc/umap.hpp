@@ -25,4 +25,27 @@ void umap_graph(const DevBuf<int> &idx, const DevBuf<double> &dist, long long n,
 void umap_epochs(const UmapGraph &G, double *dY, int dims, int n_epochs, int ep0, int ep1, double learning_rate, double a, double b,
                  int negative_sample_rate, double repulsion_strength, unsigned long long seed);
 
+// ---- the spectral start, init = "normlaplacian" (umap_spectral.hip) ----
+struct UmapSpectral {
+    int outcome = 0;             // 0 converged, 1 not connected (nothing solved), 2 not converged
+    int steps = 0;               // Lanczos steps taken
+    long long components = 0;
+    double theta[3] = {0.0, 0.0, 0.0};      // outcome 0: the dims largest eigenvalues of M = D^-1/2 W D^-1/2 below the trivial 1
+    double residual[3] = {0.0, 0.0, 0.0};   // outcome 0: the true ||M v - theta v||; outcome 2: the last estimates
+    std::vector<double> V;       // outcome 0: the unit eigenvectors, n x dims row-major (host), the largest |component| positive
+};
+// the number of connected components of G's pattern; label (n, device) = the smallest vertex of each vertex's component when wanted
+long long umap_components(const UmapGraph &G, DevBuf<int> *label = nullptr);
+// tol <= 0 / max_steps <= 0: the library's defaults (1e-6, 400); max_steps is capped at n - 2
+void umap_spectral(const UmapGraph &G, int dims, double tol, int max_steps, UmapSpectral &R);
+// what the calling context's last sharp_umap / sharp_umap_neighbors call started from (init codes: 0 pca, 1 random, 2 Y_init,
+// 3 normlaplacian); components, steps and residual are the spectral stage's, 0 when it did not run
+struct UmapInitInfo {
+    int requested = -1, used = -1;
+    long long components = 0;
+    int steps = 0;
+    double residual = 0.0;
+};
+UmapInitInfo &umap_init_info();
+
 }  // namespace sharp

@@ -8,6 +8,7 @@ umap_transform() places new rows in a fitted map: a UmapModel k
 and every new row is placed by its nearest reference rows, block after block; knn_query() returns those lists alone.
 There is no CPU path: without a device every call but umap_ab raises SharpError."""
 import ctypes as C
+import warnings
 import weakref
 
 import numpy as np
@@ -19,6 +20,9 @@ from .tsne import _neighbour_arrays
 __all__ = ["umap", "umap_neighbors", "umap_ab", "umap_transform", "UmapModel", "knn_query"]
 
 _INITS = ("pca", "random")
+_NORMLAPLACIAN = "normlaplacian"                 # init code 3; not an index into _INITS
+_INIT_NAMES = {0: "pca", 1: "random", 2: "matrix", 3: _NORMLAPLACIAN}
+_OUTCOMES = {0: "converged", 1: "not connected", 2: "not converged"}
 
 
 def _rows(X, who):
@@ -56,11 +60,13 @@ def _common(who, n, n_components, n_epochs, init, a, b, allow_pca):
         raise _lib.SharpError(f"{who}: n_epochs must be >= 0")
     Y_init = None
     if isinstance(init, str):
-        if init not in _INITS:
-            raise _lib.SharpError(f"{who}: init must be one of {_INITS} or an n x n_components matrix, not {init!r}")
+        if init not in _INITS + (_NORMLAPLACIAN,):
+            raise _lib.SharpError(f"{who}: init must be one of {_INITS + (_NORMLAPLACIAN,)} or an n x n_components matrix, not {init!r}")
         if init == "pca" and not allow_pca:
-            raise _lib.SharpError(f"{who}: init = \"pca\" needs the data; give \"random\" or an n x n_components matrix")
-        code = _INITS.index(init)
+            raise _lib.SharpError(f"{who}: init = \"pca\" needs the data; give \"random\", \"normlaplacian\" or an n x n_components matrix")
+        if init == _NORMLAPLACIAN and n < dims + 2:
+            raise _lib.SharpError(f"{who}: init = \"normlaplacian\" needs at least n_components + 2 rows")
+        code = 3 if init == _NORMLAPLACIAN else _INITS.index(init)
     else:
         Y_init = np.ascontiguousarray(init, dtype=np.float64)
         if Y_init.shape != (n, dims):
@@ -74,6 +80,19 @@ def _common(who, n, n_components, n_epochs, init, a, b, allow_pca):
     return dims, n_epochs, code, Y_init, ab
 
 
+def _init_info(who):
+    """sharp_umap_init_info of the call that just returned, as the result's "init"; a fallback is a RuntimeWarning"""
+    req, used, steps, comp, res = C.c_int(), C.c_int(), C.c_int(), C.c_longlong(), C.c_double()
+    check(lib().sharp_umap_init_info(C.byref(req), C.byref(used), C.byref(comp), C.byref(steps), C.byref(res)))
+    info = {"requested": _INIT_NAMES[req.value], "used": _INIT_NAMES[used.value], "components": comp.value, "steps": steps.value,
+            "residual": res.value}
+    if used.value != req.value:
+        why = (f"the graph has {comp.value} connected components" if comp.value != 1 else
+               f"the eigensolver did not converge in {steps.value} steps (residual estimate {res.value:.3g})")
+        warnings.warn(f"{who}: init = \"{info['requested']}\" fell back to \"{info['used']}\": {why}", RuntimeWarning, stacklevel=3)
+    return info
+
+
 def umap(X, n_neighbors=15, n_components=2, metric="euclidean", n_epochs=None, learning_rate=1.0, init="pca", spread=1.0, min_dist=0.01,
          set_op_mix_ratio=1.0, local_connectivity=1.0, bandwidth=1.0, repulsion_strength=1.0, negative_sample_rate=5, a=None, b=None,
          pca=None, pca_center=True, seed=10, ret_nn=False, n_threads=None, n_sgd_threads=0, verbose=False, batch=True, ret_model=False):
@@ -83,7 +102,9 @@ def umap(X, n_neighbors=15, n_components=2, metric="euclidean", n_epochs=None, l
 
     n_neighbors counts the point itself (2 .. 256, below n); n_components is 1, 2 or 3; n_epochs None: 500 up to 10 000 rows, else 200;
     init "pca" (the first n_components principal components of the prepared input), "random" (runif(-10, 10) from R's set.seed(seed)
-    stream) or a matrix, each coordinate then mapped onto [0, 10]; pca: None, or a number of components the input is reduced to first
+    stream), "normlaplacian" (the bottom eigenvectors of the fuzzy graph's normalised Laplacian, uwot's noise-free spectral start,
+    DESIGN.md §15: the result gains "init": {"requested", "used", "components", "steps", "residual"}, and a graph in pieces or a solve
+    that does not converge falls back to "pca" with a RuntimeWarning) or a matrix, each coordinate then mapped onto [0, 10]; pca: None, or a number of components the input is reduced to first
     (centred when pca_center).  a, b: None fits them from (spread, min_dist).  Only metric = "euclidean" and set_op_mix_ratio =
     local_connectivity = bandwidth = 1 are built: anything else is refused.  n_threads, n_sgd_threads, verbose and batch are accepted
     and ignored (the update is always the batch form: every row moves at once from the epoch's old positions).  Input NA / NaN / Inf
@@ -117,6 +138,8 @@ def umap(X, n_neighbors=15, n_components=2, metric="euclidean", n_epochs=None, l
                            int(negative_sample_rate), float(repulsion_strength), code, f64(Y_init), pca, int(bool(pca_center)), float(seed),
                            f64(Y), i32(nn_i), f64(nn_d)))
     out = {"Y": Y, "a": float(ab[0]), "b": float(ab[1]), "n_epochs": n_epochs, "n_neighbors": n_neighbors, "N": n}
+    if code == 3:
+        out["init"] = _init_info(who)
     if ret_nn:
         out["nn"] = {"index": nn_i, "distance": nn_d}
     if ret_model:
@@ -282,8 +305,9 @@ def umap_neighbors(index, distance, squared=False, n_components=2, n_epochs=None
                    set_op_mix_ratio=1.0, local_connectivity=1.0, bandwidth=1.0, n_threads=None, n_sgd_threads=0, verbose=False, batch=True):
     """umap_neighbors(index, distance, ...): the map from neighbour lists the caller already has -- what knn(X, K) returns: index
     (n x K, integers, 0-based), distance (n x K) their Euclidean distances, or their squares with squared=True.  n_neighbors is K + 1;
-    1 <= K <= 255, K <= n - 1.  The lists are validated on the GPU as Rtsne_neighbors validates them.  init is "random" or a matrix
-    (there is no data for a PCA start).  With a given init, knn(X, K)'s lists give the bits of umap(X, n_neighbors=K + 1)."""
+    1 <= K <= 255, K <= n - 1.  The lists are validated on the GPU as Rtsne_neighbors validates them.  init is "random", a matrix, or
+    "normlaplacian" (as in umap(); it needs only the graph and falls back to "random" with a RuntimeWarning) -- there is no data for a
+    PCA start.  With a given init, knn(X, K)'s lists give the bits of umap(X, n_neighbors=K + 1)."""
     who = "umap_neighbors"
     _refuse_unbuilt(who, metric, set_op_mix_ratio, local_connectivity, bandwidth)
     index, distance = _neighbour_arrays(index, distance, who)
@@ -294,7 +318,10 @@ def umap_neighbors(index, distance, squared=False, n_components=2, n_epochs=None
     check(lib().sharp_umap_neighbors(i32(index), f64(distance), n, int(K), int(bool(squared)), dims, n_epochs, float(learning_rate),
                                      float(min_dist), float(spread), f64(ab), int(negative_sample_rate), float(repulsion_strength), code,
                                      f64(Y_init), float(seed), f64(Y)))
-    return {"Y": Y, "a": float(ab[0]), "b": float(ab[1]), "n_epochs": n_epochs, "n_neighbors": K + 1, "N": n}
+    out = {"Y": Y, "a": float(ab[0]), "b": float(ab[1]), "n_epochs": n_epochs, "n_neighbors": K + 1, "N": n}
+    if code == 3:
+        out["init"] = _init_info(who)
+    return out
 
 
 # ---- the stages one at a time (tests, tools/bench_umap.py) ----------------------------------------------------------------------------
@@ -312,6 +339,56 @@ def _graph(index, distance, squared=False):
     check(lib().sharp_umap_graph(i32(index), f64(distance), n, int(K), int(bool(squared)), cap, i64(rp), i32(col), f64(val), C.byref(nnz),
                                  f64(rho), f64(sigma)))
     return rp, col[: nnz.value].copy(), val[: nnz.value].copy(), rho, sigma
+
+
+def _csr(row_ptr, col, val, who):
+    rp = np.ascontiguousarray(row_ptr, np.int64)
+    cc = np.ascontiguousarray(col, np.int32)
+    if rp.ndim != 1 or rp.size < 2 or cc.ndim != 1 or rp[0] != 0 or rp[-1] != cc.size:
+        raise _lib.SharpError(f"{who}: row_ptr must hold n + 1 values from 0 to the number of entries of col")
+    vv = None
+    if val is not None:
+        vv = np.ascontiguousarray(val, np.float64)
+        if vv.shape != cc.shape:
+            raise _lib.SharpError(f"{who}: col and val must be vectors of one length")
+    return rp, cc, vv
+
+
+def _components(row_ptr, col):
+    """(label, count) of a CSR pattern (sharp_umap_components): label[i] = the smallest vertex of i's connected component"""
+    rp, cc, _ = _csr(row_ptr, col, None, "umap components")
+    n = rp.size - 1
+    _lib.ensure_init()
+    label = np.zeros(n, np.int32)
+    count = C.c_longlong()
+    check(lib().sharp_umap_components(i64(rp), i32(cc) if cc.size else None, n, i32(label), C.byref(count)))
+    return label, count.value
+
+
+def _spectral(row_ptr, col, val, dims=2, tol=0.0, max_steps=0, V=None):
+    """the spectral start's solve on a symmetric CSR (sharp_umap_spectral): {"V" (n x dims), "theta", "residual", "steps",
+    "components", "outcome": 0 converged / 1 not connected / 2 not converged}.  tol, max_steps <= 0: the library's defaults.  V: an
+    n x dims float64 buffer to fill (it is left as it is unless the outcome is 0)."""
+    who = "umap spectral"
+    rp, cc, vv = _csr(row_ptr, col, val, who)
+    n = rp.size - 1
+    dims = int(dims)
+    if dims not in (1, 2, 3):
+        raise _lib.SharpError(f"{who}: n_components must be 1, 2 or 3")
+    if n < dims + 2:
+        raise _lib.SharpError(f"{who}: needs at least n_components + 2 rows")
+    if vv is None:
+        raise _lib.SharpError(f"{who}: col and val must be vectors of one length")
+    if V is None:
+        V = np.zeros((n, dims))
+    if not isinstance(V, np.ndarray) or V.dtype != np.float64 or V.shape != (n, dims) or not V.flags.c_contiguous:
+        raise _lib.SharpError(f"{who}: V must be a C-contiguous float64 array of shape (n, n_components)")
+    _lib.ensure_init()
+    theta, residual = np.zeros(dims), np.zeros(dims)
+    steps, outcome, comp = C.c_int(), C.c_int(), C.c_longlong()
+    check(lib().sharp_umap_spectral(i64(rp), i32(cc) if cc.size else None, f64(vv), n, dims, float(tol), int(max_steps), f64(V), f64(theta),
+                                    f64(residual), C.byref(steps), C.byref(comp), C.byref(outcome)))
+    return {"V": V, "theta": theta, "residual": residual, "steps": steps.value, "components": comp.value, "outcome": outcome.value}
 
 
 def _epochs(row_ptr, col, val, Y, n_epochs, ep0, ep1, a, b, learning_rate=1.0, negative_sample_rate=5, repulsion_strength=1.0, seed=10):
