@@ -420,6 +420,25 @@ int sharp_tsne_knn_dist(const double *d, int n, int K, int *idx, double *dist2);
 int sharp_tsne_affinities_nn(const int *index, const double *distance, long long n, int K, int squared, double perplexity, long long cap,
                              long long *row_ptr, int *col, double *val, long long *nnz);
 
+/* ---- The approximate k-NN beside sharp_tsne_knn (DESIGN.md §16 is the specification: this project's own NN-descent; no parity with
+ * pynndescent or uwot is claimed).  X: n rows of d values, row i at X + i * ld, every |x| <= 1e100 (NA / NaN / Inf refused by row and
+ * column); 1 <= K <= 255, K <= n - 1, n < 2^31.  idx (n x K, 0-based) / dist2 (n x K): each row's list, self excluded, no index twice,
+ * sorted by (distance, index) with ties to the lower index; dist2 = sum (x_i - x_j)^2 summed in column order, bitwise what sharp_tsne_knn
+ * returns for the same pair.  The lists are a pure function of the arguments: bitwise reproducible.
+ * sharp_knn_descent: the start (n_projections in 1 .. 32 sorted random projections; each row is offered the K rows on either side of it
+ * in each order), then at most n_iters >= 0 joins with max_candidates (1 .. 255; 0: min(K, 30)) sampled reverse neighbours, stopping
+ * when a join changes <= delta n K entries (0 <= delta <= 1).  seed: a whole number in [0, 2^53).  info (NULL or four values): joins
+ * run, entries the last join changed, stop reason (0: n_iters reached, 1: the delta rule), candidate rows the joins gathered.  With K = n - 1 the lists are the exact ones.
+ * Stages (tests, tools): _start: the start alone.  _join: join number `iteration` (>= 1) from the caller's lists `index` (n x K, 0-based,
+ * validated as sharp_tsne_neighbors validates them, any order: they are measured and sorted first); *updates (NULL or one value): the
+ * entries that changed.  max_rows_per_launch (0: the library's choice) only cuts the work into launches; no result depends on it. */
+int sharp_knn_descent(const double *X, long long n, int d, long long ld, int K, int n_projections, int max_candidates, int n_iters,
+                      double delta, double seed, int *idx, double *dist2, long long *info);
+int sharp_knn_descent_start(const double *X, long long n, int d, long long ld, int K, int n_projections, double seed, int max_rows_per_launch,
+                            int *idx, double *dist2);
+int sharp_knn_descent_join(const double *X, long long n, int d, long long ld, int K, const int *index, int max_candidates, int iteration,
+                           double seed, int max_rows_per_launch, int *idx, double *dist2, long long *updates);
+
 /* ---- UMAP beside t-SNE (uwot::umap's arguments; DESIGN.md §13 is the specification: this project's, modelled on umap-learn's algorithm
  * and uwot's batch = TRUE mode, with no bit parity claimed).  Euclidean metric, set_op_mix_ratio = local_connectivity = bandwidth = 1.
  * sharp_umap_ab: a, b minimising sum (1 / (1 + a x^(2b)) - y(x))^2 over x = linspace(0, 3 spread, 300), y = 1 below min_dist, else
@@ -644,6 +663,9 @@ void sharp_C_tsne_dist(double *d, int *n, int *repulsion, int *dims, double *per
                        int *mom_switch_iter, double *momentum, double *final_momentum, double *eta, double *exaggeration, int *has_Y_init,
                        double *Y_init, double *seed, double *Y, double *itercosts, double *costs, int *status);
 void sharp_C_tsne_knn(double *X, double *n, int *d, int *K, int *idx, double *dist, int *status);
+/* sharp_knn_descent in the same convention; info: a numeric(4) (joins run, entries the last join changed, stop reason, rows gathered) */
+void sharp_C_knn_descent(double *X, double *n, int *d, int *K, int *n_projections, int *max_candidates, int *n_iters, double *delta,
+                         double *seed, int *idx, double *dist2, double *info, int *status);
 /* sharp_tsne_bh in the same convention: sharp_C_tsne's arguments, theta honoured */
 void sharp_C_tsne_bh(double *X, double *n, int *d, int *dims, int *initial_dims, int *pca, int *pca_center, int *pca_scale, int *normalize,
                      int *check_duplicates, double *perplexity, double *theta, int *max_iter, int *stop_lying_iter, int *mom_switch_iter,

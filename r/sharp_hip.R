@@ -386,16 +386,30 @@ sharp_Rtsne_neighbors <- function(index, distance, dims = 2, perplexity = 30, th
                      exaggeration_factor)
 }
 
-# the exact K nearest neighbours Rtsne itself computes: list(index = n x K, 1-based; distance = n x K Euclidean, or squared), each row
+# the K nearest neighbours Rtsne itself computes: list(index = n x K, 1-based; distance = n x K Euclidean, or squared), each row
 # sorted by (distance, index), ties to the lower index.  Computed once, they serve every later sharp_Rtsne_neighbors call on the data.
-sharp_knn <- function(X, K, squared = FALSE) {
+# method = "exact" (the default): the exact lists.  method = "descent" ("nndescent"): the approximate lists of NN-descent on the GPU
+# (DESIGN.md 16; sharp_C_knn_descent) in the same layout -- every kept pair with the exact search's distance bits -- with
+# attr(, "info") = list(joins, updates, reason); max_candidates NULL: min(K, 30); seed a whole number.
+sharp_knn <- function(X, K, squared = FALSE, method = "exact", n_projections = 8L, max_candidates = NULL, n_iters = 12L, delta = 0.001,
+                      seed = 10) {
     X <- .sharp_dmat(X)
     n <- nrow(X)
-    r <- .C("sharp_C_tsne_knn", as.double(t(X)), as.double(n), ncol(X), as.integer(K), idx = integer(n * K), dist = double(n * K),
-            status = integer(1))
+    if (!method %in% c("exact", "descent", "nndescent")) stop("sharp_knn: method must be \"exact\" or \"descent\" (\"nndescent\")")
+    if (method == "exact") {
+        r <- .C("sharp_C_tsne_knn", as.double(t(X)), as.double(n), ncol(X), as.integer(K), idx = integer(n * K), dist = double(n * K),
+                status = integer(1))
+    } else {
+        r <- .C("sharp_C_knn_descent", as.double(t(X)), as.double(n), ncol(X), as.integer(K), as.integer(n_projections),
+                as.integer(if (is.null(max_candidates)) 0L else max_candidates), as.integer(n_iters), as.double(delta), as.double(seed),
+                idx = integer(n * K), dist = double(n * K), info = double(4), status = integer(1))
+    }
     .sharp_check(r$status)
     d2 <- matrix(r$dist, n, K, byrow = TRUE)
-    list(index = matrix(r$idx, n, K, byrow = TRUE) + 1L, distance = if (squared) d2 else sqrt(d2))
+    out <- list(index = matrix(r$idx, n, K, byrow = TRUE) + 1L, distance = if (squared) d2 else sqrt(d2))
+    if (method != "exact")
+        attr(out, "info") <- list(joins = r$info[1], updates = r$info[2], reason = c("n_iters", "delta")[r$info[3] + 1], gathered = r$info[4])
+    out
 }
 
 # ---- uwot::umap beside Rtsne (DESIGN.md 13) -------------------------------------------------------------------------------------------------

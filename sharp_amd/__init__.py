@@ -5,7 +5,7 @@ Python mirror of the reference's exported R functions on that path; all compute 
 in libsharp_hip.so (hand-written HIP for gfx950) through its C ABI (include/sharp_hip.h)."""
 from ._lib import SharpError, init, lib, reload_options, shutdown, so_path  # noqa: F401
 from .api import *  # noqa: F401,F403
-from .tsne import Rtsne, Rtsne_neighbors, knn  # noqa: F401
+from .tsne import Rtsne, Rtsne_neighbors, knn, knn_descent  # noqa: F401
 from .umap import UmapModel, knn_query, umap, umap_ab, umap_neighbors, umap_transform  # noqa: F401
 from .tree import get_percluster_exp, hclust, plot_markers  # noqa: F401
 from .validity import calinski_harabasz, cutree, silhouette  # noqa: F401

@@ -995,12 +995,13 @@ def _vis_neighbors_n(y, neighbors, w):
     return n
 
 
-def _vis_umap(y, label, w, filename, filetype, legendtitle, width, height, res, plot, neighbors, return_neighbors, kwargs):
+def _vis_umap(y, label, w, filename, filetype, legendtitle, width, height, res, plot, neighbors, return_neighbors, kwargs, descent=False,
+              nn_args=None):
     """visualization_SHARP(method="umap"): x1 prepared as for Rtsne, then umap() on it, or umap_neighbors() on the first
     n_neighbors - 1 columns of given lists; the start is the PCA of the prepared x1 either way unless init says otherwise"""
     import time as _t
 
-    from .tsne import _prepare
+    from .tsne import _prepare, knn_descent
     from .umap import umap, umap_neighbors
 
     t0 = _t.time()
@@ -1029,6 +1030,11 @@ def _vis_umap(y, label, w, filename, filetype, legendtitle, width, height, res, 
             raise SharpError("umap: init = \"pca\" needs at least n_components columns")
         kw["init"] = _prepare(xp, pca=True, initial_dims=dims, pca_center=True, pca_scale=False, normalize=False)
     nb = None
+    if neighbors is None and descent:                                # (the approximate lists, then the branch given lists take)
+        if not 2 <= n_neighbors <= 256 or n_neighbors >= n:
+            raise SharpError("umap: n_neighbors must be in 2 .. 256 and smaller than the number of rows")
+        idx, dd = knn_descent(xp, n_neighbors - 1, **dict(nn_args or {}, squared=False, ret_info=False))
+        neighbors = {"index": idx, "distance": dd, "squared": False, "w": w, "n": n, "method": "descent"}
     if neighbors is None:
         out = umap(xp, n_neighbors=n_neighbors, ret_nn=return_neighbors, **kw)
         if return_neighbors:
@@ -1053,7 +1059,8 @@ def _vis_umap(y, label, w, filename, filetype, legendtitle, width, height, res, 
 
 
 def visualization_SHARP(y, label=None, w=2, filename=None, filetype=None, n_cores=None, legendtitle="Cell Type", width=9.5, height=8.5,
-                        res=400, plot=True, neighbors=None, return_neighbors=False, method="tsne", **tsne_kwargs):
+                        res=400, plot=True, neighbors=None, return_neighbors=False, method="tsne", nn_method="exact", nn_args=None,
+                        **tsne_kwargs):
     """R/visualization_SHARP.R:31-177: the 2-D t-SNE map of a SHARP() / SHARP_unlimited() result.
 
     x1 = cbind(w * scale(x0), scale(viE)) (w >= 100: x0 with jitter; w <= 0.01: viE alone) goes to Rtsne(x1, check_duplicates = FALSE,
@@ -1072,13 +1079,21 @@ def visualization_SHARP(y, label=None, w=2, filename=None, filetype=None, n_core
     method="umap" draws the same figure from sharp_amd.umap.umap instead (the keyword arguments are then umap's): the same x1, prepared
     as for Rtsne (pca = 50 when ncol(x1) > 50), "Y", "a", "b" and "n_epochs" in the result, no "itercosts".  neighbors= /
     return_neighbors= work alike, and the lists do not depend on the method: those a t-SNE call returned serve a UMAP map (their first
-    n_neighbors - 1 columns) and the other way round, as far as they are wide enough."""
+    n_neighbors - 1 columns) and the other way round, as far as they are wide enough.
+
+    nn_method="descent" ("nndescent"), for both methods: where the call would run the exact k-NN it runs knn_descent() instead
+    (approximate lists; nn_args: its keywords) and goes on as a call with given neighbors does.  The "neighbors" dict
+    it returns then also holds "method": "descent" (the exact search's dict is unchanged); a dict passed as neighbors= is used as it is."""
     import time as _t
 
-    from .tsne import Rtsne, Rtsne_neighbors, _knn, _prepare
+    from .tsne import Rtsne, Rtsne_neighbors, _knn, _nn_method, _prepare, knn_descent
 
+    descent = _nn_method(nn_method, "visualization_SHARP") == "descent"
+    if nn_args and not descent:
+        raise SharpError("visualization_SHARP: nn_args belong to nn_method = \"descent\"")
     if method == "umap":
-        return _vis_umap(y, label, w, filename, filetype, legendtitle, width, height, res, plot, neighbors, return_neighbors, tsne_kwargs)
+        return _vis_umap(y, label, w, filename, filetype, legendtitle, width, height, res, plot, neighbors, return_neighbors, tsne_kwargs,
+                         descent, nn_args)
     if method != "tsne":
         raise SharpError(f"visualization_SHARP: method must be \"tsne\" or \"umap\", not {method!r}")
     t0 = _t.time()
@@ -1094,7 +1109,7 @@ def visualization_SHARP(y, label=None, w=2, filename=None, filetype=None, n_core
         filename = f"vi_SHARP.{filetype}"
     kw.setdefault("seed", 10)                                         # set.seed(10), R/visualization_SHARP.R:85
     nb = None
-    if neighbors is None and not return_neighbors:
+    if neighbors is None and not return_neighbors and not descent:
         kw.setdefault("check_duplicates", False)
         kw.setdefault("pca", x1.shape[1] > 50)
         out = Rtsne(x1, **kw)
@@ -1110,8 +1125,13 @@ def visualization_SHARP(y, label=None, w=2, filename=None, filetype=None, n_core
             if n - 1 < 3 * kw.get("perplexity", 30):
                 raise SharpError("Perplexity is too large.")
             prep.setdefault("pca", x1.shape[1] > 50)
-            idx, d2 = _knn(_prepare(x1, **prep), K)
+            if descent:
+                idx, d2 = knn_descent(_prepare(x1, **prep), K, **dict(nn_args or {}, squared=True, ret_info=False))
+            else:
+                idx, d2 = _knn(_prepare(x1, **prep), K)
             nb = {"index": idx, "distance": d2, "squared": True, "w": w, "n": n}
+            if descent:                                              # (the exact search's dict stays as it always was)
+                nb["method"] = "descent"
         else:
             nb = neighbors
             idx, d2 = np.asarray(nb["index"]), np.asarray(nb["distance"])

@@ -264,6 +264,13 @@ void sharp_C_tsne_dist(double *d, int *n, int *repulsion, int *dims, double *per
 void sharp_C_tsne_knn(double *X, double *n, int *d, int *K, int *idx, double *dist, int *status) {
     *status = sharp_tsne_knn(X, as_ll(n), *d, static_cast<long long>(*d), *K, idx, dist);
 }
+void sharp_C_knn_descent(double *X, double *n, int *d, int *K, int *n_projections, int *max_candidates, int *n_iters, double *delta,
+                         double *seed, int *idx, double *dist2, double *info, int *status) {
+    long long inf[4] = {0, 0, 0, 0};
+    *status = sharp_knn_descent(X, as_ll(n), *d, static_cast<long long>(*d), *K, *n_projections, *max_candidates, *n_iters, *delta, *seed, idx,
+                                dist2, inf);
+    for (int k = 0; k < 4; ++k) info[k] = static_cast<double>(inf[k]);
+}
 
 /* ---- uwot::umap beside Rtsne (sharp_umap, sharp_umap_neighbors, sharp_umap_ab): X = as.double(t(X)); index 0-based, n x K row-major */
 void sharp_C_umap(double *X, double *n, int *d, int *n_neighbors, int *dims, int *n_epochs, double *learning_rate, double *min_dist,

@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, f64, i32, i64, lib
 
-__all__ = ["Rtsne", "Rtsne_neighbors", "knn"]
+__all__ = ["Rtsne", "Rtsne_neighbors", "knn", "knn_descent"]
 
 
 def _rows(X):
@@ -93,7 +93,7 @@ def _optimise(entry, head, n, dims, origD, pca, normalize, perplexity, theta, ma
 def Rtsne(X, dims=2, initial_dims=50, perplexity=30, theta=0.5, check_duplicates=True, pca=True, partial_pca=False, max_iter=1000,
           verbose=False, is_distance=False, Y_init=None, pca_center=True, pca_scale=False, normalize=True, stop_lying_iter=None,
           mom_switch_iter=None, momentum=0.5, final_momentum=0.8, eta=200.0, exaggeration_factor=12.0, num_threads=1, seed=10,
-          repulsion="exact"):
+          repulsion="exact", nn_method="exact", nn_args=None):
     """Rtsne(X, ...) with Rtsne's arguments and defaults; returns Rtsne's list as a dict
     (Y, itercosts, costs, N, origD, perplexity, theta, max_iter, ...).
 
@@ -110,8 +110,35 @@ def Rtsne(X, dims=2, initial_dims=50, perplexity=30, theta=0.5, check_duplicates
     is_distance=True: X is a dist vector of length n (n - 1) / 2 (what sharp_amd.dist returns) or an n x n matrix, n <= 46340.  A matrix
     must equal its transpose exactly; its diagonal is ignored.  Every distance must be finite and >= 0.  The floor(3 perplexity)
     nearest objects of each are selected on the distances as given (ties to the lower index) and P is built from their squares.
-    pca, initial_dims, normalize and check_duplicates are ignored for a distance input, and origD is None."""
+    pca, initial_dims, normalize and check_duplicates are ignored for a distance input, and origD is None.
+
+    nn_method="descent" ("nndescent"): the neighbours come from knn_descent() (approximate; nn_args: its keywords) instead
+    of the exact search.  The stages are composed here -- prepare, knn_descent, Rtsne_neighbors -- so the map is bitwise what
+    Rtsne_neighbors gives on knn(prepared X, floor(3 perplexity), squared=True, method="descent"); check_duplicates then looks at each
+    row's nearest kept neighbour.  Not together with is_distance."""
     _check_repulsion(repulsion)
+    if _nn_method(nn_method, "Rtsne") == "descent":
+        if is_distance:
+            raise _lib.SharpError("Rtsne: nn_method = \"descent\" needs the rows of X; it is not built together with is_distance")
+        if not (np.isfinite(perplexity) and perplexity > 0):
+            raise _lib.SharpError("Rtsne: perplexity must be positive")
+        if perplexity > 85:
+            raise _lib.SharpError("Rtsne: perplexity above 85 is not supported (at most 255 neighbours per row)")
+        X = _rows(X)
+        if X.shape[0] - 1 < 3 * perplexity:
+            raise _lib.SharpError("Perplexity is too large.")
+        xp = _prepare(X, pca=pca, initial_dims=initial_dims, pca_center=pca_center, pca_scale=pca_scale, normalize=normalize)
+        idx, d2 = knn_descent(xp, int(np.floor(3 * perplexity)), squared=True, **dict(nn_args or {}, ret_info=False))
+        if check_duplicates and (d2[:, 0] == 0).any():
+            raise _lib.SharpError("Remove duplicates before running TSNE.")
+        out = Rtsne_neighbors(idx, d2, dims=dims, perplexity=perplexity, theta=theta, max_iter=max_iter, Y_init=Y_init,
+                              stop_lying_iter=stop_lying_iter, mom_switch_iter=mom_switch_iter, momentum=momentum,
+                              final_momentum=final_momentum, eta=eta, exaggeration_factor=exaggeration_factor, seed=seed,
+                              repulsion=repulsion, squared=True)
+        out.update(origD=min(int(initial_dims), X.shape[1]) if pca else X.shape[1], pca=bool(pca), normalize=bool(normalize))
+        return out
+    if nn_args:
+        raise _lib.SharpError("Rtsne: nn_args belong to nn_method = \"descent\"")
     if is_distance:
         d, n = _condensed(X, "Rtsne")
     else:
@@ -173,13 +200,70 @@ def Rtsne_neighbors(index, distance, dims=2, perplexity=30, theta=0.5, max_iter=
                      mom_switch_iter, momentum, final_momentum, eta, exaggeration_factor, Y_init, seed)
 
 
-def knn(X, K, squared=False, is_distance=False):
-    """The K exact nearest neighbours of every row: (index (n, K) int32, 0-based; distance (n, K)), self excluded, ties to the lower
+_NN_METHODS = {"exact": "exact", "descent": "descent", "nndescent": "descent"}      # ("nndescent": uwot's spelling)
+
+
+def _nn_method(nn_method, who):
+    if nn_method not in _NN_METHODS:
+        raise _lib.SharpError(f"{who}: nn_method must be \"exact\" or \"descent\" (\"nndescent\"), not {nn_method!r}")
+    return _NN_METHODS[nn_method]
+
+
+def knn_descent(X, K, squared=False, n_projections=8, max_candidates=None, n_iters=12, delta=0.001, seed=10, ret_info=False):
+    """The approximate K nearest neighbours of every row by NN-descent on the GPU (sharp_knn_descent), in knn()'s format:
+    (index (n, K) int32, 0-based; distance (n, K)), self excluded, no index twice, each row sorted by (distance, index).  Every pair a list
+    keeps carries bitwise the distance knn() gives that pair; what is approximate is which rows a list holds.  The start offers each row
+    the K rows on either side of it in each of n_projections (1 .. 32) sorted random projections; then at most n_iters joins over
+    max_candidates (1 .. 255; None: min(K, 30)) sampled reverse neighbours, until a join changes <= delta n K entries.  The lists are a
+    pure function of the arguments (seed: a whole number in [0, 2^53)): two calls give the same bits.  With K = n - 1 they are the exact
+    lists.  ret_info=True adds {"joins", "updates", "reason": "n_iters" / "delta", "gathered" (the candidate rows the joins measured),
+    "method": "descent"}.  1 <= K <= 255, K <= n - 1."""
+    who = "knn_descent"
+    X = _rows(X)
+    K = int(K)
+    n, d = X.shape
+    if not 1 <= K <= 255:
+        raise _lib.SharpError(f"{who}: K must be in 1 .. 255")
+    if K > n - 1:
+        raise _lib.SharpError(f"{who}: K neighbours per row need K <= n - 1")
+    if not 1 <= int(n_projections) <= 32:
+        raise _lib.SharpError(f"{who}: n_projections must be in 1 .. 32")
+    S = 0 if max_candidates is None else int(max_candidates)
+    if max_candidates is not None and not 1 <= S <= 255:
+        raise _lib.SharpError(f"{who}: max_candidates must be in 1 .. 255 (None: min(K, 30))")
+    if int(n_iters) < 0:
+        raise _lib.SharpError(f"{who}: n_iters must be >= 0")
+    if not 0 <= float(delta) <= 1:                                    # (false for NaN too)
+        raise _lib.SharpError(f"{who}: delta must be in [0, 1]")
+    _lib.ensure_init()
+    idx = np.zeros((n, K), np.int32)
+    d2 = np.zeros((n, K))
+    info = np.zeros(4, np.int64)
+    check(lib().sharp_knn_descent(f64(X), n, int(d), d, K, int(n_projections), S, int(n_iters), float(delta), float(seed), i32(idx), f64(d2),
+                                  i64(info)))
+    out = (idx, d2) if squared else (idx, np.sqrt(d2))
+    if ret_info:
+        return out + ({"joins": int(info[0]), "updates": int(info[1]), "reason": ("n_iters", "delta")[int(info[2])], "gathered": int(info[3]),
+                       "method": "descent"},)
+    return out
+
+
+def knn(X, K, squared=False, is_distance=False, method="exact", **descent_args):
+    """The K nearest neighbours of every row: (index (n, K) int32, 0-based; distance (n, K)), self excluded, ties to the lower
     index, each row sorted by (distance, index).  From the rows of X (the k-NN Rtsne itself runs; Euclidean distances, or their squares
     sum (x_i - x_j)^2 with squared=True), or with is_distance=True from a dist vector or a square matrix as Rtsne(is_distance=True)
     takes it: then the selection is on the distances as given, and they are returned as given (squared=True: their squares).
-    1 <= K <= 255, K <= n - 1.  The lists suit every perplexity <= K / 3 of Rtsne_neighbors."""
+    1 <= K <= 255, K <= n - 1.  The lists suit every perplexity <= K / 3 of Rtsne_neighbors.
+    method="exact" (the default): the exact lists, O(n^2 d).  method="descent" ("nndescent"): knn_descent()'s approximate lists in the
+    same format, its arguments as keywords (n_projections, max_candidates, n_iters, delta, seed); not together with is_distance."""
     K = int(K)
+    if _nn_method(method, "knn") == "descent":
+        if is_distance:
+            raise _lib.SharpError("knn: method = \"descent\" needs the rows of X; it is not built together with is_distance")
+        descent_args.pop("ret_info", None)
+        return knn_descent(X, K, squared=squared, **descent_args)
+    if descent_args:
+        raise _lib.SharpError(f"knn: {sorted(descent_args)} belong to method = \"descent\"")
     if is_distance:
         d, n = _condensed(X, "knn")
         if not 1 <= K <= min(255, n - 1):
@@ -221,6 +305,35 @@ def _knn(X, K):
     dist = np.zeros((n, K))
     check(lib().sharp_tsne_knn(f64(X), n, d, d, int(K), i32(idx), f64(dist)))
     return idx, dist
+
+
+def _knn_descent_start(X, K, n_projections=8, seed=10, max_rows_per_launch=0):
+    """knn_descent's start alone (sharp_knn_descent_start): (index, squared distance)"""
+    X = _rows(X)
+    n, d = X.shape
+    _lib.ensure_init()
+    idx = np.zeros((n, int(K)), np.int32)
+    d2 = np.zeros((n, int(K)))
+    check(lib().sharp_knn_descent_start(f64(X), n, int(d), d, int(K), int(n_projections), float(seed), int(max_rows_per_launch), i32(idx),
+                                        f64(d2)))
+    return idx, d2
+
+
+def _knn_descent_join(X, index, max_candidates=None, iteration=1, seed=10, max_rows_per_launch=0):
+    """one join from given lists (sharp_knn_descent_join): (index, squared distance, entries that changed)"""
+    X = _rows(X)
+    n, d = X.shape
+    index = np.ascontiguousarray(index, np.int32)
+    if index.ndim != 2 or index.shape[0] != n:
+        raise _lib.SharpError("knn_descent join: index must be an n x K matrix")
+    K = index.shape[1]
+    _lib.ensure_init()
+    idx = np.zeros((n, K), np.int32)
+    d2 = np.zeros((n, K))
+    upd = C.c_longlong()
+    check(lib().sharp_knn_descent_join(f64(X), n, int(d), d, int(K), i32(index), 0 if max_candidates is None else int(max_candidates),
+                                       int(iteration), float(seed), int(max_rows_per_launch), i32(idx), f64(d2), C.byref(upd)))
+    return idx, d2, upd.value
 
 
 def _affinities_nn(index, distance, perplexity, squared=False):

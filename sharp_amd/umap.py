@@ -95,7 +95,8 @@ def _init_info(who):
 
 def umap(X, n_neighbors=15, n_components=2, metric="euclidean", n_epochs=None, learning_rate=1.0, init="pca", spread=1.0, min_dist=0.01,
          set_op_mix_ratio=1.0, local_connectivity=1.0, bandwidth=1.0, repulsion_strength=1.0, negative_sample_rate=5, a=None, b=None,
-         pca=None, pca_center=True, seed=10, ret_nn=False, n_threads=None, n_sgd_threads=0, verbose=False, batch=True, ret_model=False):
+         pca=None, pca_center=True, seed=10, ret_nn=False, n_threads=None, n_sgd_threads=0, verbose=False, batch=True, ret_model=False,
+         nn_method="exact", nn_args=None):
     """umap(X, ...) with uwot's arguments and defaults; returns {"Y", "a", "b", "n_epochs", "n_neighbors", "N"} and, with ret_nn,
     "nn": {"index", "distance"} (the exact k-NN lists: n x (n_neighbors - 1), 0-based, Euclidean, self excluded); with ret_model,
     "model": a UmapModel of (X, Y) for umap_transform (n_neighbors up to 255; not together with pca).
@@ -108,8 +109,21 @@ def umap(X, n_neighbors=15, n_components=2, metric="euclidean", n_epochs=None, l
     (centred when pca_center).  a, b: None fits them from (spread, min_dist).  Only metric = "euclidean" and set_op_mix_ratio =
     local_connectivity = bandwidth = 1 are built: anything else is refused.  n_threads, n_sgd_threads, verbose and batch are accepted
     and ignored (the update is always the batch form: every row moves at once from the epoch's old positions).  Input NA / NaN / Inf
-    is refused.  Two calls with the same input and seed give bitwise-identical Y on the same GPU."""
+    is refused.  Two calls with the same input and seed give bitwise-identical Y on the same GPU.
+
+    nn_method="descent" (uwot's "nndescent" too): the lists come from knn_descent() (approximate; nn_args: its
+    keywords) instead of the exact search.  The stages are composed here -- the PCA if asked for, knn_descent, umap_neighbors, the "pca"
+    start computed from the data as a matrix -- so the map is bitwise umap_neighbors' on knn(X, n_neighbors - 1, method="descent");
+    ret_nn returns the approximate lists (and "nn"["method"]), ret_model works as before."""
     who = "umap"
+    from .tsne import _nn_method
+
+    if _nn_method(nn_method, who) == "descent":
+        return _umap_descent(X, n_neighbors, n_components, metric, n_epochs, learning_rate, init, spread, min_dist, set_op_mix_ratio,
+                             local_connectivity, bandwidth, repulsion_strength, negative_sample_rate, a, b, pca, pca_center, seed, ret_nn,
+                             ret_model, nn_args)
+    if nn_args:
+        raise _lib.SharpError(f"{who}: nn_args belong to nn_method = \"descent\"")
     _refuse_unbuilt(who, metric, set_op_mix_ratio, local_connectivity, bandwidth)
     X = _rows(X, who)
     n, d = X.shape
@@ -144,6 +158,47 @@ def umap(X, n_neighbors=15, n_components=2, metric="euclidean", n_epochs=None, l
         out["nn"] = {"index": nn_i, "distance": nn_d}
     if ret_model:
         out["model"] = UmapModel(X, Y, n_neighbors, out["a"], out["b"], n_epochs)
+    return out
+
+
+def _umap_descent(X, n_neighbors, n_components, metric, n_epochs, learning_rate, init, spread, min_dist, set_op_mix_ratio,
+                  local_connectivity, bandwidth, repulsion_strength, negative_sample_rate, a, b, pca, pca_center, seed, ret_nn, ret_model,
+                  nn_args):
+    """umap(nn_method="descent"): umap()'s checks, then prepare, knn_descent and umap_neighbors"""
+    from .tsne import _prepare, knn_descent
+
+    who = "umap"
+    _refuse_unbuilt(who, metric, set_op_mix_ratio, local_connectivity, bandwidth)
+    X = _rows(X, who)
+    n, d = X.shape
+    n_neighbors = int(n_neighbors)
+    if not 2 <= n_neighbors <= 256:
+        raise _lib.SharpError(f"{who}: n_neighbors must be in 2 .. 256")
+    if n_neighbors >= n:
+        raise _lib.SharpError(f"{who}: n_neighbors must be smaller than the number of rows")
+    dims = _common(who, n, n_components, n_epochs, init, a, b, True)[0]
+    pca = 0 if pca is None else int(pca)
+    if pca < 0:
+        raise _lib.SharpError(f"{who}: pca must be None or a positive number of components")
+    if ret_model and pca:
+        raise _lib.SharpError(f"{who}: ret_model is not built together with pca (the PCA's rotation is not kept, so new rows could not be "
+                              "brought into the model's space): reduce the data first and give pca = None")
+    if ret_model and n_neighbors > 255:
+        raise _lib.SharpError(f"{who}: ret_model needs n_neighbors <= 255 (a model's lists hold n_neighbors reference rows)")
+    pca_start = isinstance(init, str) and init == "pca"
+    if pca_start and (min(pca, d) if pca else d) < dims:
+        raise _lib.SharpError(f"{who}: init = \"pca\" needs at least n_components columns")
+    xp = _prepare(X, pca=True, initial_dims=pca, pca_center=pca_center, pca_scale=False, normalize=False) if pca else X
+    if pca_start:
+        init = _prepare(xp, pca=True, initial_dims=dims, pca_center=True, pca_scale=False, normalize=False)
+    idx, dist = knn_descent(xp, n_neighbors - 1, **dict(nn_args or {}, squared=False, ret_info=False))
+    out = umap_neighbors(idx, dist, n_components=dims, n_epochs=n_epochs, learning_rate=learning_rate, init=init, spread=spread,
+                         min_dist=min_dist, repulsion_strength=repulsion_strength, negative_sample_rate=negative_sample_rate, a=a, b=b,
+                         seed=seed)
+    if ret_nn:
+        out["nn"] = {"index": idx, "distance": dist, "method": "descent"}
+    if ret_model:
+        out["model"] = UmapModel(X, out["Y"], n_neighbors, out["a"], out["b"], out["n_epochs"])
     return out
 
 
