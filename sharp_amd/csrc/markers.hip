@@ -236,6 +236,7 @@ void marker_genes_blocks_dev(const std::vector<MgBlock> &blocks, int m, const in
     {
         KernelTimer t("marker_count");
         for (const MgBlock &b : blocks) {
+            if (b.n == 0) continue;                            // a block without cells: nothing to count (and a dense grid of 0 is no launch)
             if (b.dX) {
                 int cpb = 0;
                 const dim3 grid = dense_grid(b, cpb);
@@ -262,6 +263,7 @@ void marker_genes_blocks_dev(const std::vector<MgBlock> &blocks, int m, const in
         KernelTimer t("marker_fill");
         long long c0 = 0;
         for (const MgBlock &b : blocks) {
+            if (b.n == 0) continue;
             if (b.dX) {
                 int cpb = 0;
                 const dim3 grid = dense_grid(b, cpb);
