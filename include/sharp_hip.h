@@ -560,6 +560,16 @@ int sharp_silhouette(const double *x, long long n, int p, long long ld, int dist
  * correlation in both sums).  O(n p), 3 <= n <= 16777216, 2 <= k <= n - 1; W == 0 gives +Inf as in R. */
 int sharp_calinski_harabasz(const double *x, long long n, int p, long long ld, const int *cl, int k, int kind, double *out);
 
+/* ---- Scores of a map: neighbour ranks (sharp_amd/csrc/neighbor_rank.hip) --------------------------------------
+ * X: n rows of d values (row-major, ld >= d); index: n x K row-major, 0-based, each row K other rows (sharp_tsne_knn's list format),
+ * validated as sharp_tsne_neighbors validates an index (range, no row naming itself, no index twice in a row).
+ * rank_out[i * K + k] = 1 + the number of rows l != i with (d2(i, l), l) < (d2(i, j), j) lexicographically, j = index[i * K + k], where
+ * d2 is the direct sum of (x_ic - x_lc)^2 in column order, bitwise the squared distance sharp_tsne_knn gives the pair: 1 .. n - 1, ties
+ * to the lower index.  Matrix-free, O(n^2 d); everything the device computes is an integer, so two calls give the same bits whatever
+ * the launch split.  3 <= n <= 16777216, d >= 1, 1 <= K <= 255, K <= n - 1, |x| <= 1e100 (NA / NaN / Inf and larger values are refused
+ * by row and column).  max_rows_per_launch: 0 = by the library's pair budget (a test forces a split with a small value). */
+int sharp_neighbor_ranks(const double *X, long long n, int d, long long ld, int K, const int *index, int max_rows_per_launch, int *rank_out);
+
 /* ---- synthetic inputs (bench / tests; not part of the reference) ------------ */
 /* Counter-based generator, value = f(seed, gene, cell): bit-identical to
  * oracle_synth_value().  Fills dX (fp32, m x ncell column-major, leading dim ld). */
@@ -706,6 +716,8 @@ void sharp_C_silhouette_dist(double *d, int *n, int *cl, int *k, int *neighbor, 
 void sharp_C_silhouette(double *x, double *n, int *p, int *dist_method, double *minkowski_p, int *cl, int *k, int *neighbor, double *width,
                         int *status);
 void sharp_C_calinski_harabasz(double *x, double *n, int *p, int *cl, int *k, int *kind, double *out, int *status);
+/* sharp_neighbor_ranks in the same convention: X = as.double(t(X)), n as double, index 0-based (r/sharp_hip.R subtracts 1) */
+void sharp_C_neighbor_ranks(double *X, double *n, int *d, int *K, int *index, int *max_rows_per_launch, int *rank_out, int *status);
 
 #ifdef __cplusplus
 }

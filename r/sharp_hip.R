@@ -679,3 +679,35 @@ sharp_calinski_harabasz <- function(data, labels, distance = "euclidean") {
     .sharp_check(r$status)
     r$out
 }
+
+# ---- trustworthiness / continuity of a map (DESIGN.md 17) ---------------------------------------------------------------------------------
+# rank[i, k] = 1 + the number of rows l != i with (d2(i, l), l) < (d2(i, j), j), j = index[i, k]: where the rows a list names stand among
+# all rows of X, by sharp_knn's squared distances, ties to the lower index.  index: n x K, 1-based here (sharp_knn(X, K)$index), each row
+# K other rows.  Matrix-free on the GPU (sharp_C_neighbor_ranks): no n x n matrix.
+sharp_neighbor_ranks <- function(X, index, max_rows_per_launch = 0L) {
+    X <- .sharp_dmat(X)
+    n <- nrow(X)
+    if (is.list(index)) index <- index$index
+    index <- as.matrix(index)
+    if (nrow(index) != n) stop("the neighbour lists and the data differ in their number of rows")
+    K <- ncol(index)
+    r <- .C("sharp_C_neighbor_ranks", as.double(t(X)), as.double(n), ncol(X), as.integer(K), as.integer(t(index) - 1L),
+            as.integer(max_rows_per_launch), rank = integer(n * K), status = integer(1))
+    .sharp_check(r$status)
+    matrix(r$rank, n, K, byrow = TRUE)
+}
+
+.sharp_map_score <- function(ranked, listed, n_neighbors) {
+    n <- nrow(ranked)
+    K <- as.integer(n_neighbors)
+    if (nrow(listed) != n) stop("X and Y differ in their number of rows: a map has one row per row of X")
+    if (K >= n / 2) stop(sprintf("n_neighbors (%d) should be less than n_samples / 2 (%s)", K, format(n / 2)))
+    rank <- sharp_neighbor_ranks(ranked, sharp_knn(listed, K)$index)
+    penalty <- sum(as.numeric(pmax(rank - K, 0L)))                # (a double: exact far beyond any total that can occur)
+    1 - penalty * (2 / (as.numeric(n) * K * (2 * n - 3 * K - 1)))
+}
+
+# sklearn.manifold.trustworthiness(X, Y, n_neighbors) (Venna and Kaski): the ranks in X of each row's n_neighbors nearest rows in the
+# map Y; sharp_continuity: the ranks in Y of each row's nearest rows in X
+sharp_trustworthiness <- function(X, Y, n_neighbors = 5L) .sharp_map_score(.sharp_dmat(X), .sharp_dmat(Y), n_neighbors)
+sharp_continuity <- function(X, Y, n_neighbors = 5L) .sharp_map_score(.sharp_dmat(Y), .sharp_dmat(X), n_neighbors)

@@ -353,5 +353,8 @@ void sharp_C_silhouette(double *x, double *n, int *p, int *dist_method, double *
 void sharp_C_calinski_harabasz(double *x, double *n, int *p, int *cl, int *k, int *kind, double *out, int *status) {
     *status = sharp_calinski_harabasz(x, as_ll(n), *p, static_cast<long long>(*p), cl, *k, *kind, out);
 }
+void sharp_C_neighbor_ranks(double *X, double *n, int *d, int *K, int *index, int *max_rows_per_launch, int *rank_out, int *status) {
+    *status = sharp_neighbor_ranks(X, as_ll(n), *d, static_cast<long long>(*d), *K, index, *max_rows_per_launch, rank_out);
+}
 
 }  // extern "C"
