@@ -570,6 +570,41 @@ int sharp_calinski_harabasz(const double *x, long long n, int p, long long ld, c
  * by row and column).  max_rows_per_launch: 0 = by the library's pair budget (a test forces a split with a small value). */
 int sharp_neighbor_ranks(const double *X, long long n, int d, long long ld, int K, const int *index, int max_rows_per_launch, int *rank_out);
 
+/* ---- Louvain community detection on the neighbour graph (sharp_amd/csrc/louvain.hip) --------------------------
+ * The project's own synchronous form of the method: a call is a pure function of its arguments, and two calls give the same bits.
+ * The graph is a symmetric CSR: row_ptr (n + 1, from 0), col (0-based, strictly ascending within a row, no diagonal entry), val (finite,
+ * >= 0, <= 1e100, val[i,j] == val[j,i], at least one positive) -- what sharp_umap_graph returns.  2 <= n <= 16777216, nnz < 2^38.
+ * Weights become integers q = rint(val * 2^24 / max val) (entries with q = 0 are dropped) and every sum of weights is an int64 sum.
+ * resolution in (0, 1e6]; tol >= 0 (a round is kept when the modularity rises by more than tol); max_levels 1 .. 64, max_rounds
+ * 1 .. 100000 (rounds per level), max_fails 1 .. 64 (discarded rounds in a row that end a level); seed: a finite integer.
+ * membership[n]: 1 .. G by decreasing size, ties to the community with the smallest member.  Per level l < *n_levels (level_cap >=
+ * max_levels): level_n (vertices), level_communities, level_rounds, level_q (the modularity reached); the last level's are the
+ * result's.  level_membership: NULL, or level_cap * n ints: the 0-based coarse vertex of every input vertex after each level. */
+int sharp_louvain_graph(const long long *row_ptr, const int *col, const double *val, long long n, double resolution, double tol, int max_levels,
+                        int max_rounds, int max_fails, double seed, int *membership, int level_cap, long long *level_n,
+                        long long *level_communities, int *level_rounds, double *level_q, int *n_levels, int *level_membership);
+/* the same from neighbour lists (index, distance: n x K as sharp_umap_neighbors takes them): sharp_umap_graph's fuzzy union is built on
+ * the device and never leaves it */
+int sharp_louvain_neighbors(const int *index, const double *distance, long long n, int K, int squared, double resolution, double tol,
+                            int max_levels, int max_rounds, int max_fails, double seed, int *membership, int level_cap, long long *level_n,
+                            long long *level_communities, int *level_rounds, double *level_q, int *n_levels, int *level_membership);
+/* The stages one at a time (tests).  A level's graph is an integer-weighted CSR (q: int64 >= 0, self-loop entries allowed: a coarse
+ * vertex's internal weight); comm / membership: ids in [0, n).
+ * quantise: q (nnz, zeros kept in place), the strengths k (n) and 2m of a float-weighted graph.
+ * move: the proposals of one round (level, round >= 0) from the state comm.
+ * modularity: Q of a membership; give val (a float-weighted graph, quantised first: the public modularity) or q, the other NULL.
+ * aggregate: the coarse CSR of comm (row_ptr_out: room for n + 1, col_out / q_out: room for nnz), its entries, the number of
+ * communities, and new_out[c] = the coarse vertex of community c (-1: no member).
+ * row_caps: the longest row of the wave class and of the workgroup class of the move kernel. */
+int sharp_louvain_quantise(const long long *row_ptr, const int *col, const double *val, long long n, long long *q, long long *k, long long *m2);
+int sharp_louvain_move(const long long *row_ptr, const int *col, const long long *q, long long n, const int *comm, double resolution, double seed,
+                       int level, int round, int *proposal);
+int sharp_louvain_modularity(const long long *row_ptr, const int *col, const double *val, const long long *q, long long n, const int *membership,
+                             double resolution, double *Q);
+int sharp_louvain_aggregate(const long long *row_ptr, const int *col, const long long *q, long long n, const int *comm, long long *row_ptr_out,
+                            int *col_out, long long *q_out, long long *nnz_out, long long *nc_out, int *new_out);
+int sharp_louvain_row_caps(int *wave_cap, int *block_cap);
+
 /* ---- synthetic inputs (bench / tests; not part of the reference) ------------ */
 /* Counter-based generator, value = f(seed, gene, cell): bit-identical to
  * oracle_synth_value().  Fills dX (fp32, m x ncell column-major, leading dim ld). */
@@ -718,6 +753,16 @@ void sharp_C_silhouette(double *x, double *n, int *p, int *dist_method, double *
 void sharp_C_calinski_harabasz(double *x, double *n, int *p, int *cl, int *k, int *kind, double *out, int *status);
 /* sharp_neighbor_ranks in the same convention: X = as.double(t(X)), n as double, index 0-based (r/sharp_hip.R subtracts 1) */
 void sharp_C_neighbor_ranks(double *X, double *n, int *d, int *K, int *index, int *max_rows_per_launch, int *rank_out, int *status);
+/* sharp_louvain_graph / sharp_louvain_neighbors / sharp_louvain_modularity in the same convention: row_ptr (n + 1 values) and n as
+ * double, col and index 0-based; levels: a numeric matrix of level_cap rows x 4 (n, communities, rounds, modularity; row-major);
+ * want_levels = 0: level_membership is a buffer of length >= 1 that is left alone */
+void sharp_C_louvain_graph(double *row_ptr, int *col, double *val, double *n, double *resolution, double *tol, int *max_levels, int *max_rounds,
+                           int *max_fails, double *seed, int *membership, int *level_cap, double *levels, int *n_levels, int *want_levels,
+                           int *level_membership, int *status);
+void sharp_C_louvain_neighbors(int *index, double *distance, double *n, int *K, int *squared, double *resolution, double *tol, int *max_levels,
+                               int *max_rounds, int *max_fails, double *seed, int *membership, int *level_cap, double *levels, int *n_levels,
+                               int *want_levels, int *level_membership, int *status);
+void sharp_C_louvain_modularity(double *row_ptr, int *col, double *val, double *n, int *membership, double *resolution, double *Q, int *status);
 
 #ifdef __cplusplus
 }

@@ -711,3 +711,55 @@ sharp_neighbor_ranks <- function(X, index, max_rows_per_launch = 0L) {
 # map Y; sharp_continuity: the ranks in Y of each row's nearest rows in X
 sharp_trustworthiness <- function(X, Y, n_neighbors = 5L) .sharp_map_score(.sharp_dmat(X), .sharp_dmat(Y), n_neighbors)
 sharp_continuity <- function(X, Y, n_neighbors = 5L) .sharp_map_score(.sharp_dmat(Y), .sharp_dmat(X), n_neighbors)
+
+# ---- Louvain on the neighbour graph (DESIGN.md 18) -----------------------------------------------------------------------------------------
+.sharp_louvain_result <- function(r, n, ret_levels) {
+    nl <- r$n_levels
+    lev <- matrix(r$levels, ncol = 4, byrow = TRUE)[seq_len(nl), , drop = FALSE]
+    colnames(lev) <- c("n", "communities", "rounds", "modularity")
+    out <- list(membership = r$membership, n_communities = lev[nl, "communities"], modularity = lev[nl, "modularity"], levels = lev)
+    if (ret_levels) out$level_membership <- matrix(r$lm[seq_len(nl * n)], nl, n, byrow = TRUE) + 1L
+    out
+}
+
+# A clustering read off the neighbour graph, as sc.tl.louvain and Seurat's FindClusters run it: X (observations in rows; the exact
+# k-NN is sharp_knn's) or the lists sharp_knn returned (a list with $index, 1-based, and $distance).  membership: 1 .. G by decreasing
+# size; levels: one row (n, communities, rounds, modularity) per level.  The method is the project's own synchronous form of Louvain;
+# two calls give the same bits.
+sharp_louvain <- function(X, n_neighbors = 15L, resolution = 1, seed = 10, tol = 1e-7, max_levels = 20L, max_rounds = 200L, max_fails = 4L,
+                          ret_levels = FALSE) {
+    nn <- if (is.list(X) && !is.null(X$index)) X else sharp_knn(.sharp_dmat(X), as.integer(n_neighbors) - 1L)
+    index <- as.matrix(nn$index)
+    n <- nrow(index)
+    K <- ncol(index)
+    cap <- as.integer(max_levels)
+    r <- .C("sharp_C_louvain_neighbors", as.integer(t(index) - 1L), as.double(t(as.matrix(nn$distance))), as.double(n), as.integer(K), 0L,
+            as.double(resolution), as.double(tol), cap, as.integer(max_rounds), as.integer(max_fails), as.double(seed),
+            membership = integer(n), cap, levels = double(4 * cap), n_levels = integer(1), as.integer(ret_levels),
+            lm = integer(if (ret_levels) cap * n else 1L), status = integer(1))
+    .sharp_check(r$status)
+    .sharp_louvain_result(r, n, ret_levels)
+}
+
+# the same on any symmetric graph: a dgCMatrix-like triple (row_ptr 0-based with n + 1 values, col 0-based, val), e.g. an SNN graph
+sharp_louvain_graph <- function(row_ptr, col, val, resolution = 1, seed = 10, tol = 1e-7, max_levels = 20L, max_rounds = 200L,
+                                max_fails = 4L, ret_levels = FALSE) {
+    n <- length(row_ptr) - 1L
+    cap <- as.integer(max_levels)
+    r <- .C("sharp_C_louvain_graph", as.double(row_ptr), as.integer(col), as.double(val), as.double(n), as.double(resolution),
+            as.double(tol), cap, as.integer(max_rounds), as.integer(max_fails), as.double(seed), membership = integer(n), cap,
+            levels = double(4 * cap), n_levels = integer(1), as.integer(ret_levels), lm = integer(if (ret_levels) cap * n else 1L),
+            status = integer(1))
+    .sharp_check(r$status)
+    .sharp_louvain_result(r, n, ret_levels)
+}
+
+# Q of a labelling of that graph, on the integer weights and in the order sharp_louvain sums them
+sharp_modularity <- function(row_ptr, col, val, membership, resolution = 1) {
+    n <- length(row_ptr) - 1L
+    if (length(membership) != n) stop("membership must hold one label per vertex")
+    r <- .C("sharp_C_louvain_modularity", as.double(row_ptr), as.integer(col), as.double(val), as.double(n),
+            as.integer(factor(membership)) - 1L, as.double(resolution), Q = double(1), status = integer(1))
+    .sharp_check(r$status)
+    r$Q
+}

@@ -357,4 +357,47 @@ void sharp_C_neighbor_ranks(double *X, double *n, int *d, int *K, int *index, in
     *status = sharp_neighbor_ranks(X, as_ll(n), *d, static_cast<long long>(*d), *K, index, *max_rows_per_launch, rank_out);
 }
 
+/* Louvain on a graph or on neighbour lists (sharp_louvain_graph, sharp_louvain_neighbors, sharp_louvain_modularity): row_ptr and n as
+ * double; levels: level_cap rows of (n, communities, rounds, modularity) */
+static void louvain_levels_out(int status, int nl, const std::vector<long long> &ln, const std::vector<long long> &lc, const std::vector<int> &lr,
+                               const std::vector<double> &lq, double *levels) {
+    if (status != 0) return;
+    for (int l = 0; l < nl; ++l) {
+        levels[4 * l] = static_cast<double>(ln[l]);
+        levels[4 * l + 1] = static_cast<double>(lc[l]);
+        levels[4 * l + 2] = static_cast<double>(lr[l]);
+        levels[4 * l + 3] = lq[l];
+    }
+}
+void sharp_C_louvain_graph(double *row_ptr, int *col, double *val, double *n, double *resolution, double *tol, int *max_levels, int *max_rounds,
+                           int *max_fails, double *seed, int *membership, int *level_cap, double *levels, int *n_levels, int *want_levels,
+                           int *level_membership, int *status) {
+    const long long nn = as_ll(n);
+    const std::vector<long long> rp = row_ptr_ll(row_ptr, nn);
+    const size_t cap = *level_cap > 0 ? static_cast<size_t>(*level_cap) : 1;
+    std::vector<long long> ln(cap), lc(cap);
+    std::vector<int> lr(cap);
+    std::vector<double> lq(cap);
+    *status = sharp_louvain_graph(rp.data(), col, val, nn, *resolution, *tol, *max_levels, *max_rounds, *max_fails, *seed, membership, *level_cap,
+                                  ln.data(), lc.data(), lr.data(), lq.data(), n_levels, *want_levels ? level_membership : nullptr);
+    louvain_levels_out(*status, *n_levels, ln, lc, lr, lq, levels);
+}
+void sharp_C_louvain_neighbors(int *index, double *distance, double *n, int *K, int *squared, double *resolution, double *tol, int *max_levels,
+                               int *max_rounds, int *max_fails, double *seed, int *membership, int *level_cap, double *levels, int *n_levels,
+                               int *want_levels, int *level_membership, int *status) {
+    const size_t cap = *level_cap > 0 ? static_cast<size_t>(*level_cap) : 1;
+    std::vector<long long> ln(cap), lc(cap);
+    std::vector<int> lr(cap);
+    std::vector<double> lq(cap);
+    *status = sharp_louvain_neighbors(index, distance, as_ll(n), *K, *squared, *resolution, *tol, *max_levels, *max_rounds, *max_fails, *seed,
+                                      membership, *level_cap, ln.data(), lc.data(), lr.data(), lq.data(), n_levels,
+                                      *want_levels ? level_membership : nullptr);
+    louvain_levels_out(*status, *n_levels, ln, lc, lr, lq, levels);
+}
+void sharp_C_louvain_modularity(double *row_ptr, int *col, double *val, double *n, int *membership, double *resolution, double *Q, int *status) {
+    const long long nn = as_ll(n);
+    const std::vector<long long> rp = row_ptr_ll(row_ptr, nn);
+    *status = sharp_louvain_modularity(rp.data(), col, val, nullptr, nn, membership, *resolution, Q);
+}
+
 }  // extern "C"

@@ -392,6 +392,12 @@ void umap_epochs(const UmapGraph &G, double *dY, int dims, int n_epochs, int ep0
     stream_sync();   // (the second buffer goes out of scope)
 }
 
+void umap_sqrt_lists(DevBuf<double> &dist, long long n, int K) {
+    KernelTimer t("umap_sqrt");
+    hipLaunchKernelGGL(sqrt_kernel, dim3(grid_for(n * K, 256)), dim3(256), 0, ctx().stream, dist.p, n * K);
+    launch_check("sqrt_kernel");
+}
+
 }  // namespace sharp
 
 using namespace sharp;
@@ -411,11 +417,7 @@ void as_umap(const char *who, F f) {
     }
 }
 
-void sqrt_lists(DevBuf<double> &dist, long long n, int K) {
-    KernelTimer t("umap_sqrt");
-    hipLaunchKernelGGL(sqrt_kernel, dim3(grid_for(n * K, 256)), dim3(256), 0, ctx().stream, dist.p, n * K);
-    launch_check("sqrt_kernel");
-}
+void sqrt_lists(DevBuf<double> &dist, long long n, int K) { umap_sqrt_lists(dist, n, K); }
 
 struct UmapArgs {
     int dims, n_epochs;

@@ -21,6 +21,8 @@ void umap_ab(double spread, double min_dist, double *a, double *b);
 // the graph from the lists (device, n x K, Euclidean distances, self excluded; n_neighbors = K + 1); rho / sigma (n each) when wanted
 void umap_graph(const DevBuf<int> &idx, const DevBuf<double> &dist, long long n, int K, UmapGraph &G, DevBuf<double> *rho = nullptr,
                 DevBuf<double> *sigma = nullptr);
+// squared distances of lists (device, n x K) made Euclidean in place
+void umap_sqrt_lists(DevBuf<double> &dist, long long n, int K);
 // epochs [ep0, ep1) of n_epochs on dY (device, n x dims, in and out)
 void umap_epochs(const UmapGraph &G, double *dY, int dims, int n_epochs, int ep0, int ep1, double learning_rate, double a, double b,
                  int negative_sample_rate, double repulsion_strength, unsigned long long seed);
