@@ -605,6 +605,28 @@ int sharp_louvain_aggregate(const long long *row_ptr, const int *col, const long
                             int *col_out, long long *q_out, long long *nnz_out, long long *nc_out, int *new_out);
 int sharp_louvain_row_caps(int *wave_cap, int *block_cap);
 
+/* ---- The SNN / Jaccard neighbour graph (sharp_amd/csrc/snn.hip) ------------------------------------------------
+ * index: n x K row-major, 0-based, each row K other rows, no index twice in a row (sharp_tsne_knn's and sharp_knn_descent's lists;
+ * validated on the device before an index is dereferenced: range, self, twice).  2 <= n <= 16777216, 1 <= K <= 255, K <= n - 1.
+ * k = K + 1 (Seurat's k.param: the row itself counts), S(i) = {i} + the row's neighbours, s(i, j) = |S(i) n S(j)| for i != j,
+ * w(i, j) = (double)s / (double)(2k - s) (Seurat's ComputeSNN).  An entry exists iff s >= 1 and w >= prune (prune in [0, 1]; a weight
+ * equal to prune stays).  The result is sharp_louvain_graph's input: row_ptr (n + 1), col strictly ascending within a row, no diagonal
+ * entry, val[i,j] == val[j,i] bit for bit; a row may be empty.  Everything the device computes is an integer: two calls give the
+ * same bits.  The formula is Seurat's; no run against Seurat is claimed.
+ * col == NULL (then val and shared NULL too): the count alone -- row_ptr and *nnz are written and the caller allocates.  Otherwise
+ * cap (the room of col / val / shared) must be >= nnz, or the call is refused with the needed count in the message and in *nnz.
+ * shared: NULL, or the s of every entry.  nnz >= 2^38, or a result beyond the device's free memory, is refused by name.
+ * row_caps: the largest row work t(i) = sum over m in S(i) of |{j : m in S(j)}| of the one-wave and of the one-workgroup class of the
+ * product kernels (rows beyond the second use a dense counter row in device memory). */
+int sharp_snn_graph(const int *index, long long n, int K, double prune, long long cap, long long *row_ptr, int *col, double *val, int *shared,
+                    long long *nnz);
+int sharp_snn_row_caps(int *wave_cap, int *block_cap);
+/* lists -> the SNN graph -> Louvain (sharp_louvain_neighbors' arguments and outputs from resolution on): the graph never leaves the
+ * device.  A pruned graph without any entry is refused ("holds no positive weight"). */
+int sharp_louvain_snn(const int *index, long long n, int K, double prune, double resolution, double tol, int max_levels, int max_rounds,
+                      int max_fails, double seed, int *membership, int level_cap, long long *level_n, long long *level_communities,
+                      int *level_rounds, double *level_q, int *n_levels, int *level_membership);
+
 /* ---- synthetic inputs (bench / tests; not part of the reference) ------------ */
 /* Counter-based generator, value = f(seed, gene, cell): bit-identical to
  * oracle_synth_value().  Fills dX (fp32, m x ncell column-major, leading dim ld). */
@@ -763,6 +785,13 @@ void sharp_C_louvain_neighbors(int *index, double *distance, double *n, int *K, 
                                int *max_rounds, int *max_fails, double *seed, int *membership, int *level_cap, double *levels, int *n_levels,
                                int *want_levels, int *level_membership, int *status);
 void sharp_C_louvain_modularity(double *row_ptr, int *col, double *val, double *n, int *membership, double *resolution, double *Q, int *status);
+/* sharp_snn_graph / sharp_louvain_snn in the same convention: n, cap, nnz and row_ptr (n + 1 values) as double, index 0-based;
+ * want: 1 = fill col / val (0: the count alone, col / val / shared are buffers of length >= 1 that are left alone), 2 = shared too */
+void sharp_C_snn_graph(int *index, double *n, int *K, double *prune, double *cap, double *row_ptr, int *col, double *val, int *shared, int *want,
+                       double *nnz, int *status);
+void sharp_C_louvain_snn(int *index, double *n, int *K, double *prune, double *resolution, double *tol, int *max_levels, int *max_rounds,
+                         int *max_fails, double *seed, int *membership, int *level_cap, double *levels, int *n_levels, int *want_levels,
+                         int *level_membership, int *status);
 
 #ifdef __cplusplus
 }

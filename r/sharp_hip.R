@@ -723,25 +723,54 @@ sharp_continuity <- function(X, Y, n_neighbors = 5L) .sharp_map_score(.sharp_dma
 }
 
 # A clustering read off the neighbour graph, as sc.tl.louvain and Seurat's FindClusters run it: X (observations in rows; the exact
-# k-NN is sharp_knn's) or the lists sharp_knn returned (a list with $index, 1-based, and $distance).  membership: 1 .. G by decreasing
-# size; levels: one row (n, communities, rounds, modularity) per level.  The method is the project's own synchronous form of Louvain;
-# two calls give the same bits.
+# k-NN is sharp_knn's) or the lists sharp_knn returned (a list with $index, 1-based, and $distance).  graph = "fuzzy": the fuzzy union
+# sharp_umap builds (scanpy's connectivities); graph = "snn": the SNN / Jaccard graph of the same lists (n_neighbors is Seurat's k.param,
+# prune its prune.SNN; DESIGN.md 19).  membership: 1 .. G by decreasing size; levels: one row (n, communities, rounds, modularity) per
+# level.  The method is the project's own synchronous form of Louvain; two calls give the same bits.
 sharp_louvain <- function(X, n_neighbors = 15L, resolution = 1, seed = 10, tol = 1e-7, max_levels = 20L, max_rounds = 200L, max_fails = 4L,
-                          ret_levels = FALSE) {
+                          ret_levels = FALSE, graph = c("fuzzy", "snn"), prune = NULL) {
+    graph <- match.arg(graph)
+    if (graph == "fuzzy" && !is.null(prune)) stop("prune belongs to graph = \"snn\"")
     nn <- if (is.list(X) && !is.null(X$index)) X else sharp_knn(.sharp_dmat(X), as.integer(n_neighbors) - 1L)
     index <- as.matrix(nn$index)
     n <- nrow(index)
     K <- ncol(index)
     cap <- as.integer(max_levels)
-    r <- .C("sharp_C_louvain_neighbors", as.integer(t(index) - 1L), as.double(t(as.matrix(nn$distance))), as.double(n), as.integer(K), 0L,
-            as.double(resolution), as.double(tol), cap, as.integer(max_rounds), as.integer(max_fails), as.double(seed),
-            membership = integer(n), cap, levels = double(4 * cap), n_levels = integer(1), as.integer(ret_levels),
-            lm = integer(if (ret_levels) cap * n else 1L), status = integer(1))
+    if (graph == "snn") {
+        r <- .C("sharp_C_louvain_snn", as.integer(t(index) - 1L), as.double(n), as.integer(K), as.double(if (is.null(prune)) 1 / 15 else prune),
+                as.double(resolution), as.double(tol), cap, as.integer(max_rounds), as.integer(max_fails), as.double(seed),
+                membership = integer(n), cap, levels = double(4 * cap), n_levels = integer(1), as.integer(ret_levels),
+                lm = integer(if (ret_levels) cap * n else 1L), status = integer(1))
+    } else {
+        r <- .C("sharp_C_louvain_neighbors", as.integer(t(index) - 1L), as.double(t(as.matrix(nn$distance))), as.double(n), as.integer(K), 0L,
+                as.double(resolution), as.double(tol), cap, as.integer(max_rounds), as.integer(max_fails), as.double(seed),
+                membership = integer(n), cap, levels = double(4 * cap), n_levels = integer(1), as.integer(ret_levels),
+                lm = integer(if (ret_levels) cap * n else 1L), status = integer(1))
+    }
     .sharp_check(r$status)
     .sharp_louvain_result(r, n, ret_levels)
 }
 
-# the same on any symmetric graph: a dgCMatrix-like triple (row_ptr 0-based with n + 1 values, col 0-based, val), e.g. an SNN graph
+# The SNN / Jaccard graph of neighbour lists (Seurat's ComputeSNN formula; DESIGN.md 19): index as sharp_knn returns it (n x K, 1-based,
+# self excluded), k = K + 1, w = s / (2k - s) for the s shared members of the two rows' lists (each with the row itself), entries with
+# w < prune dropped, no diagonal.  Returns the 1-based triplet list(i, j, x, n) for Matrix::sparseMatrix(i = i, j = j, x = x,
+# dims = c(n, n)), by rows with ascending columns; two .C calls: the count, then the fill.
+sharp_snn_graph <- function(index, prune = 1 / 15) {
+    index <- as.matrix(index)
+    n <- nrow(index)
+    K <- ncol(index)
+    idx <- as.integer(t(index) - 1L)
+    r <- .C("sharp_C_snn_graph", idx, as.double(n), as.integer(K), as.double(prune), 0, row_ptr = double(n + 1), integer(1), double(1),
+            integer(1), 0L, nnz = double(1), status = integer(1))
+    .sharp_check(r$status)
+    nnz <- r$nnz
+    r <- .C("sharp_C_snn_graph", idx, as.double(n), as.integer(K), as.double(prune), as.double(nnz), row_ptr = double(n + 1),
+            col = integer(max(nnz, 1)), val = double(max(nnz, 1)), integer(1), 1L, nnz = double(1), status = integer(1))
+    .sharp_check(r$status)
+    list(i = rep.int(seq_len(n), diff(r$row_ptr)), j = r$col[seq_len(nnz)] + 1L, x = r$val[seq_len(nnz)], n = n)
+}
+
+# the same on any symmetric graph: a dgCMatrix-like triple (row_ptr 0-based with n + 1 values, col 0-based, val)
 sharp_louvain_graph <- function(row_ptr, col, val, resolution = 1, seed = 10, tol = 1e-7, max_levels = 20L, max_rounds = 200L,
                                 max_fails = 4L, ret_levels = FALSE) {
     n <- length(row_ptr) - 1L

@@ -10,5 +10,6 @@ from .umap import UmapModel, knn_query, umap, umap_ab, umap_neighbors, umap_tran
 from .tree import get_percluster_exp, hclust, plot_markers  # noqa: F401
 from .validity import calinski_harabasz, cutree, silhouette  # noqa: F401
 from .mapquality import continuity, knn_recall, neighbor_ranks, trustworthiness  # noqa: F401
-from .community import louvain, louvain_graph, louvain_neighbors, modularity  # noqa: F401
+from .community import louvain, louvain_graph, louvain_neighbors, louvain_snn, modularity  # noqa: F401
+from .snn import snn, snn_graph  # noqa: F401
 from . import dist  # noqa: F401,E402  (the multi-GPU module; calling it is R's dist() on the GPU, sharp_amd/tree.py)

@@ -1,7 +1,9 @@
-"""louvain(), louvain_neighbors(), louvain_graph() and modularity(): a clustering read off the neighbour graph.
+"""louvain(), louvain_neighbors(), louvain_snn(), louvain_graph() and modularity(): a clustering read off the neighbour graph
+(DESIGN.md 18, 19).
 
-The graph is the fuzzy union umap() builds from the k-NN lists -- scanpy's connectivities -- or any symmetric CSR the caller has (a
-Seurat-style SNN graph made elsewhere).  The method is this project's own synchronous form of Louvain: weights are quantised to integers
+The graph is the fuzzy union umap() builds from the k-NN lists -- scanpy's connectivities --, the shared-nearest-neighbour graph with
+Jaccard weights that Seurat clusters (louvain_snn(), louvain(graph="snn"); snn_graph() returns it), or any symmetric CSR the caller
+has.  The method is this project's own synchronous form of Louvain: weights are quantised to integers
 once, so every sum of weights is exact whatever the order of the GPU's atomics; a round moves all vertices at once from the round's start
 state, a hashed bit per community deciding whether it may lose or gain members in that round; a round is kept when the modularity rises.
 A call is a pure function of its arguments: two calls give the same bits.  No parity with networkx, igraph or cuGraph is claimed.
@@ -12,9 +14,10 @@ import numpy as np
 
 from . import _lib
 from ._lib import SharpError, check, f64, i32, i64, lib
+from .snn import PRUNE, _lists, _prune, _search
 from .tsne import _neighbour_arrays
 
-__all__ = ["louvain", "louvain_neighbors", "louvain_graph", "modularity"]
+__all__ = ["louvain", "louvain_neighbors", "louvain_snn", "louvain_graph", "modularity"]
 
 _MAX_N = 16777216
 
@@ -129,41 +132,47 @@ def louvain_neighbors(index, distance, squared=False, resolution=1.0, seed=10, t
     return _result(n, mem, ln, lc, lr, lq, nl.value, lm, a[5])
 
 
+def louvain_snn(index, prune=PRUNE, resolution=1.0, seed=10, tol=1e-7, max_levels=20, max_rounds=200, max_fails=4, ret_levels=False):
+    """Louvain on the SNN graph of neighbour lists the caller already has (index: n x K, 0-based, what knn(X, K) returns; distances are
+    not used): snn_graph(index, prune)'s graph with k = K + 1, built on the device, and never leaving it.  The result is
+    louvain_graph's on that graph, bit for bit.  A prune that leaves no entry is refused."""
+    who = "louvain_snn"
+    a = _limits(who, resolution, tol, max_levels, max_rounds, max_fails, seed)
+    prune = _prune(prune, who)
+    index = _lists(index, who)
+    n, K = index.shape
+    _lib.ensure_init()
+    mem, ln, lc, lr, lq, lm = _outputs(n, a[2], ret_levels)
+    nl = C.c_int()
+    check(lib().sharp_louvain_snn(i32(index), n, int(K), prune, a[0], a[1], a[2], a[3], a[4], float(a[5]), i32(mem), a[2], i64(ln), i64(lc),
+                                  i32(lr), f64(lq), C.byref(nl), i32(lm)))
+    return _result(n, mem, ln, lc, lr, lq, nl.value, lm, a[5])
+
+
 def louvain(X, n_neighbors=15, resolution=1.0, nn_method="exact", nn_args=None, pca=None, seed=10, tol=1e-7, max_levels=20,
-            ret_levels=False, ret_nn=False, pca_center=True, max_rounds=200, max_fails=4):
+            ret_levels=False, ret_nn=False, pca_center=True, max_rounds=200, max_fails=4, graph="fuzzy", prune=None):
     """Louvain on the neighbour graph of the rows of X, as sc.tl.louvain runs it on scanpy's connectivities.  The input is prepared and
     searched as umap() does it: pca None or a number of components (centred when pca_center), n_neighbors counts the row itself
     (2 .. 256, below n), nn_method "exact" or "descent" (knn_descent()'s approximate lists, nn_args its keywords).  The result is
-    louvain_neighbors' on those lists; with ret_nn it also carries "nn": {"index", "distance"}."""
-    from .tsne import _nn_method, _prepare, _rows, knn, knn_descent
+    louvain_neighbors' on those lists; with ret_nn it also carries "nn": {"index", "distance"}.  graph="snn": the SNN / Jaccard graph
+    of those lists instead (n_neighbors is Seurat's k.param; prune in [0, 1], None: 1/15) -- louvain_snn's result.  prune belongs to
+    graph="snn"."""
+    from .tsne import _nn_method
 
     who = "louvain"
     method = _nn_method(nn_method, who)
     if nn_args and method != "descent":
         raise SharpError(f"{who}: nn_args belong to nn_method = \"descent\"")
+    if graph not in ("fuzzy", "snn"):
+        raise SharpError(f"{who}: graph must be \"fuzzy\" or \"snn\", not {graph!r}")
+    if graph == "fuzzy" and prune is not None:
+        raise SharpError(f"{who}: prune belongs to graph = \"snn\"")
+    if graph == "snn":
+        prune = _prune(PRUNE if prune is None else prune, who)
     a = _limits(who, resolution, tol, max_levels, max_rounds, max_fails, seed)
-    X = _rows(X)
-    if X.ndim != 2:
-        raise SharpError(f"{who}: X must be a matrix")
-    n = X.shape[0]
-    n_neighbors = int(n_neighbors)
-    if not 2 <= n_neighbors <= 256:
-        raise SharpError(f"{who}: n_neighbors must be in 2 .. 256")
-    if n_neighbors >= n:
-        raise SharpError(f"{who}: n_neighbors must be smaller than the number of rows")
-    pca = 0 if pca is None else int(pca)
-    if pca < 0:
-        raise SharpError(f"{who}: pca must be None or a positive number of components")
-    if not np.isfinite(X).all():
-        r, c = np.argwhere(~np.isfinite(X))[0]
-        raise SharpError(f"{who}: the input holds NA / NaN / Inf (row {r + 1}, column {c + 1})")
-    xp = _prepare(X, pca=True, initial_dims=pca, pca_center=pca_center, pca_scale=False, normalize=False) if pca else X
-    if method == "descent":
-        idx, dist = knn_descent(xp, n_neighbors - 1, **dict(nn_args or {}, squared=False, ret_info=False))
-    else:
-        idx, dist = knn(xp, n_neighbors - 1)
-    out = louvain_neighbors(idx, dist, resolution=a[0], seed=a[5], tol=a[1], max_levels=a[2], max_rounds=a[3], max_fails=a[4],
-                            ret_levels=ret_levels)
+    idx, dist, method = _search(X, n_neighbors, nn_method, nn_args, pca, pca_center, who)
+    kw = dict(resolution=a[0], seed=a[5], tol=a[1], max_levels=a[2], max_rounds=a[3], max_fails=a[4], ret_levels=ret_levels)
+    out = louvain_snn(idx, prune, **kw) if graph == "snn" else louvain_neighbors(idx, dist, **kw)
     if ret_nn:
         out["nn"] = {"index": idx, "distance": dist}
         if method == "descent":

@@ -400,4 +400,30 @@ void sharp_C_louvain_modularity(double *row_ptr, int *col, double *val, double *
     *status = sharp_louvain_modularity(rp.data(), col, val, nullptr, nn, membership, *resolution, Q);
 }
 
+/* The SNN graph (sharp_snn_graph: the same count-then-fill protocol) and Louvain on it (sharp_louvain_snn): n, cap, nnz and row_ptr
+ * as double; want: 1 fill col / val (0: the count alone), 2 shared as well */
+void sharp_C_snn_graph(int *index, double *n, int *K, double *prune, double *cap, double *row_ptr, int *col, double *val, int *shared, int *want,
+                       double *nnz, int *status) {
+    const long long nn = as_ll(n);
+    std::vector<long long> rp(nn > 0 && nn <= (1ll << 24) ? static_cast<size_t>(nn) + 1 : 1, 0);   // (another n is refused before row_ptr is written)
+    long long z = 0;
+    const bool fill = (*want & 1) != 0;
+    *status = sharp_snn_graph(index, nn, *K, *prune, as_ll(cap), rp.data(), fill ? col : nullptr, fill ? val : nullptr,
+                              fill && (*want & 2) ? shared : nullptr, &z);
+    *nnz = static_cast<double>(z);
+    if (*status == 0)
+        for (long long i = 0; i <= nn; ++i) row_ptr[i] = static_cast<double>(rp[i]);
+}
+void sharp_C_louvain_snn(int *index, double *n, int *K, double *prune, double *resolution, double *tol, int *max_levels, int *max_rounds,
+                         int *max_fails, double *seed, int *membership, int *level_cap, double *levels, int *n_levels, int *want_levels,
+                         int *level_membership, int *status) {
+    const size_t cap = *level_cap > 0 ? static_cast<size_t>(*level_cap) : 1;
+    std::vector<long long> ln(cap), lc(cap);
+    std::vector<int> lr(cap);
+    std::vector<double> lq(cap);
+    *status = sharp_louvain_snn(index, as_ll(n), *K, *prune, *resolution, *tol, *max_levels, *max_rounds, *max_fails, *seed, membership,
+                                *level_cap, ln.data(), lc.data(), lr.data(), lq.data(), n_levels, *want_levels ? level_membership : nullptr);
+    louvain_levels_out(*status, *n_levels, ln, lc, lr, lq, levels);
+}
+
 }  // extern "C"

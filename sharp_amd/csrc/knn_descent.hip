@@ -352,6 +352,17 @@ void check_lds(size_t bytes, const char *what) {
 
 }  // namespace
 
+void reverse_sort_by_target(const unsigned long long *keys, unsigned long long *keys_s, const int *vals, int *vals_s, long long n, long long ne) {
+    Ctx &c = ctx();
+    unsigned bits = 33;
+    while (bits < 64 && (static_cast<unsigned long long>(n) >> (bits - 32)) != 0) ++bits;
+    size_t tmp_bytes = 0;
+    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys_s, vals, vals_s, static_cast<size_t>(ne), 0, bits, c.stream));
+    DevBuf<unsigned char> tmp(std::max<size_t>(tmp_bytes, 1));
+    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys, keys_s, vals, vals_s, static_cast<size_t>(ne), 0, bits, c.stream));
+    stream_sync();   // (the sort's temporary storage leaves scope)
+}
+
 int knn_descent_candidates(int K, int max_candidates) { return max_candidates > 0 ? max_candidates : std::min(K, 30); }
 
 void knn_descent_start(const double *dX, long long n, int d, int K, int T, unsigned long long seed, int max_rows_per_launch, DevBuf<int> &idx,
@@ -430,12 +441,7 @@ long long knn_descent_join(const double *dX, long long n, int d, int K, int S, i
         const unsigned long long base = mix64(seed * KD_GOLD + static_cast<unsigned long long>(iteration));
         hipLaunchKernelGGL(kd_revkey_kernel, dim3(grid_for(ne, 256)), dim3(256), 0, c.stream, idx.p, ne, K, base, keys.p, vals.p);
         launch_check("kd_revkey_kernel");
-        unsigned bits = 33;
-        while (bits < 64 && (static_cast<unsigned long long>(n) >> (bits - 32)) != 0) ++bits;
-        size_t tmp_bytes = 0;
-        SHARP_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.p, keys_s.p, vals.p, vals_s.p, static_cast<size_t>(ne), 0, bits, c.stream));
-        DevBuf<unsigned char> tmp(std::max<size_t>(tmp_bytes, 1));
-        SHARP_HIP_CHECK(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys.p, keys_s.p, vals.p, vals_s.p, static_cast<size_t>(ne), 0, bits, c.stream));
+        reverse_sort_by_target(keys.p, keys_s.p, vals.p, vals_s.p, n, ne);
         SHARP_HIP_CHECK(hipMemsetAsync(start.p, 0xFF, static_cast<size_t>(n) * sizeof(long long), c.stream));
         hipLaunchKernelGGL(kd_segstart_kernel, dim3(grid_for(ne, 256)), dim3(256), 0, c.stream, keys_s.p, ne, start.p);
         launch_check("kd_segstart_kernel");

@@ -29,6 +29,7 @@
 #include <rocprim/device/device_reduce_by_key.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "snn.hpp"
 #include "tsne.hpp"
 
 namespace sharp {
@@ -919,6 +920,28 @@ int sharp_louvain_neighbors(const int *index, const double *distance, long long 
     umap_graph(idx, dist, n, K, G);
     idx.release();
     dist.release();
+    run_and_report(w, G, a, membership, level_cap, level_n, level_communities, level_rounds, level_q, n_levels, level_membership);
+    SHARP_API_END
+}
+
+int sharp_louvain_snn(const int *index, long long n, int K, double prune, double resolution, double tol, int max_levels, int max_rounds,
+                      int max_fails, double seed, int *membership, int level_cap, long long *level_n, long long *level_communities,
+                      int *level_rounds, double *level_q, int *n_levels, int *level_membership) {
+    SHARP_API_BEGIN
+    const std::string w("louvain_snn");
+    SHARP_REQUIRE(index, w + ": null index");
+    SHARP_REQUIRE(membership && level_n && level_communities && level_rounds && level_q && n_levels, w + ": null output");
+    snn_check_args(w, n, K, prune);
+    const LouvainArgs a = louvain_args(w, resolution, tol, max_levels, max_rounds, max_fails, seed);
+    SHARP_REQUIRE(level_cap >= max_levels, w + ": level_cap must be at least max_levels");
+    ctx();
+    UmapGraph G;
+    {
+        DevBuf<int> idx(static_cast<size_t>(n) * K);
+        idx.upload(index, static_cast<size_t>(n) * K);
+        snn_graph(w, idx, n, K, prune, false, G, nullptr);   // (synchronises: idx leaves scope)
+    }
+    SHARP_REQUIRE(G.nnz >= 1 && G.wmax > 0.0, w + ": the pruned graph holds no positive weight");
     run_and_report(w, G, a, membership, level_cap, level_n, level_communities, level_rounds, level_q, n_levels, level_membership);
     SHARP_API_END
 }
