@@ -6,12 +6,11 @@
 // -ffp-contract=off).  The lists are therefore a pure function of (X, K, the parameters, seed), whatever the launch split, the tile
 // filling or the lossy duplicate filter of the join do.
 //
-// This file writes its own copies of lex_less (tsne.hip), mix64 (umap.hip) and the rank step of knn_merge_kernel, as umap_transform.hip
-// did.
+// This file writes its own copies of lex_less (tsne.hip) and the rank step of knn_merge_kernel, as umap_transform.hip did;
+// mix64, iota and the sorts are graph.hpp's.
 #include "knn_descent.hpp"
+#include "graph_prim.hpp"
 #include "tsne.hpp"
-
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
 #include <cfloat>
@@ -30,17 +29,6 @@ constexpr int KD_HASH = 512;           // slots of the join's per-row "already o
 constexpr int KD_MAXT = 32;            // projections
 constexpr double KD_XMAX = 1.0e100;    // |x| above this is refused: squared distances and projections stay finite below it
 constexpr unsigned long long KD_GOLD = 0x9E3779B97F4A7C15ull;
-
-inline unsigned grid_for(long long n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
-
-__host__ __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {   // the splitmix64 finaliser (§13's mix)
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
 
 __device__ __forceinline__ bool lex_less(double a, int ia, double b, int ib) { return a < b || (a == b && ia < ib); }
 
@@ -171,11 +159,6 @@ __global__ __launch_bounds__(256) void kd_project_kernel(const double *__restric
 #pragma unroll
     for (int t = 0; t < KD_MAXT; ++t)
         if (t < T) keys[static_cast<long long>(t) * n + i] = sortable(p[t]);
-}
-
-__global__ __launch_bounds__(256) void kd_iota_kernel(int *__restrict__ v, long long n) {
-    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (i < n) v[i] = static_cast<int>(i);
 }
 
 // pos[t n + order[t n + p]] = p
@@ -352,14 +335,13 @@ void check_lds(size_t bytes, const char *what) {
 
 }  // namespace
 
-void reverse_sort_by_target(const unsigned long long *keys, unsigned long long *keys_s, const int *vals, int *vals_s, long long n, long long ne) {
-    Ctx &c = ctx();
-    unsigned bits = 33;
-    while (bits < 64 && (static_cast<unsigned long long>(n) >> (bits - 32)) != 0) ++bits;
-    size_t tmp_bytes = 0;
-    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys_s, vals, vals_s, static_cast<size_t>(ne), 0, bits, c.stream));
-    DevBuf<unsigned char> tmp(std::max<size_t>(tmp_bytes, 1));
-    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys, keys_s, vals, vals_s, static_cast<size_t>(ne), 0, bits, c.stream));
+// (graph.hpp declares it; it lives here, in the code object it has always been in)
+void reverse_sort_by_target(const u64 *keys, u64 *keys_s, const int *vals, int *vals_s, long long n, long long ne) {
+    Scratch tmp;
+    with_scratch(tmp, false, [&](void *p, size_t &bytes) {   // (const inputs: the instantiation this sort has had from the start)
+        return rocprim::radix_sort_pairs(p, bytes, keys, keys_s, vals, vals_s, static_cast<size_t>(ne), 0, key_bits(static_cast<u64>(n) << 32),
+                                         ctx().stream);
+    });
     stream_sync();   // (the sort's temporary storage leaves scope)
 }
 
@@ -382,17 +364,13 @@ void knn_descent_start(const double *dX, long long n, int d, int K, int T, unsig
     dR.upload(R.data(), R.size());
     const size_t tn = static_cast<size_t>(T) * n;
     DevBuf<unsigned long long> keys(tn), keys_s(n);
-    DevBuf<int> iota(n), order(tn), pos(tn);
+    DevBuf<int> ident(n), order(tn), pos(tn);
     hipLaunchKernelGGL(kd_project_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, dX, n, d, dR.p, T, keys.p);
     launch_check("kd_project_kernel");
-    hipLaunchKernelGGL(kd_iota_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, iota.p, n);
-    launch_check("kd_iota_kernel");
-    size_t tmp_bytes = 0;
-    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.p, keys_s.p, iota.p, order.p, static_cast<size_t>(n), 0, 64, c.stream));
-    DevBuf<unsigned char> tmp(std::max<size_t>(tmp_bytes, 1));
+    iota(ident.p, n);
+    Scratch tmp;
     for (int t = 0; t < T; ++t)   // (stable: equal projections stay in index order)
-        SHARP_HIP_CHECK(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys.p + static_cast<size_t>(t) * n, keys_s.p, iota.p,
-                                                  order.p + static_cast<size_t>(t) * n, static_cast<size_t>(n), 0, 64, c.stream));
+        sort_pairs(keys.p + static_cast<size_t>(t) * n, keys_s.p, ident.p, order.p + static_cast<size_t>(t) * n, static_cast<size_t>(n), 0, 64, tmp, t > 0);
     hipLaunchKernelGGL(kd_pos_kernel, dim3(grid_for(static_cast<long long>(tn), 256)), dim3(256), 0, c.stream, order.p, n,
                        static_cast<long long>(tn), pos.p);
     launch_check("kd_pos_kernel");

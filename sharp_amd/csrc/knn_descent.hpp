@@ -14,11 +14,6 @@ struct KnnDescentInfo {
     long long gathered = 0;  // candidate rows the joins gathered and measured (what the filters let through)
 };
 
-// Reverse lists by sorted 64-bit keys: keys[e] = (target << 32 | order within the target), vals[e] = the source; the stable sort leaves
-// every target's sources together, ascending in the keys' low words, in keys_s / vals_s (ne entries each; targets below n).  The join's
-// reverse candidates and the SNN graph's reverse lists (snn.hip) are both made this way.
-void reverse_sort_by_target(const unsigned long long *keys, unsigned long long *keys_s, const int *vals, int *vals_s, long long n, long long ne);
-
 // S = max_candidates, 0: min(K, 30)
 int knn_descent_candidates(int K, int max_candidates);
 // the start alone: dX (n x d, device, finite) -> each row's K best of its T windows, sorted by (distance, index).

@@ -3,6 +3,7 @@
 // (R/get_opt_hclust.R:71-72: n_t x n_t x p contraction per task) and for the per-cluster sums behind
 // silhouette / CH (hclust.hip).
 #include "linalg.hpp"
+#include "graph.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -347,12 +348,6 @@ void gemm_tn_f64_batched(const GemmTask *d_tasks, int count, int max_M, int max_
 // ---------------------------------------------------------------------------------------------
 // Row preparation: one wave per row.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // sum over the row held as RP_MAXV values per lane (entries beyond p are zero and masked by the caller)
 constexpr int RP_MAXV = 8;
 

@@ -14,10 +14,12 @@
 //              the arg-max is a reduction under a total order.
 //   state      tot and in by int64 global atomics, the surviving communities counted and ranked by a scan, the fp64 terms
 //              in / 2m - gamma (tot / 2m)^2 written at their ranks and sorted by value (rocprim radix sort: Q is a function of the partition, not of its labels)
-//              and summed by umap.hip's two-stage fixed-order reduction (no floating-point atomic).  The host reads Q and the
+//              and summed by graph.hpp's two-stage fixed-order reduction (no floating-point atomic).  The host reads Q and the
 //              number of communities once per round and decides acceptance.
-//   aggregate  key = new[row] * nc + new[col], rocprim radix sort, reduce_by_key with an integer plus, row_ptr by binary search
+//   aggregate  key = new[row] * nc + new[col], then graph.hpp's CSR builder: radix sort, equal keys merged by an integer plus, row_ptr by
+//              binary search
 #include "louvain.hpp"
+#include "graph_prim.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -25,28 +27,13 @@
 #include <string>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_reduce_by_key.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include "snn.hpp"
 #include "tsne.hpp"
+#include "umap.hpp"
 
 namespace sharp {
 namespace {
 
-using u64 = unsigned long long;
-
-inline unsigned grid_for(long long n, int per) { return static_cast<unsigned>((std::max<long long>(n, 1) + per - 1) / per); }
-
-__host__ __device__ __forceinline__ u64 mix64(u64 z) {   // the splitmix64 finaliser (umap.hip)
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
 // x1 = mix(mix(seed * golden + level) + round); h(c) = the top bit of mix(x1 + c)
 inline u64 round_key(u64 seed, int level, int round) {
     return mix64(mix64(seed * 0x9E3779B97F4A7C15ull + static_cast<u64>(level)) + static_cast<u64>(round));
@@ -98,11 +85,6 @@ __global__ __launch_bounds__(256) void lv_rowptr_map_kernel(const long long *__r
 __global__ __launch_bounds__(256) void lv_strength_kernel(const int *__restrict__ row, const u64 *__restrict__ q, long long nnz, u64 *__restrict__ k) {
     const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
     if (e < nnz) atomicAdd(&k[row[e]], q[e]);
-}
-
-__global__ __launch_bounds__(256) void lv_iota_kernel(int *__restrict__ v, long long n) {
-    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (i < n) v[i] = static_cast<int>(i);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -293,9 +275,8 @@ __global__ __launch_bounds__(256) void lv_terms_kernel(const u64 *__restrict__ t
     terms[pos[c]] = static_cast<double>(static_cast<long long>(in[c])) / m2 - gamma * (t * t);   // (pos[c] < n: inside the buffer whatever the bound)
 }
 
-// umap.hip's reduce_fixed with the length read on the device (*len = the number of communities): stage 1 folds chunks of
+// graph.hpp's fixed_reduce with the length read on the device (*len = the number of communities): stage 1 folds chunks of
 // max(256, ceil(len / 1024)) values, 256 strided running sums and a tree per workgroup; stage 2 folds the workgroups' results alike.
-constexpr int kRedBlocks = 1024;
 __device__ __forceinline__ double block_fold(double a, double *s) {
     const int tid = threadIdx.x;
     s[tid] = a;
@@ -339,27 +320,6 @@ __global__ __launch_bounds__(256) void lv_keys_kernel(const int *__restrict__ ro
     keys[e] = static_cast<u64>(pos[comm[row[e]]]) * nc + static_cast<u64>(pos[comm[col[e]]]);
 }
 
-__global__ __launch_bounds__(256) void lv_coarse_kernel(const u64 *__restrict__ keys, long long m, u64 nc, int *__restrict__ row, int *__restrict__ col) {
-    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (e >= m) return;
-    const u64 r = keys[e] / nc;
-    row[e] = static_cast<int>(r);
-    col[e] = static_cast<int>(keys[e] - r * nc);
-}
-
-// row_ptr[r] = the first entry whose key is >= r * nc, r = 0 .. nc (a coarse vertex without entries gets an empty row)
-__global__ __launch_bounds__(256) void lv_coarse_rowptr_kernel(const u64 *__restrict__ keys, long long m, u64 nc, long long *__restrict__ rp) {
-    const long long r = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (r > static_cast<long long>(nc)) return;
-    const u64 want = static_cast<u64>(r) * nc;
-    long long lo = 0, hi = m;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (keys[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    rp[r] = lo;
-}
-
 __global__ __launch_bounds__(256) void lv_compose_kernel(int *__restrict__ vmap, long long n0, const int *__restrict__ comm, const int *__restrict__ pos) {
     const long long v = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
     if (v < n0) vmap[v] = pos[comm[vmap[v]]];
@@ -378,7 +338,7 @@ void fill_strengths(LouvainGraph &L) {
     L.k.alloc(L.n);
     L.k.zero();
     if (L.nnz) {
-        hipLaunchKernelGGL(lv_strength_kernel, dim3(grid_for(L.nnz, 256)), dim3(256), 0, c.stream, L.row.p, L.q.p, L.nnz, L.k.p);
+        hipLaunchKernelGGL(lv_strength_kernel, dim3(grid_for(L.nnz, 256)), dim3(256), 0, c.stream, L.row.p, L.val.p, L.nnz, L.k.p);
         launch_check("lv_strength_kernel");
     }
 }
@@ -387,44 +347,29 @@ void fill_strengths(LouvainGraph &L) {
 struct Work {
     long long n = 0;
     DevBuf<u64> tot, tot2, in, scratch;
-    DevBuf<int> present, pos, rows_wave, rows_block, rows_dense;
+    DevBuf<int> present, pos;
+    RowClasses rows;
     DevBuf<double> terms, sorted, part, out;
-    DevBuf<unsigned char> tmp, tmp_sort;
-    int n_wave = 0, n_block = 0, n_dense = 0, dense_grid = 0;
+    Scratch tmp, tmp_sort;                   // (sized by the level's first lv_state, whose counts are its largest; reused by every round)
+    bool sized = false;
 
     void size(long long nn) {
         n = nn;
         tot.alloc(n); tot2.alloc(n); in.alloc(n);
         present.alloc(n + 1); pos.alloc(n + 1);
         terms.alloc(n); sorted.alloc(n); part.alloc(kRedBlocks); out.alloc(1);
-        size_t bytes = 0;
-        SHARP_HIP_CHECK(rocprim::radix_sort_keys(nullptr, bytes, terms.p, sorted.p, static_cast<size_t>(n), 0, 64, ctx().stream));
-        tmp_sort.alloc(std::max<size_t>(bytes, 1));
-        bytes = 0;
-        SHARP_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, present.p, pos.p, 0, static_cast<size_t>(n + 1), rocprim::plus<int>(), ctx().stream));
-        tmp.alloc(std::max<size_t>(bytes, 1));
     }
 
     void classify(const LouvainGraph &L) {
-        std::vector<long long> rp(L.n + 1);
-        L.row_ptr.download(rp.data(), rp.size());
-        std::vector<int> a, b, d;
-        for (long long v = 0; v < L.n; ++v) {
-            const long long len = rp[v + 1] - rp[v];
-            if (len == 0) continue;
-            (len <= kLvWaveCap ? a : len <= kLvBlockCap ? b : d).push_back(static_cast<int>(v));
-        }
-        auto up = [](DevBuf<int> &buf, const std::vector<int> &h) { buf.alloc(h.size()); if (!h.empty()) buf.upload(h.data(), h.size()); };
-        up(rows_wave, a); up(rows_block, b); up(rows_dense, d);
-        n_wave = static_cast<int>(a.size()); n_block = static_cast<int>(b.size()); n_dense = static_cast<int>(d.size());
-        dense_grid = 0;
-        if (n_dense) {
-            // dense rows of n slots each: at most 2^27 slots (1 GB) in all, at most 128 workgroups
-            dense_grid = static_cast<int>(std::min<long long>(n_dense, std::max<long long>(1, std::min<long long>(128, (1ll << 27) / L.n))));
-            scratch.alloc(static_cast<size_t>(dense_grid) * L.n);
+        std::vector<long long> len(L.n + 1);
+        L.row_ptr.download(len.data(), len.size());
+        for (long long v = 0; v < L.n; ++v) len[v] = len[v + 1] - len[v];
+        len.pop_back();
+        rows.classify(len, kLvWaveCap, kLvBlockCap, true);   // (an empty row has nothing to move by)
+        if (rows.n_dense) {                                // dense rows of n slots each: at most 1 GB in all
+            scratch.alloc(static_cast<size_t>(rows.dense_grid) * L.n);
             scratch.zero();
         }
-        stream_sync();                                     // (the host vectors go out of scope)
     }
 };
 
@@ -442,17 +387,16 @@ double lv_state(const LouvainGraph &L, const int *comm, u64 *tot, Work &W, doubl
     hipLaunchKernelGGL(lv_tot_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, comm, L.k.p, n, tot, W.present.p);
     launch_check("lv_tot_kernel");
     if (L.nnz) {
-        hipLaunchKernelGGL(lv_in_kernel, dim3(grid_for(L.nnz, 256)), dim3(256), 0, c.stream, L.row.p, L.col.p, L.q.p, L.nnz, comm, W.in.p);
+        hipLaunchKernelGGL(lv_in_kernel, dim3(grid_for(L.nnz, 256)), dim3(256), 0, c.stream, L.row.p, L.col.p, L.val.p, L.nnz, comm, W.in.p);
         launch_check("lv_in_kernel");
     }
-    size_t bytes = W.tmp.n;
-    SHARP_HIP_CHECK(rocprim::exclusive_scan(W.tmp.p, bytes, W.present.p, W.pos.p, 0, static_cast<size_t>(n + 1), rocprim::plus<int>(), c.stream));
+    exclusive_scan(W.present.p, W.pos.p, static_cast<size_t>(n + 1), W.tmp, W.sized);
     hipLaunchKernelGGL(lv_fill_kernel, dim3(grid_for(bound, 256)), dim3(256), 0, c.stream, W.terms.p, bound, HUGE_VAL);
     hipLaunchKernelGGL(lv_terms_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, tot, W.in.p, W.present.p, W.pos.p, n,
                        static_cast<double>(L.m2), gamma, W.terms.p);
     launch_check("lv_terms_kernel");
-    bytes = W.tmp_sort.n;                                  // (sized for n keys: enough for any bound)
-    SHARP_HIP_CHECK(rocprim::radix_sort_keys(W.tmp_sort.p, bytes, W.terms.p, W.sorted.p, static_cast<size_t>(bound), 0, 64, c.stream));
+    sort_keys(W.terms.p, W.sorted.p, static_cast<size_t>(bound), 0, 64, W.tmp_sort, W.sized);
+    W.sized = true;
     hipLaunchKernelGGL(lv_reduce1_kernel, dim3(kRedBlocks), dim3(256), 0, c.stream, W.sorted.p, W.pos.p + n, W.part.p);
     hipLaunchKernelGGL(lv_reduce2_kernel, dim3(1), dim3(256), 0, c.stream, W.part.p, W.pos.p + n, W.out.p);
     launch_check("lv_reduce_kernel");
@@ -471,18 +415,18 @@ void lv_move(const LouvainGraph &L, const int *comm, const u64 *tot, Work &W, do
     KernelTimer t("louvain_move");
     SHARP_HIP_CHECK(hipMemcpyAsync(prop, comm, L.n * sizeof(int), hipMemcpyDeviceToDevice, c.stream));
     const double m2 = static_cast<double>(L.m2);
-    if (W.n_wave) {
-        hipLaunchKernelGGL((lv_move_lds_kernel<64, 256>), dim3(grid_for(W.n_wave, 4)), dim3(256), 0, c.stream, W.rows_wave.p, W.n_wave, L.row_ptr.p,
-                           L.col.p, L.q.p, comm, L.k.p, tot, gamma, m2, x1, prop);
+    if (W.rows.n_wave) {
+        hipLaunchKernelGGL((lv_move_lds_kernel<64, 256>), dim3(grid_for(W.rows.n_wave, 4)), dim3(256), 0, c.stream, W.rows.rows_wave.p, W.rows.n_wave, L.row_ptr.p,
+                           L.col.p, L.val.p, comm, L.k.p, tot, gamma, m2, x1, prop);
         launch_check("lv_move_lds_kernel<64>");
     }
-    if (W.n_block) {
-        hipLaunchKernelGGL((lv_move_lds_kernel<256, 4096>), dim3(W.n_block), dim3(256), 0, c.stream, W.rows_block.p, W.n_block, L.row_ptr.p,
-                           L.col.p, L.q.p, comm, L.k.p, tot, gamma, m2, x1, prop);
+    if (W.rows.n_block) {
+        hipLaunchKernelGGL((lv_move_lds_kernel<256, 4096>), dim3(W.rows.n_block), dim3(256), 0, c.stream, W.rows.rows_block.p, W.rows.n_block, L.row_ptr.p,
+                           L.col.p, L.val.p, comm, L.k.p, tot, gamma, m2, x1, prop);
         launch_check("lv_move_lds_kernel<256>");
     }
-    if (W.n_dense) {
-        hipLaunchKernelGGL(lv_move_dense_kernel, dim3(W.dense_grid), dim3(256), 0, c.stream, W.rows_dense.p, W.n_dense, L.row_ptr.p, L.col.p, L.q.p,
+    if (W.rows.n_dense) {
+        hipLaunchKernelGGL(lv_move_dense_kernel, dim3(W.rows.dense_grid), dim3(256), 0, c.stream, W.rows.rows_dense.p, W.rows.n_dense, L.row_ptr.p, L.col.p, L.val.p,
                            comm, L.k.p, tot, gamma, m2, x1, W.scratch.p, L.n, prop);
         launch_check("lv_move_dense_kernel");
     }
@@ -497,33 +441,17 @@ void lv_aggregate(const LouvainGraph &L, const int *comm, const Work &W, long lo
     DevBuf<u64> keys(ne), keys2(ne), vals2(ne), ukeys(ne);
     C.n = nc;
     C.m2 = L.m2;
-    C.q.alloc(ne);
+    C.val.alloc(ne);
     hipLaunchKernelGGL(lv_keys_kernel, dim3(grid_for(L.nnz, 256)), dim3(256), 0, c.stream, L.row.p, L.col.p, L.nnz, comm, W.pos.p, unc, keys.p);
     launch_check("lv_keys_kernel");
-    unsigned bits = 1;
-    while (bits < 64 && (unc * unc >> bits) != 0) ++bits;
-    size_t tb = 0;
-    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tb, keys.p, keys2.p, L.q.p, vals2.p, ne, 0, bits, c.stream));
-    DevBuf<unsigned char> tmp(std::max<size_t>(tb, 1));
-    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(tmp.p, tb, keys.p, keys2.p, L.q.p, vals2.p, ne, 0, bits, c.stream));
-    DevBuf<size_t> count(1);
-    size_t tb2 = 0;
-    SHARP_HIP_CHECK(rocprim::reduce_by_key(nullptr, tb2, keys2.p, vals2.p, ne, ukeys.p, C.q.p, count.p, rocprim::plus<u64>(),
-                                           rocprim::equal_to<u64>(), c.stream));
-    if (tb2 > tmp.n) tmp.alloc(tb2);
-    tb2 = tmp.n;
-    SHARP_HIP_CHECK(rocprim::reduce_by_key(tmp.p, tb2, keys2.p, vals2.p, ne, ukeys.p, C.q.p, count.p, rocprim::plus<u64>(),
-                                           rocprim::equal_to<u64>(), c.stream));
-    size_t m = 0;
-    count.download(&m, 1);
+    MergeScratch tmp;
+    const size_t m = merge_by_key<u64, Plus>(keys.p, L.val.p, ne, unc * unc, keys2.p, vals2.p, ukeys.p, C.val.p, tmp);
     SHARP_REQUIRE(m >= 1 && m <= ne, "louvain: the coarse graph holds an impossible number of entries");
     C.nnz = static_cast<long long>(m);
     C.row.alloc(m);
     C.col.alloc(m);
     C.row_ptr.alloc(nc + 1);
-    hipLaunchKernelGGL(lv_coarse_kernel, dim3(grid_for(C.nnz, 256)), dim3(256), 0, c.stream, ukeys.p, C.nnz, unc, C.row.p, C.col.p);
-    hipLaunchKernelGGL(lv_coarse_rowptr_kernel, dim3(grid_for(nc + 1, 256)), dim3(256), 0, c.stream, ukeys.p, C.nnz, unc, C.row_ptr.p);
-    launch_check("lv_coarse_kernel");
+    merged_to_csr<u64>(ukeys.p, C.nnz, nc, true, C.row_ptr.p, C.col.p, C.row.p);   // (a coarse vertex may be left without entries)
     fill_strengths(C);
     stream_sync();                                         // (the sort's buffers go out of scope)
 }
@@ -546,7 +474,7 @@ void relabel_by_size(const std::vector<int> &lab, long long nc, std::vector<int>
 
 }  // namespace
 
-void louvain_quantise(const UmapGraph &G, LouvainGraph &L) {
+void louvain_quantise(const Graph &G, LouvainGraph &L) {
     Ctx &c = ctx();
     SHARP_REQUIRE(G.n >= 2 && G.n <= kLvMaxN, "louvain: need 2 <= n <= 16777216 vertices");
     SHARP_REQUIRE(G.nnz >= 1 && G.nnz < kLvMaxNnz, "louvain: need 1 <= nnz < 2^38 entries");
@@ -559,10 +487,8 @@ void louvain_quantise(const UmapGraph &G, LouvainGraph &L) {
     hipLaunchKernelGGL(lv_quantise_kernel, dim3(grid_for(nnz + 1, 256)), dim3(256), 0, c.stream, G.val.p, nnz, G.wmax, q.p, flag.p);
     hipLaunchKernelGGL(lv_rows_kernel, dim3(grid_for(nnz, 256)), dim3(256), 0, c.stream, G.row_ptr.p, G.n, nnz, row.p);
     launch_check("lv_quantise_kernel");
-    size_t bytes = 0;
-    SHARP_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, flag.p, pos.p, 0ll, static_cast<size_t>(nnz + 1), rocprim::plus<long long>(), c.stream));
-    DevBuf<unsigned char> tmp(std::max<size_t>(bytes, 1));
-    SHARP_HIP_CHECK(rocprim::exclusive_scan(tmp.p, bytes, flag.p, pos.p, 0ll, static_cast<size_t>(nnz + 1), rocprim::plus<long long>(), c.stream));
+    Scratch tmp;
+    exclusive_scan(flag.p, pos.p, static_cast<size_t>(nnz + 1), tmp);
     long long kept = 0;
     SHARP_HIP_CHECK(hipMemcpyAsync(&kept, pos.p + nnz, sizeof(long long), hipMemcpyDeviceToHost, c.stream));
     stream_sync();
@@ -572,8 +498,8 @@ void louvain_quantise(const UmapGraph &G, LouvainGraph &L) {
     L.row_ptr.alloc(G.n + 1);
     L.col.alloc(kept);
     L.row.alloc(kept);
-    L.q.alloc(kept);
-    hipLaunchKernelGGL(lv_compact_kernel, dim3(grid_for(nnz, 256)), dim3(256), 0, c.stream, pos.p, G.col.p, row.p, q.p, nnz, L.col.p, L.row.p, L.q.p);
+    L.val.alloc(kept);
+    hipLaunchKernelGGL(lv_compact_kernel, dim3(grid_for(nnz, 256)), dim3(256), 0, c.stream, pos.p, G.col.p, row.p, q.p, nnz, L.col.p, L.row.p, L.val.p);
     hipLaunchKernelGGL(lv_rowptr_map_kernel, dim3(grid_for(G.n + 1, 256)), dim3(256), 0, c.stream, G.row_ptr.p, pos.p, G.n, L.row_ptr.p);
     launch_check("lv_compact_kernel");
     fill_strengths(L);
@@ -589,8 +515,7 @@ void louvain_run(LouvainGraph &L0, const LouvainArgs &a, std::vector<int> &membe
     SHARP_REQUIRE(L0.m2 > 0, "louvain: the graph holds no positive weight");
     const long long n0 = L0.n;
     DevBuf<int> vmap(n0);
-    hipLaunchKernelGGL(lv_iota_kernel, dim3(grid_for(n0, 256)), dim3(256), 0, c.stream, vmap.p, n0);
-    launch_check("lv_iota_kernel");
+    iota(vmap.p, n0);
     levels.clear();
     if (level_membership) level_membership->clear();
     LouvainGraph next, *L = &L0;
@@ -604,8 +529,7 @@ void louvain_run(LouvainGraph &L0, const LouvainArgs &a, std::vector<int> &membe
         DevBuf<int> comm_a(n), comm_b(n);
         int *comm = comm_a.p, *prop = comm_b.p;
         u64 *tot = W.tot.p, *tot2 = W.tot2.p;
-        hipLaunchKernelGGL(lv_iota_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, comm, n);
-        launch_check("lv_iota_kernel");
+        iota(comm, n);
         double Q = lv_state(*L, comm, tot, W, a.resolution, &nc);
         int rounds = 0, fails = 0;
         while (rounds < a.max_rounds && fails < a.max_fails) {
@@ -652,8 +576,6 @@ using namespace sharp;
 
 namespace {
 
-using u64 = unsigned long long;
-
 void check_csr_shape(const std::string &w, const long long *row_ptr, const int *col, long long n) {
     SHARP_REQUIRE(row_ptr && col, w + ": null row_ptr / col");
     SHARP_REQUIRE(n >= 2 && n <= kLvMaxN, w + ": need 2 <= n <= 16777216 vertices");
@@ -669,7 +591,7 @@ void check_csr_shape(const std::string &w, const long long *row_ptr, const int *
 }
 
 // a float-weighted symmetric CSR without diagonal entries on the device (the input of rule 1)
-void upload_float_graph(const std::string &w, const long long *row_ptr, const int *col, const double *val, long long n, UmapGraph &G) {
+void upload_float_graph(const std::string &w, const long long *row_ptr, const int *col, const double *val, long long n, Graph &G) {
     check_csr_shape(w, row_ptr, col, n);
     SHARP_REQUIRE(val, w + ": null val");
     const long long nnz = row_ptr[n];
@@ -715,10 +637,10 @@ void upload_int_graph(const std::string &w, const long long *row_ptr, const int 
     L.row_ptr.upload(row_ptr, n + 1);
     L.col.alloc(nnz);
     L.row.alloc(nnz);
-    L.q.alloc(nnz);
+    L.val.alloc(nnz);
     if (nnz) {
         L.col.upload(col, nnz);
-        L.q.upload(reinterpret_cast<const u64 *>(q), nnz);
+        L.val.upload(reinterpret_cast<const u64 *>(q), nnz);
         hipLaunchKernelGGL(lv_rows_kernel, dim3(grid_for(nnz, 256)), dim3(256), 0, ctx().stream, L.row_ptr.p, n, nnz, L.row.p);
         launch_check("lv_rows_kernel");
     }
@@ -745,7 +667,7 @@ LouvainArgs louvain_args(const std::string &w, double resolution, double tol, in
     return a;
 }
 
-void run_and_report(const std::string &w, const UmapGraph &G, const LouvainArgs &a, int *membership, int level_cap, long long *level_n,
+void run_and_report(const std::string &w, const Graph &G, const LouvainArgs &a, int *membership, int level_cap, long long *level_n,
                     long long *level_communities, int *level_rounds, double *level_q, int *n_levels, int *level_membership) {
     LouvainGraph L;
     louvain_quantise(G, L);
@@ -781,7 +703,7 @@ int sharp_louvain_quantise(const long long *row_ptr, const int *col, const doubl
     Ctx &c = ctx();
     const std::string w("sharp_louvain_quantise");
     SHARP_REQUIRE(q && k && m2, w + ": null output");
-    UmapGraph G;
+    Graph G;
     upload_float_graph(w, row_ptr, col, val, n, G);
     DevBuf<u64> dq(G.nnz);
     DevBuf<long long> flag(G.nnz + 1);
@@ -793,9 +715,9 @@ int sharp_louvain_quantise(const long long *row_ptr, const int *col, const doubl
     L.row.alloc(G.nnz);
     hipLaunchKernelGGL(lv_rows_kernel, dim3(grid_for(G.nnz, 256)), dim3(256), 0, c.stream, G.row_ptr.p, n, G.nnz, L.row.p);
     launch_check("lv_rows_kernel");
-    L.q = std::move(dq);
+    L.val = std::move(dq);
     fill_strengths(L);
-    L.q.download(reinterpret_cast<u64 *>(q), G.nnz);
+    L.val.download(reinterpret_cast<u64 *>(q), G.nnz);
     L.k.download(reinterpret_cast<u64 *>(k), n);
     *m2 = 0;
     for (long long v = 0; v < n; ++v) *m2 += k[v];
@@ -835,7 +757,7 @@ int sharp_louvain_modularity(const long long *row_ptr, const int *col, const dou
     const LouvainArgs a = louvain_args(w, resolution, 0.0, 1, 1, 1, 0.0);
     LouvainGraph L;
     if (val) {
-        UmapGraph G;
+        Graph G;
         upload_float_graph(w, row_ptr, col, val, n, G);
         louvain_quantise(G, L);
     } else {
@@ -873,7 +795,7 @@ int sharp_louvain_aggregate(const long long *row_ptr, const int *col, const long
     *nnz_out = Cg.nnz;
     Cg.row_ptr.download(row_ptr_out, nc + 1);              // (room for n + 1 and nnz entries: the coarse graph is never larger)
     Cg.col.download(col_out, Cg.nnz);
-    Cg.q.download(reinterpret_cast<u64 *>(q_out), Cg.nnz);
+    Cg.val.download(reinterpret_cast<u64 *>(q_out), Cg.nnz);
     dnew.download(new_out, n);
     SHARP_API_END
 }
@@ -887,7 +809,7 @@ int sharp_louvain_graph(const long long *row_ptr, const int *col, const double *
     SHARP_REQUIRE(membership && level_n && level_communities && level_rounds && level_q && n_levels, w + ": null output");
     const LouvainArgs a = louvain_args(w, resolution, tol, max_levels, max_rounds, max_fails, seed);
     SHARP_REQUIRE(level_cap >= max_levels, w + ": level_cap must be at least max_levels");
-    UmapGraph G;
+    Graph G;
     upload_float_graph(w, row_ptr, col, val, n, G);
     run_and_report(w, G, a, membership, level_cap, level_n, level_communities, level_rounds, level_q, n_levels, level_membership);
     SHARP_API_END
@@ -916,7 +838,7 @@ int sharp_louvain_neighbors(const int *index, const double *distance, long long 
         throw sharp::Error(e.code, m);
     }
     if (squared) umap_sqrt_lists(dist, n, K);
-    UmapGraph G;
+    Graph G;
     umap_graph(idx, dist, n, K, G);
     idx.release();
     dist.release();
@@ -935,7 +857,7 @@ int sharp_louvain_snn(const int *index, long long n, int K, double prune, double
     const LouvainArgs a = louvain_args(w, resolution, tol, max_levels, max_rounds, max_fails, seed);
     SHARP_REQUIRE(level_cap >= max_levels, w + ": level_cap must be at least max_levels");
     ctx();
-    UmapGraph G;
+    Graph G;
     {
         DevBuf<int> idx(static_cast<size_t>(n) * K);
         idx.upload(index, static_cast<size_t>(n) * K);

@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "dist_pairs.hpp"
-#include "common.hpp"
+#include "graph.hpp"
 
 namespace sharp {
 
@@ -34,8 +34,6 @@ constexpr int kNrMaxParts = 32;              // workgroups per row tile and slic
 constexpr double kNrXMax = 1.0e100;          // |x| above this is refused: a squared distance stays finite below it (knn_descent.hip's KD_XMAX)
 constexpr unsigned long long NR_OK = ~0ull;
 enum NrKind { NR_RANGE = 1, NR_SELF = 2, NR_TWICE = 3 };
-
-inline unsigned grid_for(long long n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
 
 // tsne.hip: lex_less
 __device__ __forceinline__ bool lex_less(double a, int ia, double b, int ib) { return a < b || (a == b && ia < ib); }

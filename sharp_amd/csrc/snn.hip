@@ -2,7 +2,7 @@
 // is claimed).  A is the n x n 0/1 matrix with k = K + 1 ones per row, S(i) = {i} + the row's K neighbours; the graph is A A^T without
 // its diagonal, s(i, j) = |S(i) n S(j)|, w = s / (2k - s), an entry kept iff s >= smin (prune turned into an integer once, on the host).
 //   reverse    the lists validated (range, self, twice) and the in-degrees |R(m)| counted by integer atomics in one kernel, a scan, the
-//              reverse lists R(m) = {j : m in S(j)} ascending by knn_descent.hip's sort of (target << 32 | source) keys, and the row
+//              reverse lists R(m) = {j : m in S(j)} ascending by graph.hpp's sort of (target << 32 | source) keys, and the row
 //              work t(i) = sum over m in S(i) of |R(m)|, which the host reads once to deal the rows into classes
 //   count      Gustavson's row product per row: for m in S(i), for j in R(m), j != i: count[j] += 1; the entries with count >= smin are
 //              counted, a scan gives row_ptr and nnz.  Three row classes by t(i), all exact:
@@ -18,22 +18,14 @@
 //              unpacked; tab[s] = (double)s / (double)(2k - s) is made on the host
 // No floating-point atomic anywhere; the slot order of a table and the order of the atomics do not reach the result.
 #include "snn.hpp"
+#include "graph_prim.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "knn_descent.hpp"
-
 namespace sharp {
 namespace {
-
-using u64 = unsigned long long;
-
-inline unsigned grid_for(long long n, int per) { return static_cast<unsigned>((std::max<long long>(n, 1) + per - 1) / per); }
 
 enum : int { SNN_RANGE = 0, SNN_SELF = 1, SNN_TWICE = 2 };
 constexpr u64 SNN_OK = ~0ull;
@@ -254,9 +246,8 @@ __global__ __launch_bounds__(256) void snn_unpack_kernel(const u64 *__restrict__
 struct Rev {
     DevBuf<long long> rptr, t;               // n + 1, n
     DevBuf<int> R;                           // n k
-    DevBuf<int> rows_wave, rows_block, rows_dense;
+    RowClasses rows;
     DevBuf<unsigned> scratch;
-    int n_wave = 0, n_block = 0, n_dense = 0, dense_grid = 0;
 };
 
 void build_reverse(const std::string &who, const DevBuf<int> &idx, long long n, int K, Rev &V) {
@@ -280,10 +271,8 @@ void build_reverse(const std::string &who, const DevBuf<int> &idx, long long n, 
         }
     }
     V.rptr.alloc(n + 1);
-    size_t bytes = 0;
-    SHARP_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, deg.p, V.rptr.p, 0ll, static_cast<size_t>(n + 1), rocprim::plus<long long>(), c.stream));
-    DevBuf<unsigned char> tmp(std::max<size_t>(bytes, 1));
-    SHARP_HIP_CHECK(rocprim::exclusive_scan(tmp.p, bytes, deg.p, V.rptr.p, 0ll, static_cast<size_t>(n + 1), rocprim::plus<long long>(), c.stream));
+    Scratch tmp;
+    exclusive_scan(deg.p, V.rptr.p, static_cast<size_t>(n + 1), tmp);
     {
         DevBuf<u64> keys(nk), keys_s(nk);
         DevBuf<int> vals(nk);
@@ -297,36 +286,28 @@ void build_reverse(const std::string &who, const DevBuf<int> &idx, long long n, 
     launch_check("snn_work_kernel");
     std::vector<long long> ht(n);
     V.t.download(ht.data(), ht.size());                     // (synchronises: deg and tmp leave scope)
-    std::vector<int> a, b, d;
-    for (long long i = 0; i < n; ++i) (ht[i] <= kSnnWaveCap ? a : ht[i] <= kSnnBlockCap ? b : d).push_back(static_cast<int>(i));
-    auto up = [](DevBuf<int> &buf, const std::vector<int> &h) { buf.alloc(h.size()); if (!h.empty()) buf.upload(h.data(), h.size()); };
-    up(V.rows_wave, a); up(V.rows_block, b); up(V.rows_dense, d);
-    V.n_wave = static_cast<int>(a.size()); V.n_block = static_cast<int>(b.size()); V.n_dense = static_cast<int>(d.size());
-    V.dense_grid = 0;
-    if (V.n_dense) {
-        // dense rows of n counters each: at most 2^27 slots (512 MB) in all, at most 128 workgroups
-        V.dense_grid = static_cast<int>(std::min<long long>(V.n_dense, std::max<long long>(1, std::min<long long>(128, (1ll << 27) / n))));
-        V.scratch.alloc(static_cast<size_t>(V.dense_grid) * n);
+    V.rows.classify(ht, kSnnWaveCap, kSnnBlockCap, false);
+    if (V.rows.n_dense) {                                         // dense rows of n counters each: at most 512 MB in all
+        V.scratch.alloc(static_cast<size_t>(V.rows.dense_grid) * n);
         V.scratch.zero();
     }
-    stream_sync();                                           // (the host vectors go out of scope)
 }
 
 template <bool FILL>
 void run_product(const DevBuf<int> &idx, long long n, int K, int smin, Rev &V, long long *cnt, int *smax, const long long *rp, u64 *packed) {
     Ctx &c = ctx();
-    if (V.n_wave) {
-        hipLaunchKernelGGL((snn_lds_kernel<64, kSnnWaveSlots, FILL>), dim3(grid_for(V.n_wave, 2)), dim3(128), 0, c.stream, V.rows_wave.p, V.n_wave,
+    if (V.rows.n_wave) {
+        hipLaunchKernelGGL((snn_lds_kernel<64, kSnnWaveSlots, FILL>), dim3(grid_for(V.rows.n_wave, 2)), dim3(128), 0, c.stream, V.rows.rows_wave.p, V.rows.n_wave,
                            idx.p, V.rptr.p, V.R.p, V.t.p, K, smin, cnt, smax, rp, packed);
         launch_check("snn_lds_kernel<64>");
     }
-    if (V.n_block) {
-        hipLaunchKernelGGL((snn_lds_kernel<256, kSnnBlockSlots, FILL>), dim3(V.n_block), dim3(256), 0, c.stream, V.rows_block.p, V.n_block, idx.p,
+    if (V.rows.n_block) {
+        hipLaunchKernelGGL((snn_lds_kernel<256, kSnnBlockSlots, FILL>), dim3(V.rows.n_block), dim3(256), 0, c.stream, V.rows.rows_block.p, V.rows.n_block, idx.p,
                            V.rptr.p, V.R.p, V.t.p, K, smin, cnt, smax, rp, packed);
         launch_check("snn_lds_kernel<256>");
     }
-    if (V.n_dense) {
-        hipLaunchKernelGGL(snn_dense_kernel<FILL>, dim3(V.dense_grid), dim3(256), 0, c.stream, V.rows_dense.p, V.n_dense, idx.p, V.rptr.p, V.R.p, K,
+    if (V.rows.n_dense) {
+        hipLaunchKernelGGL(snn_dense_kernel<FILL>, dim3(V.rows.dense_grid), dim3(256), 0, c.stream, V.rows.rows_dense.p, V.rows.n_dense, idx.p, V.rptr.p, V.R.p, K,
                            smin, V.scratch.p, n, cnt, smax, rp, packed);
         launch_check("snn_dense_kernel");
     }
@@ -346,7 +327,7 @@ void snn_check_args(const std::string &who, long long n, int K, double prune) {
     SHARP_REQUIRE(prune >= 0.0 && prune <= 1.0, who + ": prune must be in [0, 1]");   // (false for NaN too)
 }
 
-void snn_graph(const std::string &who, const DevBuf<int> &idx, long long n, int K, double prune, bool count_only, UmapGraph &G,
+void snn_graph(const std::string &who, const DevBuf<int> &idx, long long n, int K, double prune, bool count_only, Graph &G,
                DevBuf<int> *shared, long long cap) {
     Ctx &c = ctx();
     snn_check_args(who, n, K, prune);
@@ -364,10 +345,8 @@ void snn_graph(const std::string &who, const DevBuf<int> &idx, long long n, int 
         smax.zero();
         SHARP_HIP_CHECK(hipMemsetAsync(cnt.p + n, 0, sizeof(long long), c.stream));
         run_product<false>(idx, n, K, smin, V, cnt.p, smax.p, nullptr, nullptr);
-        size_t bytes = 0;
-        SHARP_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, cnt.p, G.row_ptr.p, 0ll, static_cast<size_t>(n + 1), rocprim::plus<long long>(), c.stream));
-        DevBuf<unsigned char> tmp(std::max<size_t>(bytes, 1));
-        SHARP_HIP_CHECK(rocprim::exclusive_scan(tmp.p, bytes, cnt.p, G.row_ptr.p, 0ll, static_cast<size_t>(n + 1), rocprim::plus<long long>(), c.stream));
+        Scratch tmp;
+        exclusive_scan(cnt.p, G.row_ptr.p, static_cast<size_t>(n + 1), tmp);
         SHARP_HIP_CHECK(hipMemcpyAsync(&nnz, G.row_ptr.p + n, sizeof(long long), hipMemcpyDeviceToHost, c.stream));
         SHARP_HIP_CHECK(hipMemcpyAsync(&hmax, smax.p, sizeof(int), hipMemcpyDeviceToHost, c.stream));
         stream_sync();
@@ -399,12 +378,8 @@ void snn_graph(const std::string &who, const DevBuf<int> &idx, long long n, int 
         DevBuf<double> dtab(tab.size());
         dtab.upload(tab.data(), tab.size());
         // by (row, column): the rows are in place already, so the sort only orders each row's range; keys are unique
-        unsigned bits = 33;
-        while (bits < 64 && (static_cast<u64>(n) >> (bits - 32)) != 0) ++bits;
-        size_t bytes = 0;
-        SHARP_HIP_CHECK(rocprim::radix_sort_keys(nullptr, bytes, packed.p, sorted.p, static_cast<size_t>(nnz), 8, bits, c.stream));
-        DevBuf<unsigned char> tmp(std::max<size_t>(bytes, 1));
-        SHARP_HIP_CHECK(rocprim::radix_sort_keys(tmp.p, bytes, packed.p, sorted.p, static_cast<size_t>(nnz), 8, bits, c.stream));
+        Scratch tmp;
+        sort_keys(packed.p, sorted.p, static_cast<size_t>(nnz), 8, key_bits(static_cast<u64>(n) << 32), tmp);
         hipLaunchKernelGGL(snn_unpack_kernel, dim3(grid_for(nnz, 256)), dim3(256), 0, c.stream, sorted.p, nnz, dtab.p, G.col.p, G.val.p,
                            shared ? shared->p : nullptr);
         launch_check("snn_unpack_kernel");
@@ -437,7 +412,7 @@ int sharp_snn_graph(const int *index, long long n, int K, double prune, long lon
     ctx();
     DevBuf<int> idx(static_cast<size_t>(n) * K);
     idx.upload(index, static_cast<size_t>(n) * K);
-    UmapGraph G;
+    Graph G;
     DevBuf<int> ds;
     try {
         snn_graph(w, idx, n, K, prune, col == nullptr, G, shared ? &ds : nullptr, col ? std::max<long long>(cap, 0) : -1);

@@ -1,13 +1,12 @@
 // snn.hpp -- the shared-nearest-neighbour graph with Jaccard weights (Seurat's ComputeSNN): from k-NN lists, the sparse
 // product A A^T of the 0/1 matrix with k = K + 1 ones per row (the row itself and its K neighbours), the diagonal left out:
 // s(i, j) = |S(i) n S(j)|, w = s / (2k - s), an entry kept iff w >= prune.  Everything the device computes is an integer, so a call is a
-// pure function of its arguments.  The result is a UmapGraph on the device: what louvain_quantise takes.  The C ABI entries
+// pure function of its arguments.  The result is a Graph (graph.hpp) on the device: what louvain_quantise takes.  The C ABI entries
 // (sharp_snn_graph, sharp_louvain_snn, include/sharp_hip.h) wrap these.
 #pragma once
 #include <string>
 
-#include "common.hpp"
-#include "umap.hpp"
+#include "graph.hpp"
 
 namespace sharp {
 
@@ -25,7 +24,7 @@ void snn_check_args(const std::string &who, long long n, int K, double prune);
 // idx: n x K on the device, not yet validated (range, self, an index twice in a row are refused here, before an index is dereferenced).
 // count_only: G.row_ptr, G.n and G.nnz only.  Otherwise G in full (col ascending within a row, val, wmax) and, when wanted, the s of
 // every entry.  cap >= 0: a graph of more entries is refused after the count, with the count in the message and in G.nnz.
-void snn_graph(const std::string &who, const DevBuf<int> &idx, long long n, int K, double prune, bool count_only, UmapGraph &G,
+void snn_graph(const std::string &who, const DevBuf<int> &idx, long long n, int K, double prune, bool count_only, Graph &G,
                DevBuf<int> *shared, long long cap = -1);
 
 }  // namespace sharp

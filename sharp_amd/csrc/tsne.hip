@@ -14,6 +14,7 @@
 //                       (gains, velocity, position), mean subtraction, KL every 50 iterations
 // No floating-point atomics anywhere; every reduction runs in an order fixed by n alone, so a call is bitwise reproducible.
 #include "tsne.hpp"
+#include "graph_prim.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -22,10 +23,6 @@
 #include <cmath>
 #include <string>
 #include <vector>
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_reduce_by_key.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include "dist_pairs.hpp"
 #include "linalg.hpp"
@@ -36,36 +33,9 @@ namespace {
 
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
-inline unsigned grid_for(long long n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
-
 // ---------------------------------------------------------------------------------------------------------------------------
-// fixed-order reductions
+// column statistics in a fixed order (the sum of a whole vector is graph.hpp's fixed_reduce)
 // ---------------------------------------------------------------------------------------------------------------------------
-// sum of v[0..n): block b sums its chunk (strided per thread, then a tree), one block sums the block partials the same way
-constexpr int kSumBlocks = 1024;
-__global__ __launch_bounds__(256) void sum_partial_kernel(const double *__restrict__ v, long long n, long long chunk, double *__restrict__ part) {
-    __shared__ double s[256];
-    const int tid = threadIdx.x;
-    const long long b0 = static_cast<long long>(blockIdx.x) * chunk, e = b0 + chunk < n ? b0 + chunk : n;
-    double a = 0.0;
-    for (long long k = b0 + tid; k < e; k += 256) a += v[k];
-    s[tid] = a;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) s[tid] += s[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) part[blockIdx.x] = s[0];
-}
-
-void sum_fixed(const double *v, long long n, double *part, double *out) {   // out: device scalar; part: kSumBlocks doubles
-    const long long chunk = std::max<long long>(256, (n + kSumBlocks - 1) / kSumBlocks);
-    const unsigned nb = grid_for(std::max<long long>(n, 1), static_cast<int>(std::min<long long>(chunk, INT_MAX)));
-    hipLaunchKernelGGL(sum_partial_kernel, dim3(nb), dim3(256), 0, ctx().stream, v, n, chunk, part);
-    hipLaunchKernelGGL(sum_partial_kernel, dim3(1), dim3(256), 0, ctx().stream, part, static_cast<long long>(nb), static_cast<long long>(nb), out);
-    launch_check("sum_partial_kernel");
-}
-
 // column sums of X (n x d, row i at X + i * ld) over slabs of rows: part[s * d + c]; with mu, sums of (x - mu)^2
 __global__ __launch_bounds__(256) void colsum_kernel(const double *__restrict__ X, long long n, int d, long long ld, long long rps,
                                                      const double *__restrict__ mu, double *__restrict__ part) {
@@ -110,21 +80,6 @@ __global__ __launch_bounds__(256) void affine_kernel(const double *X, long long 
     double v = X[r * ld + c];
     if (mu) v = v - mu[c];
     out[e] = v / (sd ? sd[c] : scal);
-}
-
-__global__ __launch_bounds__(256) void absmax_kernel(const double *__restrict__ v, long long n, long long chunk, double *__restrict__ part) {
-    __shared__ double s[256];
-    const int tid = threadIdx.x;
-    const long long b0 = static_cast<long long>(blockIdx.x) * chunk, e = b0 + chunk < n ? b0 + chunk : n;
-    double a = 0.0;
-    for (long long k = b0 + tid; k < e; k += 256) a = fmax(a, fabs(v[k]));
-    s[tid] = a;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) s[tid] = fmax(s[tid], s[tid + w]);
-        __syncthreads();
-    }
-    if (tid == 0) part[blockIdx.x] = s[0];
 }
 
 // out (n x k) = Xc (n x d) . V (d x k), one thread per output, sequential over d
@@ -541,12 +496,6 @@ __global__ __launch_bounds__(256) void square_kernel(double *__restrict__ v, lon
 // perplexity calibration: one wave per row, fp64 (bhtsne's bisection: beta from 1, doubling / halving while a bound is open, tol 1e-5
 // on the entropy in nats, at most 200 steps)
 // ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
 __global__ __launch_bounds__(256) void calib_kernel(const double *__restrict__ dist, long long n, int K, double logU, double *__restrict__ P) {
     const int lane = threadIdx.x & 63;
     const long long i = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
@@ -596,19 +545,6 @@ __global__ __launch_bounds__(256) void coo_kernel(const int *__restrict__ idx, c
     vals[2 * e] = p;
     keys[2 * e + 1] = j * static_cast<unsigned long long>(n) + i;
     vals[2 * e + 1] = p;
-}
-
-__global__ __launch_bounds__(256) void csr_kernel(const unsigned long long *__restrict__ keys, const double *__restrict__ uvals, long long nnz,
-                                                  long long n, const double *__restrict__ total, long long *__restrict__ rp, int *__restrict__ col,
-                                                  double *__restrict__ val) {
-    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (e >= nnz) return;
-    const unsigned long long un = static_cast<unsigned long long>(n);
-    const long long r = static_cast<long long>(keys[e] / un);
-    col[e] = static_cast<int>(keys[e] - static_cast<unsigned long long>(r) * un);
-    val[e] = uvals[e] / total[0];
-    if (e == 0 || static_cast<long long>(keys[e - 1] / un) != r) rp[r] = e;
-    if (e == nnz - 1) rp[n] = nnz;
 }
 
 __global__ __launch_bounds__(256) void scale_kernel(double *__restrict__ v, long long n, double f, int divide) {
@@ -863,11 +799,6 @@ __global__ __launch_bounds__(256) void bh_key_kernel(const double *__restrict__ 
     key[i] = K;
 }
 
-__global__ __launch_bounds__(256) void iota_kernel(int *__restrict__ v, long long n) {
-    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (i < n) v[i] = static_cast<int>(i);
-}
-
 template <int DIMS>
 __global__ __launch_bounds__(256) void bh_gather_kernel(const double *__restrict__ Y, const int *__restrict__ perm, long long n, double *__restrict__ Ys) {
     const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
@@ -1060,13 +991,11 @@ struct BhTree {
     DevBuf<double> Ys, lay, part, root, com;
     DevBuf<unsigned> cnt, off;
     DevBuf<uint4> meta;
-    DevBuf<unsigned char> sort_tmp, scan_tmp;
-    size_t sort_bytes = 0, scan_bytes = 0;
+    Scratch sort_tmp, scan_tmp;   // (sized by the first build, reused by every later one: the counts do not change)
     BhLayers L{};
     int nslab = 1, end_bit = 64;
     long long rps = 1;
     void init(long long n, int dims) {
-        Ctx &c = ctx();
         const size_t nn = static_cast<size_t>(n);
         key.alloc(nn); key_s.alloc(nn); iota.alloc(nn); perm.alloc(nn);
         Ys.alloc(nn * dims);
@@ -1092,12 +1021,7 @@ struct BhTree {
             L.p[l] = l == 0 ? Ys.p : lay.p + at[l] * dims;
         }
         end_bit = dims == 1 ? 63 : (dims == 2 ? 64 : 63);
-        hipLaunchKernelGGL(iota_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, iota.p, n);
-        launch_check("iota_kernel");
-        SHARP_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, key.p, key_s.p, iota.p, perm.p, nn, 0, end_bit, c.stream));
-        sort_tmp.alloc(std::max<size_t>(sort_bytes, 1));
-        SHARP_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, cnt.p, off.p, 0u, nn + 1, rocprim::plus<unsigned>(), c.stream));
-        scan_tmp.alloc(std::max<size_t>(scan_bytes, 1));
+        sharp::iota(iota.p, n);
     }
 };
 
@@ -1119,7 +1043,7 @@ struct Work {
         zrow.alloc(n); kl.alloc(n);
         if (theta > 0.0) bh.init(n, dims);
         else part.alloc(static_cast<size_t>(plan.nc) * plan.rows * 4);
-        red.alloc(kSumBlocks);
+        red.alloc(kRedBlocks);
         scal.alloc(8);
     }
 };
@@ -1136,18 +1060,14 @@ void bh_build(Work &w) {
     hipLaunchKernelGGL(bh_root_kernel<DIMS>, dim3(1), dim3(64), 0, c.stream, t.part.p, t.nslab, n, t.root.p);
     hipLaunchKernelGGL(bh_key_kernel<DIMS>, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, w.Y.p, n, t.root.p, t.key.p);
     launch_check("bh_key_kernel");
-    size_t bytes = t.sort_bytes;
-    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(t.sort_tmp.p, bytes, t.key.p, t.key_s.p, t.iota.p, t.perm.p, static_cast<size_t>(n), 0, t.end_bit,
-                                              c.stream));
+    sort_pairs(t.key.p, t.key_s.p, t.iota.p, t.perm.p, static_cast<size_t>(n), 0, t.end_bit, t.sort_tmp, t.sort_tmp.n > 0);
     hipLaunchKernelGGL(bh_gather_kernel<DIMS>, dim3(grid_for(n * DIMS, 256)), dim3(256), 0, c.stream, w.Y.p, t.perm.p, n, t.Ys.p);
     for (int l = 1; l < t.L.nl; ++l)
         hipLaunchKernelGGL(bh_layer_kernel<DIMS>, dim3(grid_for(t.L.len[l], 256)), dim3(256), 0, c.stream, t.L.p[l - 1], t.L.len[l - 1],
                            const_cast<double *>(t.L.p[l]), t.L.len[l]);
     hipLaunchKernelGGL(bh_count_kernel<DIMS>, dim3(grid_for(n + 1, 256)), dim3(256), 0, c.stream, t.key_s.p, n, t.cnt.p);
     launch_check("bh_count_kernel");
-    bytes = t.scan_bytes;
-    SHARP_HIP_CHECK(rocprim::exclusive_scan(t.scan_tmp.p, bytes, t.cnt.p, t.off.p, 0u, static_cast<size_t>(n) + 1, rocprim::plus<unsigned>(),
-                                            c.stream));
+    exclusive_scan(t.cnt.p, t.off.p, static_cast<size_t>(n) + 1, t.scan_tmp, t.scan_tmp.n > 0);
     hipLaunchKernelGGL(bh_node_kernel<DIMS>, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, t.key_s.p, t.perm.p, n, t.off.p, t.L, t.meta.p,
                        t.com.p);
     launch_check("bh_node_kernel");
@@ -1175,7 +1095,7 @@ void gradient_terms(const TsneP &P, Work &w) {
         hipLaunchKernelGGL(bh_walk_kernel<DIMS>, dim3(grid_for(w.n, 256)), dim3(256), 0, c.stream, w.bh.Ys.p, w.bh.perm.p, w.n, w.bh.meta.p,
                            w.bh.com.p, w.bh.root.p, w.theta, w.rep.p, w.zrow.p);
         launch_check("bh_walk_kernel");
-        sum_fixed(w.zrow.p, w.n, w.red.p, w.scal.p);
+        fixed_reduce(Fold::Sum, w.zrow.p, w.n, w.red.p, w.scal.p);
         return;
     }
     KernelTimer t("tsne_rep");
@@ -1186,7 +1106,7 @@ void gradient_terms(const TsneP &P, Work &w) {
                            w.rep.p, w.zrow.p);
         launch_check("rep_kernel");
     }
-    sum_fixed(w.zrow.p, w.n, w.red.p, w.scal.p);
+    fixed_reduce(Fold::Sum, w.zrow.p, w.n, w.red.p, w.scal.p);
 }
 
 template <int DIMS>
@@ -1194,7 +1114,7 @@ void kl_eval(const TsneP &P, Work &w, double *dst) {
     KernelTimer t("tsne_kl");
     hipLaunchKernelGGL(kl_kernel<DIMS>, dim3(grid_for(w.n, 256)), dim3(256), 0, ctx().stream, P.row_ptr.p, P.col.p, P.val.p, w.Y.p, w.n, w.scal.p, w.kl.p);
     launch_check("kl_kernel");
-    sum_fixed(w.kl.p, w.n, w.red.p, dst);
+    fixed_reduce(Fold::Sum, w.kl.p, w.n, w.red.p, dst);
 }
 
 struct LoopArgs {
@@ -1343,11 +1263,9 @@ void tsne_prepare(const double *X, long long n, int d, long long ld, bool pca, i
         column_stat(out.p, n, dd, dd, nullptr, static_cast<double>(n), part, stat.p);
         hipLaunchKernelGGL(affine_kernel, dim3(grid_for(n * dd, 256)), dim3(256), 0, c.stream, out.p, n, dd, static_cast<long long>(dd), stat.p,
                            nullptr, 1.0, out.p);
-        const long long chunk = std::max<long long>(256, (n * dd + kSumBlocks - 1) / kSumBlocks);
-        const unsigned nb = grid_for(n * dd, static_cast<int>(std::min<long long>(chunk, INT_MAX)));
+        const unsigned nb = fixed_reduce_blocks(n * dd);
         DevBuf<double> mx(nb);
-        hipLaunchKernelGGL(absmax_kernel, dim3(nb), dim3(256), 0, c.stream, out.p, n * dd, chunk, mx.p);
-        launch_check("absmax_kernel");
+        fixed_reduce_parts(Fold::AbsMax, out.p, n * dd, mx.p);
         std::vector<double> hm(nb);
         mx.download(hm.data(), nb);
         double m = 0.0;
@@ -1422,32 +1340,18 @@ void tsne_affinities(const DevBuf<int> &idx, const DevBuf<double> &dist, long lo
     hipLaunchKernelGGL(coo_kernel, dim3(grid_for(n * K, 256)), dim3(256), 0, c.stream, idx.p, Pc.p, n, K, keys.p, vals.p);
     launch_check("coo_kernel");
     Pc.release();
-    unsigned bits = 1;
-    while (bits < 64 && (static_cast<unsigned long long>(n) * static_cast<unsigned long long>(n) >> bits) != 0) ++bits;
-    size_t tmp_bytes = 0;
-    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.p, keys2.p, vals.p, vals2.p, ne, 0, bits, c.stream));
-    DevBuf<unsigned char> tmp(std::max<size_t>(tmp_bytes, 1));
-    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys.p, keys2.p, vals.p, vals2.p, ne, 0, bits, c.stream));
     // merge the (at most two) entries of a key: p_ij + p_ji
-    DevBuf<size_t> count(1);
-    size_t tmp2 = 0;
-    SHARP_HIP_CHECK(rocprim::reduce_by_key(nullptr, tmp2, keys2.p, vals2.p, ne, keys.p, vals.p, count.p, rocprim::plus<double>(),
-                                           rocprim::equal_to<unsigned long long>(), c.stream));
-    if (tmp2 > tmp.n) tmp.alloc(tmp2);
-    tmp2 = tmp.n;
-    SHARP_HIP_CHECK(rocprim::reduce_by_key(tmp.p, tmp2, keys2.p, vals2.p, ne, keys.p, vals.p, count.p, rocprim::plus<double>(),
-                                           rocprim::equal_to<unsigned long long>(), c.stream));
-    size_t nnz = 0;
-    count.download(&nnz, 1);
-    DevBuf<double> red(kSumBlocks), total(1);
-    sum_fixed(vals.p, static_cast<long long>(nnz), red.p, total.p);
+    const u64 un = static_cast<u64>(n);
+    MergeScratch tmp;
+    const size_t nnz = merge_by_key<double, Plus>(keys.p, vals.p, ne, un * un, keys2.p, vals2.p, keys.p, vals.p, tmp);
+    DevBuf<double> red(kRedBlocks), total(1);
+    fixed_reduce(Fold::Sum, vals.p, static_cast<long long>(nnz), red.p, total.p);
     P.n = n;
     P.nnz = static_cast<long long>(nnz);
     P.row_ptr.alloc(n + 1);
     P.col.alloc(nnz);
     P.val.alloc(nnz);
-    hipLaunchKernelGGL(csr_kernel, dim3(grid_for(P.nnz, 256)), dim3(256), 0, c.stream, keys.p, vals.p, P.nnz, n, total.p, P.row_ptr.p, P.col.p, P.val.p);
-    launch_check("csr_kernel");
+    merged_to_csr<double>(keys.p, P.nnz, n, false, P.row_ptr.p, P.col.p, nullptr, vals.p, total.p, P.val.p);   // (no row is empty: K entries each)
     stream_sync();
 }
 

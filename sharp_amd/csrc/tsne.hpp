@@ -2,17 +2,12 @@
 // (PCA, normalisation), exact k-NN on the f64 MFMA, per-row perplexity calibration, the symmetric P in CSR, and the optimiser loop with
 // an exact O(n^2) repulsion or bhtsne's Barnes-Hut one.  The C ABI entries (sharp_tsne*, include/sharp_hip.h) are thin wrappers over these.
 #pragma once
-#include "common.hpp"
+#include "graph.hpp"
 
 namespace sharp {
 
 // P = (P_cond + P_cond^T) / sum, CSR on the device (rows sorted by column)
-struct TsneP {
-    long long n = 0, nnz = 0;
-    DevBuf<long long> row_ptr;   // n + 1
-    DevBuf<int> col;             // nnz
-    DevBuf<double> val;          // nnz
-};
+using TsneP = Csr<double>;
 
 // X (n rows of d values, row i at X + i * ld, host) -> the prepared matrix on the device (n x d_out, row-major, ld d_out):
 // PCA to min(initial_dims, d) components if pca, then centring and division by the largest |entry| if normalize

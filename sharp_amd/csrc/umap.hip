@@ -10,6 +10,7 @@
 //              (seed, epoch, edge, term) alone, so any range of epochs can be run from a given Y.
 // fp64 throughout, no floating-point atomics, every sum in an order fixed by the shape alone: a call is bitwise reproducible.
 #include "umap.hpp"
+#include "graph_prim.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -18,51 +19,11 @@
 #include <string>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_reduce_by_key.hpp>
-
 #include "rrng.hpp"
 #include "tsne.hpp"
 
 namespace sharp {
 namespace {
-
-inline unsigned grid_for(long long n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// fixed-order reductions: block b folds its chunk (strided per thread, then a tree), one block folds the block results the same way
-// ---------------------------------------------------------------------------------------------------------------------------
-constexpr int kRedBlocks = 1024;
-template <bool MAX>
-__global__ __launch_bounds__(256) void reduce_kernel(const double *__restrict__ v, long long n, long long chunk, double *__restrict__ part) {
-    __shared__ double s[256];
-    const int tid = threadIdx.x;
-    const long long b0 = static_cast<long long>(blockIdx.x) * chunk, e = b0 + chunk < n ? b0 + chunk : n;
-    double a = 0.0;   // (the values are >= 0: 0 is the identity of max too)
-    for (long long k = b0 + tid; k < e; k += 256) a = MAX ? fmax(a, v[k]) : a + v[k];
-    s[tid] = a;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) s[tid] = MAX ? fmax(s[tid], s[tid + w]) : s[tid] + s[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) part[blockIdx.x] = s[0];
-}
-
-template <bool MAX>
-void reduce_fixed(const double *v, long long n, double *part, double *out) {   // out: device scalar; part: kRedBlocks doubles
-    const long long chunk = std::max<long long>(256, (n + kRedBlocks - 1) / kRedBlocks);
-    const unsigned nb = static_cast<unsigned>((std::max<long long>(n, 1) + chunk - 1) / chunk);
-    hipLaunchKernelGGL(reduce_kernel<MAX>, dim3(nb), dim3(256), 0, ctx().stream, v, n, chunk, part);
-    hipLaunchKernelGGL(reduce_kernel<MAX>, dim3(1), dim3(256), 0, ctx().stream, part, static_cast<long long>(nb), static_cast<long long>(nb), out);
-    launch_check("reduce_kernel");
-}
 
 __global__ __launch_bounds__(256) void sqrt_kernel(double *__restrict__ v, long long n) {
     const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
@@ -140,35 +101,9 @@ __global__ __launch_bounds__(256) void sigma_kernel(const int *__restrict__ idx,
     }
 }
 
-// the fuzzy union of the at most two entries of a key (commutative: the result does not depend on the sort's order of equal keys)
-struct FuzzyUnion {
-    __host__ __device__ double operator()(const double &x, const double &y) const { return x + y - x * y; }
-};
-
-__global__ __launch_bounds__(256) void csr_kernel(const unsigned long long *__restrict__ keys, const double *__restrict__ uvals, long long nnz,
-                                                  long long n, long long *__restrict__ rp, int *__restrict__ col, double *__restrict__ val) {
-    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (e >= nnz) return;
-    const unsigned long long un = static_cast<unsigned long long>(n);
-    const long long r = static_cast<long long>(keys[e] / un);
-    col[e] = static_cast<int>(keys[e] - static_cast<unsigned long long>(r) * un);
-    val[e] = uvals[e];
-    if (e == 0 || static_cast<long long>(keys[e - 1] / un) != r) rp[r] = e;   // (every row holds its own K entries: none is empty)
-    if (e == nnz - 1) rp[n] = nnz;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // epochs
 // ---------------------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {   // the splitmix64 finaliser
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
 __device__ __forceinline__ double clip4(double v) { return fmin(4.0, fmax(-4.0, v)); }
 
 // One wave per row i, lanes over the slots s = edge * T + term of the row (T = 1 + negative_sample_rate), pass after pass of 64 in
@@ -320,38 +255,25 @@ void umap_graph(const DevBuf<int> &idx, const DevBuf<double> &dist, long long n,
         DevBuf<double> rowsum(n);
         hipLaunchKernelGGL(row_stat_kernel, dim3(grid_for(n, 4)), dim3(256), 0, c.stream, dist.p, n, K, rho.p, rowsum.p);
         launch_check("row_stat_kernel");
-        reduce_fixed<false>(rowsum.p, n, red.p, scal.p);
+        fixed_reduce(Fold::Sum, rowsum.p, n, red.p, scal.p);
         hipLaunchKernelGGL(sigma_kernel, dim3(grid_for(n, 4)), dim3(256), 0, c.stream, idx.p, dist.p, n, K, std::log2(static_cast<double>(K + 1)),
                            rho.p, rowsum.p, scal.p, sigma.p, keys.p, vals.p);
         launch_check("sigma_kernel");
         stream_sync();   // (rowsum goes out of scope)
     }
     KernelTimer t("umap_sym");
-    unsigned bits = 1;
-    while (bits < 64 && (static_cast<unsigned long long>(n) * static_cast<unsigned long long>(n) >> bits) != 0) ++bits;
-    size_t tmp_bytes = 0;
-    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.p, keys2.p, vals.p, vals2.p, ne, 0, bits, c.stream));
-    DevBuf<unsigned char> tmp(std::max<size_t>(tmp_bytes, 1));
-    SHARP_HIP_CHECK(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys.p, keys2.p, vals.p, vals2.p, ne, 0, bits, c.stream));
-    DevBuf<size_t> count(1);
-    size_t tmp2 = 0;
-    SHARP_HIP_CHECK(rocprim::reduce_by_key(nullptr, tmp2, keys2.p, vals2.p, ne, keys.p, vals.p, count.p, FuzzyUnion(),
-                                           rocprim::equal_to<unsigned long long>(), c.stream));
-    if (tmp2 > tmp.n) tmp.alloc(tmp2);
-    tmp2 = tmp.n;
-    SHARP_HIP_CHECK(rocprim::reduce_by_key(tmp.p, tmp2, keys2.p, vals2.p, ne, keys.p, vals.p, count.p, FuzzyUnion(),
-                                           rocprim::equal_to<unsigned long long>(), c.stream));
-    size_t nnz = 0;
-    count.download(&nnz, 1);
+    // the fuzzy union of the at most two entries of a key
+    const u64 un = static_cast<u64>(n);
+    MergeScratch tmp;
+    const size_t nnz = merge_by_key<double, FuzzyUnion>(keys.p, vals.p, ne, un * un, keys2.p, vals2.p, keys.p, vals.p, tmp);
     SHARP_REQUIRE(nnz >= static_cast<size_t>(n) * K && nnz <= ne, "umap_graph: the union holds an impossible number of entries");
-    reduce_fixed<true>(vals.p, static_cast<long long>(nnz), red.p, scal.p + 1);
+    fixed_reduce(Fold::Max, vals.p, static_cast<long long>(nnz), red.p, scal.p + 1);
     G.n = n;
     G.nnz = static_cast<long long>(nnz);
     G.row_ptr.alloc(n + 1);
     G.col.alloc(nnz);
     G.val.alloc(nnz);
-    hipLaunchKernelGGL(csr_kernel, dim3(grid_for(G.nnz, 256)), dim3(256), 0, c.stream, keys.p, vals.p, G.nnz, n, G.row_ptr.p, G.col.p, G.val.p);
-    launch_check("csr_kernel");
+    merged_to_csr<double>(keys.p, G.nnz, n, false, G.row_ptr.p, G.col.p, nullptr, vals.p, nullptr, G.val.p);   // (no row is empty: K entries each)
     SHARP_HIP_CHECK(hipMemcpyAsync(&G.wmax, scal.p + 1, sizeof(double), hipMemcpyDeviceToHost, c.stream));
     stream_sync();
 }

@@ -3,18 +3,12 @@
 // hashed negative samples, all rows updated at once from the old positions).  Input preparation, the exact k-NN and the validation of
 // given lists are t-SNE's (tsne.hpp).  The C ABI entries (sharp_umap*, include/sharp_hip.h) are thin wrappers over these.
 #pragma once
-#include "common.hpp"
+#include "graph.hpp"
 
 namespace sharp {
 
 // W = A + A^T - A o A^T, CSR on the device (rows sorted by column), wmax = max W
-struct UmapGraph {
-    long long n = 0, nnz = 0;
-    DevBuf<long long> row_ptr;   // n + 1
-    DevBuf<int> col;             // nnz
-    DevBuf<double> val;          // nnz
-    double wmax = 0.0;
-};
+using UmapGraph = Graph;
 
 // a, b minimising sum_k (1 / (1 + a x_k^(2b)) - y(x_k))^2 over the 300 points x = linspace(0, 3 spread); host only, no device
 void umap_ab(double spread, double min_dist, double *a, double *b);

@@ -27,24 +27,6 @@ namespace {
 constexpr double kSpectralTol = 1e-6;
 constexpr int kSpectralMaxSteps = 400;
 constexpr int kCheckEvery = 8;      // steps between two solves of T on the host (and once more at max_steps)
-constexpr int kRedBlocks = 1024;    // a length-n sum: at most this many chunks, each folded by a tree, the chunks by one more tree
-
-inline unsigned grid_for(long long n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
-__host__ __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {   // the splitmix64 finaliser (§13's mix)
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // connected components

@@ -35,8 +35,6 @@ constexpr double KNN_INF = 1.0e300;
 constexpr int KREG = 16;      // k-steps of four columns whose A fragments stay in registers
 constexpr size_t LDS_MAX = 160 * 1024;   // LDS of a gfx950 compute unit
 
-inline unsigned grid_for(long long n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
-
 // ---- copies of small device helpers, each named after its original ---------------------------------------------------------------------
 // tsne.hip: lex_less
 __device__ __forceinline__ bool lex_less(double a, int ia, double b, int ib) { return a < b || (a == b && ia < ib); }
@@ -72,23 +70,6 @@ __device__ __forceinline__ void knn_offer(double v, int ci, bool valid, double *
         widx = bi;
         wpos = bp;
     }
-}
-
-// umap.hip: wave_sum (the butterfly leaves every lane the same bits)
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
-// umap.hip: mix64 (the splitmix64 finaliser)
-__host__ __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
 }
 
 // umap.hip: clip4

@@ -1,7 +1,7 @@
 """The Louvain specification of DESIGN.md §18 in numpy: integer weights, one synchronous round of local moving under the hashed
 source / target bits, the fixed-order modularity, aggregation and the driver over the levels.  This is the project's own specification;
 no parity with networkx, igraph or cuGraph is claimed.  Every sum of weights is an int64 sum (exact, order-independent), every fp64
-expression is written in the operation order the kernels use, and the sum of the modularity's terms runs in the order of umap.hip's
+expression is written in the operation order the kernels use, and the sum of the modularity's terms runs in the order of graph.hpp's
 two-stage reduction, so the GPU tests ask for equal bits.  No Python loop runs over vertices or entries.  The case builders of the
 tests are at the end."""
 import numpy as np
@@ -103,7 +103,7 @@ def move(rp, col, q, comm, gamma, seed, level, rnd, k=None, tot=None):
 
 # ---- rule 3: modularity ---------------------------------------------------------------------------------------------------------------
 def fixed_sum(v):
-    """umap.hip's reduce_fixed: blocks of chunk values, 256 strided running sums per block folded by a tree, then the same once more"""
+    """graph.hpp's fixed_reduce: blocks of chunk values, 256 strided running sums per block folded by a tree, then the same once more"""
     def stage(v, chunk):
         n = v.size
         nb = (max(n, 1) + chunk - 1) // chunk

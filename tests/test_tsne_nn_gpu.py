@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 from scipy.spatial.distance import cdist
 
+import _snn_ref
 import _tsne_nn_ref as nn
 import _tsne_ref as ref
 
@@ -92,6 +93,54 @@ def test_affinities_from_neighbours_match_reference(sa, blobs1500, perplexity, K
     rp3, col3, val3 = tsne._affinities_nn(idx, np.sqrt(d2), perplexity)
     assert np.array_equal(rp3, P.indptr) and np.array_equal(col3, P.indices)
     np.testing.assert_allclose(val3, P.data, rtol=1e-10, atol=0)
+
+
+def _ring_lists(n, K):
+    """row i names i + 1 .. i + K mod n, with squared distances that ascend along a row and differ between rows"""
+    idx = _snn_ref.ring(n, K)
+    d2 = np.sort(np.random.default_rng(n * 1000 + K).uniform(0.5, 2.0, size=(n, K)), axis=1)
+    return idx, d2
+
+
+def _check_p(idx, d2, perplexity):
+    """the stage's P against the reference's: the pattern exactly, the values at the bar of test_affinities_from_neighbours_match_reference"""
+    from sharp_amd import tsne
+
+    P = nn.joint_p_from_neighbours(idx, d2, perplexity)
+    rp, col, val = tsne._affinities_nn(idx, d2, perplexity, squared=True)
+    assert np.array_equal(rp, P.indptr) and np.array_equal(col, P.indices)
+    np.testing.assert_allclose(val, P.data, rtol=1e-10, atol=0)
+    return rp, col
+
+
+# The edges of the CSR builder behind the symmetrisation (sort by row * n + col, merge equal keys, split the keys) that k-NN lists of
+# random points do not pin down.
+def test_affinities_without_a_mutual_pair(sa):
+    """a directed ring, n = 40, K = 3: i names j and j names i never both (that needs a + b = 0 mod 40 with a, b in 1 .. 3), so no key
+    appears twice and nothing is merged"""
+    idx, d2 = _ring_lists(40, 3)
+    rp, col = _check_p(idx, d2, 2.0)
+    assert col.size == 2 * 40 * 3 and np.array_equal(np.diff(rp), np.full(40, 6))
+
+
+def test_affinities_with_every_pair_mutual(sa):
+    """the complete graph, n = K + 1 = 9: every key appears twice"""
+    n = 9
+    idx = _snn_ref.complete_lists(n)
+    d2 = np.sort(np.random.default_rng(9).uniform(0.5, 2.0, size=(n, n - 1)), axis=1)
+    rp, col = _check_p(idx, d2, 2.0)
+    assert col.size == n * (n - 1) and np.array_equal(col.reshape(n, n - 1), idx)
+
+
+@pytest.mark.parametrize("n", [255, 256, 257])
+def test_affinities_where_the_key_width_changes(sa, n):
+    """n * n reaches 2^16 at n = 256, so the sort's end bit (the width of n * n) moves from 16 to 17; the largest key, the last row's
+    last column (n - 1, n - 2), must come out last"""
+    idx, d2 = _ring_lists(n, 5)
+    assert (n * n).bit_length() == (16 if n == 255 else 17)
+    rp, col = _check_p(idx, d2, 3.0)
+    assert rp[n] == col.size == 2 * n * 5 and rp[n - 1] < rp[n] and col[-1] == n - 2
+    assert col[0] == 1 and rp[0] == 0 and rp[1] == 10                # (row 0: the columns 1 .. 5 and n - 5 .. n - 1)
 
 
 # ---- 3. the bits of the direct path ------------------------------------------------------------------------------------------------

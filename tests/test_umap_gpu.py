@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import _snn_ref
 import _umap_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -60,13 +61,20 @@ def test_graph_matches_the_reference(sa, stages, case, K):
     share = (np.abs(sigma - rsigma) <= 1e-12 * rsigma).mean()
     print(f"K = {K}: share of rows with the reference's sigma {share}")
     assert share >= 0.99
+    _check_union(idx, d, rp, col, val, rho, sigma, f"K = {K}")
+
+
+def _check_union(idx, d, rp, col, val, rho, sigma, label, one_sided=True, two_sided=True):
+    """W on the stage's own rho and sigma against the reference's union: the pattern exactly, the values to the bound below;
+    one_sided / two_sided: whether the lists hold pairs named in one direction only / in both"""
+    n = idx.shape[0]
     # W on the stage's own rho and sigma: the reference's pattern exactly
     A = ref.weights(d, rho, sigma)
     wrp, wcol, x, y = ref.union_parts(idx, A, n)
     assert np.array_equal(rp, wrp) and np.array_equal(col, wcol)
     _, _, want = ref.fuzzy_union(idx, A, n)
     one, both = np.isnan(y) | np.isnan(x), ~np.isnan(x) & ~np.isnan(y)
-    assert one.any() and both.any()
+    assert one.any() == one_sided and both.any() == two_sided
     assert np.array_equal(want[both], (x + y - x * y)[both]) and np.array_equal(want[one], np.where(np.isnan(y), x, y)[one])
     # Bound.  A weight is exp(-t), t = (d - rho) / sigma: the quotient carries one rounding (relative eps, so |t| eps absolute in the
     # exponent, |t| eps relative in the weight) and exp at most one ulp, on either side: 2 (1 + |t|) eps relative for a weight <= 1.
@@ -76,13 +84,55 @@ def test_graph_matches_the_reference(sa, stages, case, K):
     _, _, tx, ty = ref.union_parts(idx, T, n)
     tol = 4 * EPS * (1 + np.nan_to_num(tx) + np.nan_to_num(ty))
     err = np.abs(val - want)
-    print(f"K = {K}: largest |W - reference| / bound {(err / tol).max()}")
+    print(f"{label}: largest |W - reference| / bound {(err / tol).max()}")
     assert (err <= tol).all()
     # mirrored entries carry the same bits (x + y - x y is commutative), so they fire together
     row = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp))
     key = row * n + col
     mirror = np.searchsorted(key, col.astype(np.int64) * n + row)
     assert np.array_equal(val[mirror], val)
+
+
+def _ring_lists(n, K):
+    """row i names i + 1 .. i + K mod n, with distances that ascend along a row and differ between rows"""
+    idx = _snn_ref.ring(n, K)
+    d = np.sort(np.random.default_rng(n * 1000 + K).uniform(0.5, 2.0, size=(n, K)), axis=1)
+    return idx, d
+
+
+# The edges of the CSR builder behind the union (sort by row * n + col, merge equal keys, split the keys) that random lists do not pin down.
+def test_graph_without_a_mutual_pair(sa, stages):
+    """a directed ring, n = 40, K = 3: i names j and j names i never both (that needs a + b = 0 mod 40 with a, b in 1 .. 3), so no key
+    appears twice and nothing is merged"""
+    graph, _ = stages
+    idx, d = _ring_lists(40, 3)
+    rp, col, val, rho, sigma = graph(idx, d)
+    assert col.size == 2 * 40 * 3 and np.array_equal(np.diff(rp), np.full(40, 6))
+    _check_union(idx, d, rp, col, val, rho, sigma, "ring 40 x 3", two_sided=False)
+
+
+def test_graph_with_every_pair_mutual(sa, stages):
+    """the complete graph, n = K + 1 = 9: every key appears twice"""
+    graph, _ = stages
+    n = 9
+    idx = _snn_ref.complete_lists(n)
+    d = np.sort(np.random.default_rng(9).uniform(0.5, 2.0, size=(n, n - 1)), axis=1)
+    rp, col, val, rho, sigma = graph(idx, d)
+    assert col.size == n * (n - 1) and np.array_equal(col.reshape(n, n - 1), idx)
+    _check_union(idx, d, rp, col, val, rho, sigma, "complete 9", one_sided=False)
+
+
+@pytest.mark.parametrize("n", [255, 256, 257])
+def test_graph_where_the_key_width_changes(sa, stages, n):
+    """n * n reaches 2^16 at n = 256, so the sort's end bit (the width of n * n) moves from 16 to 17; the largest key, the last row's
+    last column (n - 1, n - 2), must come out last"""
+    graph, _ = stages
+    idx, d = _ring_lists(n, 5)
+    assert (n * n).bit_length() == (16 if n == 255 else 17)
+    rp, col, val, rho, sigma = graph(idx, d)
+    assert rp[n] == col.size == 2 * n * 5 and rp[n - 1] < rp[n] and col[-1] == n - 2
+    assert col[0] == 1 and rp[0] == 0 and rp[1] == 10                # (row 0: the columns 1 .. 5 and n - 5 .. n - 1)
+    _check_union(idx, d, rp, col, val, rho, sigma, f"ring {n} x 5", two_sided=False)
 
 
 # ---- one epoch ------------------------------------------------------------------------------------------------------------------------
