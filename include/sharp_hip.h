@@ -627,6 +627,47 @@ int sharp_louvain_snn(const int *index, long long n, int K, double prune, double
                       int max_fails, double seed, int *membership, int level_cap, long long *level_n, long long *level_communities,
                       int *level_rounds, double *level_q, int *n_levels, int *level_membership);
 
+/* ---- A truncated PCA of sparse expression blocks (sharp_amd/csrc/expr_pca.hip) --------------------------------
+ * The blocks are sharp_SHARP_unlimited_csc's: colptr[b] (ncb[b] + 1 ints from 0), rowidx[b] (0-based genes, strictly ascending within
+ * a cell), val[b] (finite; a stored zero counts as a zero); a block may hold no cell.  2 <= n <= 2^31 - 2 cells in all, 1 <= m <=
+ * 16777216 genes, fewer than 2^38 stored entries.  A kernel validates range, order and values before an index is dereferenced; the
+ * message names the first offending cell (counted from 0 over all blocks).
+ * Transform: t = x; normalize_total = T > 0: t = x (T / L_c), L_c the cell's sum (a cell whose sum is 0 stays 0); log1p != 0:
+ * t = log1p(.) after that; with either, a negative value is refused.  Gene statistics: mu = (sum t) / n, var = (sum over the stored
+ * entries of (t - mu)^2 + (n - stored) mu^2) / (n - 1); a gene whose n values are all equal has mu = that value and var = 0 exactly.
+ * w = 1, or with scale 1 / sqrt(var) (0 where var = 0).  A = (T^T - 1 mu^T) diag(w), n x m, is never formed.
+ * sharp_expr_pca_csc: randomised subspace iteration with l = n_components + oversample columns (1 <= l <= 128, l <= min(n, m)),
+ * Omega[g, j] = (mix(mix(seed * 0x9E3779B97F4A7C15 + g) + j) >> 11) 2^-53 - 0.5; Y = A Omega; n_iter times Q = orth(Y), Z = orth(A^T Q),
+ * Y = A Z; then Q = orth(Y), Z = A^T Q, Z^T Z = W diag(lambda) W^T (host), s = sqrt(lambda) descending, loadings = Z W_k diag(1 / s) (m x k
+ * row-major; each component's loading of largest magnitude positive, on ties the lowest gene decides), scores = A loadings (n x k
+ * row-major: the cell-side product once more, so sharp_expr_pca_transform_csc on the fitted cells gives the same scores; the subspace's
+ * Q W_k diag(s) = Q Q^T A loadings agrees with it as far as a component has converged), sdev = s / sqrt(n - 1), center = mu, scale_out = 1 / w (1 where w = 0), gene_var, *total_var = sum w^2 var.  orth is
+ * CholeskyQR2; a pivot that is not finite, <= 0 or within l 2^-52 of the Gram's diagonal, or an eigenvalue <= 0, is refused:
+ * "numerical rank below n_components + oversample".  Bitwise reproducible: no floating-point atomic, every sum in an order that
+ * the input's shape fixes; one block and the same cells cut into several blocks give the same bits.  The data and the workspaces
+ * beyond the device's free memory are refused by name before anything is allocated.
+ * sharp_expr_stats_csc: mean, var (m each), nnz (m: the non-zero values of a gene) and cell_sum (n) after the transform.
+ * sharp_expr_pca_transform_csc: scores (n x n_components) of new cells (n >= 0) from a fit's loadings, center and scale: a cell's row
+ * depends on that cell and the fit alone.
+ * Stage entries for the tests: sharp_expr_spmm_cells (Y (n x l) = A B, B m x l row-major), sharp_expr_spmm_genes (Z (m x l) = A^T Q,
+ * Q n x l), sharp_expr_orth (Q = orth(Y), rows x l, rows >= l), sharp_expr_row_caps (the entries of a gene that one wave sums, the
+ * rows of a slab of the Gram; needs no device). */
+int sharp_expr_pca_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks, int m,
+                       int n_components, int oversample, int n_iter, double normalize_total, int log1p, int scale, long long seed,
+                       double *scores, double *loadings, double *singular_values, double *sdev, double *center, double *scale_out,
+                       double *gene_var, double *total_var);
+int sharp_expr_stats_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks, int m,
+                         double normalize_total, int log1p, double *mean, double *var, long long *nnz, double *cell_sum);
+int sharp_expr_pca_transform_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks,
+                                 int m, double normalize_total, int log1p, const double *loadings, const double *center, const double *scale,
+                                 int n_components, double *scores);
+int sharp_expr_spmm_cells(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks, int m,
+                          double normalize_total, int log1p, int scale, const double *Bm, int l, double *Y);
+int sharp_expr_spmm_genes(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks, int m,
+                          double normalize_total, int log1p, int scale, const double *Q, int l, double *Z);
+int sharp_expr_orth(const double *Y, long long rows, int l, double *Q);
+int sharp_expr_row_caps(int *chunk, int *slab_rows);
+
 /* ---- synthetic inputs (bench / tests; not part of the reference) ------------ */
 /* Counter-based generator, value = f(seed, gene, cell): bit-identical to
  * oracle_synth_value().  Fills dX (fp32, m x ncell column-major, leading dim ld). */
@@ -792,6 +833,17 @@ void sharp_C_snn_graph(int *index, double *n, int *K, double *prune, double *cap
 void sharp_C_louvain_snn(int *index, double *n, int *K, double *prune, double *resolution, double *tol, int *max_levels, int *max_rounds,
                          int *max_fails, double *seed, int *membership, int *level_cap, double *levels, int *n_levels, int *want_levels,
                          int *level_membership, int *status);
+/* sharp_expr_pca_csc / sharp_expr_stats_csc / sharp_expr_pca_transform_csc for a list of dgCMatrix blocks laid out as
+ * sharp_C_SHARP_unlimited_csc takes them (pcat / icat / xcat = the blocks' @p / @i / @x one after the other, ncb as double); seed and
+ * the genes' nnz as double */
+void sharp_C_expr_pca_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, int *n_components, int *oversample,
+                          int *n_iter, double *normalize_total, int *log1p, int *scale, double *seed, double *scores, double *loadings,
+                          double *singular_values, double *sdev, double *center, double *scale_out, double *gene_var, double *total_var,
+                          int *status);
+void sharp_C_expr_stats_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, double *normalize_total, int *log1p,
+                            double *mean, double *var, double *nnz, double *cell_sum, int *status);
+void sharp_C_expr_pca_transform_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, double *normalize_total, int *log1p,
+                                    double *loadings, double *center, double *scale, int *n_components, double *scores, int *status);
 
 #ifdef __cplusplus
 }

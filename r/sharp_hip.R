@@ -770,6 +770,51 @@ sharp_snn_graph <- function(index, prune = 1 / 15) {
     list(i = rep.int(seq_len(n), diff(r$row_ptr)), j = r$col[seq_len(nnz)] + 1L, x = r$val[seq_len(nnz)], n = n)
 }
 
+# A truncated PCA of sparse expression blocks (DESIGN.md 21): scExp a dgCMatrix or a list of them, genes x cells, as SHARP_unlimited
+# takes them (a dense block is converted).  Cells are scaled to normalize.total counts (NULL: not), log1p is taken, genes are centred
+# and, with scale, divided by their standard deviation.  Returns list(scores (cells x n.components: the input of sharp_knn, sharp_umap
+# (pca = NULL) and sharp_louvain), loadings (genes x n.components), singular.values, sdev, center, scale, gene.var, total.var).
+.sharp_csc_cat <- function(scExp, who) {
+    if (!is.list(scExp)) scExp <- list(scExp)
+    if (length(scExp) < 1) stop("No expression data is provided!")
+    cs <- lapply(scExp, function(b) .sharp_block(if (inherits(b, "sparseMatrix")) b else methods::as(methods::as(data.matrix(b), "CsparseMatrix"), "dgCMatrix")))
+    if (sum(as.numeric(vapply(cs, function(b) length(b$x), 1))) >= 2^31) stop(paste0(who, ": .C() carries at most 2^31 - 1 values"))
+    list(p = unlist(lapply(cs, `[[`, "p")), i = unlist(lapply(cs, `[[`, "i")), x = as.double(unlist(lapply(cs, `[[`, "x"))), nb = length(cs),
+         ncb = as.double(vapply(cs, function(b) b$dim[2], 1L)), m = as.integer(cs[[1]]$dim[1]))
+}
+sharp_expression_pca <- function(scExp, n.components = 50L, oversample = 10L, n.iter = 4L, normalize.total = 1e4, log1p = TRUE, scale = FALSE,
+                                 seed = 0) {
+    b <- .sharp_csc_cat(scExp, "sharp_expression_pca")
+    n <- sum(b$ncb); k <- as.integer(n.components)
+    r <- .C("sharp_C_expr_pca_csc", as.integer(b$p), as.integer(b$i), b$x, b$nb, b$ncb, b$m, k, as.integer(oversample), as.integer(n.iter),
+            as.double(if (is.null(normalize.total)) 0 else normalize.total), as.integer(log1p), as.integer(scale), as.double(seed),
+            scores = double(n * k), loadings = double(b$m * k), sv = double(k), sdev = double(k), center = double(b$m), scale = double(b$m),
+            gene_var = double(b$m), total_var = double(1), status = integer(1))
+    .sharp_check(r$status)
+    list(scores = t(matrix(r$scores, nrow = k)), loadings = t(matrix(r$loadings, nrow = k)), singular.values = r$sv, sdev = r$sdev,
+         center = r$center, scale = r$scale, gene.var = r$gene_var, total.var = r$total_var, normalize.total = normalize.total, log1p = log1p)
+}
+# the scores of new cells in a fit of sharp_expression_pca
+sharp_expression_pca_transform <- function(scExp.new, fit) {
+    b <- .sharp_csc_cat(scExp.new, "sharp_expression_pca_transform")
+    n <- sum(b$ncb); k <- ncol(fit$loadings)
+    if (nrow(fit$loadings) != b$m) stop("the new cells and the fit do not have the same genes")
+    r <- .C("sharp_C_expr_pca_transform_csc", as.integer(b$p), as.integer(b$i), b$x, b$nb, b$ncb, b$m,
+            as.double(if (is.null(fit$normalize.total)) 0 else fit$normalize.total), as.integer(fit$log1p), as.double(t(fit$loadings)),
+            as.double(fit$center), as.double(fit$scale), as.integer(k), scores = double(max(n * k, 1)), status = integer(1))
+    .sharp_check(r$status)
+    t(matrix(r$scores[seq_len(n * k)], nrow = k))
+}
+# per gene, after that transform: mean, var (n - 1 in the denominator), nnz (cells with a non-zero value); per cell cell.sum
+sharp_gene_stats <- function(scExp, normalize.total = 1e4, log1p = TRUE) {
+    b <- .sharp_csc_cat(scExp, "sharp_gene_stats")
+    r <- .C("sharp_C_expr_stats_csc", as.integer(b$p), as.integer(b$i), b$x, b$nb, b$ncb, b$m,
+            as.double(if (is.null(normalize.total)) 0 else normalize.total), as.integer(log1p), mean = double(b$m), var = double(b$m),
+            nnz = double(b$m), cell_sum = double(sum(b$ncb)), status = integer(1))
+    .sharp_check(r$status)
+    list(mean = r$mean, var = r$var, nnz = r$nnz, cell.sum = r$cell_sum)
+}
+
 # the same on any symmetric graph: a dgCMatrix-like triple (row_ptr 0-based with n + 1 values, col 0-based, val)
 sharp_louvain_graph <- function(row_ptr, col, val, resolution = 1, seed = 10, tol = 1e-7, max_levels = 20L, max_rounds = 200L,
                                 max_fails = 4L, ret_levels = FALSE) {

@@ -427,3 +427,61 @@ void sharp_C_louvain_snn(int *index, double *n, int *K, double *prune, double *r
 }
 
 }  // extern "C"
+
+namespace {
+
+/* a list of dgCMatrix blocks laid out as sharp_C_SHARP_unlimited_csc takes it, as the pointer lists of the plain entries */
+struct CscList {
+    std::vector<const int *> cp, ri;
+    std::vector<const double *> vx;
+    std::vector<long long> nc;
+    bool ok = false;
+    CscList(int *pcat, int *icat, double *xcat, int B, double *ncb, int *status) {
+        if (B < 1) { sharp::set_error("No expression data is provided!"); *status = SHARP_ERR_ARG; return; }
+        cp.resize(B); ri.resize(B); vx.resize(B); nc.resize(B);
+        long long poff = 0, eoff = 0;
+        for (int b = 0; b < B; ++b) {
+            nc[b] = as_ll(ncb + b);
+            if (nc[b] < 0) { sharp::set_error("a block with a negative number of cells"); *status = SHARP_ERR_ARG; return; }
+            cp[b] = pcat + poff; ri[b] = icat + eoff; vx[b] = xcat + eoff;
+            eoff += static_cast<long long>(cp[b][nc[b]]) - cp[b][0];
+            poff += nc[b] + 1;
+        }
+        ok = true;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+/* The truncated PCA of sparse expression blocks: the plain entries' bits */
+void sharp_C_expr_pca_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, int *n_components, int *oversample,
+                          int *n_iter, double *normalize_total, int *log1p, int *scale, double *seed, double *scores, double *loadings,
+                          double *singular_values, double *sdev, double *center, double *scale_out, double *gene_var, double *total_var,
+                          int *status) {
+    const CscList L(pcat, icat, xcat, *nblocks, ncb, status);
+    if (!L.ok) return;
+    *status = sharp_expr_pca_csc(L.cp.data(), L.ri.data(), L.vx.data(), L.nc.data(), *nblocks, *m, *n_components, *oversample, *n_iter,
+                                 *normalize_total, *log1p, *scale, as_ll(seed), scores, loadings, singular_values, sdev, center, scale_out,
+                                 gene_var, total_var);
+}
+void sharp_C_expr_stats_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, double *normalize_total, int *log1p,
+                            double *mean, double *var, double *nnz, double *cell_sum, int *status) {
+    const CscList L(pcat, icat, xcat, *nblocks, ncb, status);
+    if (!L.ok) return;
+    std::vector<long long> z(*m > 0 ? static_cast<size_t>(*m) : 1, 0);
+    *status = sharp_expr_stats_csc(L.cp.data(), L.ri.data(), L.vx.data(), L.nc.data(), *nblocks, *m, *normalize_total, *log1p, mean, var,
+                                   z.data(), cell_sum);
+    if (*status == 0)
+        for (int g = 0; g < *m; ++g) nnz[g] = static_cast<double>(z[g]);
+}
+void sharp_C_expr_pca_transform_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, double *normalize_total, int *log1p,
+                                    double *loadings, double *center, double *scale, int *n_components, double *scores, int *status) {
+    const CscList L(pcat, icat, xcat, *nblocks, ncb, status);
+    if (!L.ok) return;
+    *status = sharp_expr_pca_transform_csc(L.cp.data(), L.ri.data(), L.vx.data(), L.nc.data(), *nblocks, *m, *normalize_total, *log1p,
+                                           loadings, center, scale, *n_components, scores);
+}
+
+}  // extern "C"

@@ -1,0 +1,56 @@
+// expr_pca.hpp -- a truncated PCA of sparse expression blocks: the blocks on the device as a cell-major and a gene-major
+// copy of the transformed values, the gene statistics, the two sparse x dense products, CholeskyQR2 and the fit.  The C ABI entries
+// (sharp_expr_*, include/sharp_hip.h) are thin wrappers over these.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "graph.hpp"
+
+namespace sharp {
+
+constexpr int kExprChunk = 512;                  // entries of a gene that one wave sums (the split rule of a per-destination sum pass)
+constexpr int kExprSlabRows = 4096;              // rows of a slab of the l x l Gram
+constexpr int kExprMaxL = 128;                   // n_components + oversample: two columns per lane
+constexpr long long kExprMaxN = 2147483646ll;
+constexpr int kExprMaxM = 16777216;
+constexpr long long kExprMaxNnz = 1ll << 38;
+
+// a list of CSC blocks as the C ABI hands it over: colptr[b] (ncb[b] + 1 ints), rowidx[b] (0-based genes), val[b]
+struct ExprBlocks {
+    const int *const *colptr;
+    const int *const *rowidx;
+    const double *const *val;
+    const long long *ncb;
+    int nblocks, m;
+};
+
+struct ExprData {
+    long long n = 0, nnz = 0, nch = 0;
+    int m = 0;
+    DevBuf<long long> cptr;                      // n + 1: a cell's entries
+    DevBuf<int> ridx;                            // nnz: their genes, ascending within a cell
+    DevBuf<double> t;                            // nnz: the transformed values
+    DevBuf<double> lsum;                         // n: the cells' sums before the transform
+    DevBuf<long long> gptr;                      // m + 1: a gene's entries in the gene-major copy
+    DevBuf<int> gcell;                           // nnz: their cells, ascending within a gene
+    DevBuf<double> gval;                         // nnz
+    DevBuf<long long> chptr;                     // m + 1: a gene's chunks of kExprChunk entries
+    DevBuf<int> chgene;                          // nch: the gene of a chunk
+    DevBuf<double> mu, var, sd, w;               // m each: mean, variance, the result's `scale`, the weight
+    DevBuf<long long> gnnz;                      // m: the non-zero values of a gene
+    double total_var = 0.0;
+};
+
+// validates and uploads the blocks, transforms the values; genes: also the gene-major copy, the chunks and the statistics (scale: w = 1 /
+// sd).  l_work: the columns of the dense workspaces the caller will hold, for the refusal before anything is allocated.
+void expr_load(const std::string &who, const ExprBlocks &B, double normalize_total, bool log1p, bool genes, bool scale, int l_work,
+               long long min_cells, ExprData &D);
+// Y (n x l) = A Bm, Bm m x l on the device: Y[c, :] = sum over the cell's entries of t_gc w_g Bm[g, :] - mu^T diag(w) Bm
+void expr_spmm_cells(const ExprData &D, const double *mu, const double *w, const double *Bm, int l, double *Y);
+// Z (m x l) = A^T Q, Q n x l on the device
+void expr_spmm_genes(const ExprData &D, const double *Q, int l, double *Z);
+// Y (rows x l, device) -> Q with orthonormal columns, in place (CholeskyQR2)
+void expr_orth(const std::string &who, double *Y, long long rows, int l);
+
+}  // namespace sharp

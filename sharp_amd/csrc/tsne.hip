@@ -1182,6 +1182,13 @@ int perplexity_K(double perplexity) {
 
 }  // namespace
 
+void symmetric_eigen(int d, std::vector<double> &V, std::vector<double> &w) {
+    std::vector<double> e(d);
+    w.assign(d, 0.0);
+    tred2(d, V, w, e);
+    tql2(d, V, w, e);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 void tsne_prepare(const double *X, long long n, int d, long long ld, bool pca, int initial_dims, bool pca_center, bool pca_scale, bool normalize,
                   DevBuf<double> &out, int *d_out) {

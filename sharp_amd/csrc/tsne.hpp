@@ -30,5 +30,8 @@ void tsne_upload_neighbours(const int *index, const double *distance, long long 
 // dY = sum_j P_ij q_ij (y_i - y_j) - (1/Z) sum_j q_ij^2 (y_i - y_j) at Y (device, n x dims); theta > 0: the repulsion and Z by
 // Barnes-Hut at that theta; Z (host, may be null) receives Z
 void tsne_gradient(const TsneP &P, const double *dY_in, int dims, double *dGrad, double theta = 0.0, double *Z = nullptr);
+// the host eigensolver behind tsne_prepare's PCA (Householder + implicit QL), for a caller with a small symmetric matrix of its own:
+// V (d x d, row-major) holds the matrix on entry and the eigenvectors as columns on exit, w their eigenvalues (the caller orders them)
+void symmetric_eigen(int d, std::vector<double> &V, std::vector<double> &w);
 
 }  // namespace sharp
