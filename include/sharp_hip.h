@@ -681,6 +681,27 @@ int sharp_synth_labels(unsigned seed, long long cell0, int ncell, int G, int *la
  * triangle computed and mirrored); fast: the 128 x 128-tile kernel on zero-padded copies, else the generic 64 x 64 kernel. */
 int sharp_gemm_tn_f64(const double *At, const double *Bt, double *C, int M, int N, int K, int epilogue, int symmetric, int fast);
 
+/* Test entries for a whole BATCH of the kernels above and of the row preparation in front of them (tests/test_linalg_gpu.py): one
+ * descriptor array, one gemm_tn_f64_batched / row_prep_batched call, operands padded as the production callers pad them.  Every output
+ * buffer is filled with the NaN of bit pattern 0x7ff8c0de5eed0001 (the sentinel) before the call and comes back whole, so
+ * the caller sees what was written and what was not.
+ *
+ * sharp_gemm_tn_f64_batch: task t is C_t (M[t] x N[t]) = At_t^T Bt_t with At_t (K[t] x M[t]) and Bt_t (K[t] x N[t]) row-major, the
+ * tasks' operands one after the other in At / Bt (symmetric: Bt is not read, N must equal M).  epilogue, symmetric, fast and nn_square
+ * hold for every task.  fast: the operands' K rows are padded to a multiple of 16 and their leading dimensions to a multiple of 128,
+ * with zeros.  ldc_t = N[t] rounded up to 128 with ldc_pad, else N[t].  C receives the tasks' M[t] x ldc_t buffers one after the other;
+ * with want_nn (needs fast, symmetric and ldc_pad) nn receives their (ldc_t / 128) x ldc_t row minima (GemmTask::nn), else it may be
+ * null.  polite: the call is made as for a block prepared under another block's tail (sliced launches, SHARP_GEMM_SLICE).
+ *
+ * sharp_row_prep_batch: task t prepares the n[t] x p[t] matrix (leading dimension lds[t]) that follows its predecessors' n x lds values
+ * in src, in mode[t] (0 feature rows, 1 symmetric similarity, 2 symmetric distance; 1 and 2 need n == p), with nld = n rounded up to 128
+ * and p_pad = p rounded up to 16.  all_feature_rows as row_prep_batched takes it (every task mode 0 with p <= 512).  Each of Cr, Ct, nrm
+ * and D receives every task's buffer (n x p, p_pad x nld, n, nld x nld), one after the other in task order, whatever the task's mode. */
+int sharp_gemm_tn_f64_batch(int count, const int *M, const int *N, const int *K, const double *At, const double *Bt, int epilogue,
+                            int symmetric, int fast, int nn_square, int want_nn, int polite, int ldc_pad, double *C, double *nn);
+int sharp_row_prep_batch(int count, const int *n, const int *p, const long long *lds, const int *mode, const double *src,
+                         int all_feature_rows, double *Cr, double *Ct, double *nrm, double *D);
+
 /* ---- device memory helpers for non-torch hosts (R glue, tests) -------------- */
 int sharp_dev_alloc(long long bytes, void **dptr);
 int sharp_dev_free(void *dptr);

@@ -6,6 +6,8 @@
 #include "graph.hpp"
 
 #include <algorithm>
+#include <cstring>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -559,6 +561,142 @@ int sharp_gemm_tn_f64(const double *At, const double *Bt, double *C, int M, int 
     dt.upload(&t, 1);
     gemm_tn_f64_batched(dt.p, 1, M, N, "test_gemm", fast != 0, symmetric != 0);
     dC.download(C, static_cast<size_t>(M) * N);
+    SHARP_API_END
+}
+
+}  // extern "C"
+
+namespace {
+
+// what the batch test entries fill their outputs with before the kernels run: a quiet NaN no arithmetic produces
+constexpr unsigned long long kTestSentinelBits = 0x7ff8c0de5eed0001ull;
+
+// a device buffer of `count` sentinels
+void alloc_sentinel(DevBuf<double> &d, size_t count) {
+    double s;
+    static_assert(sizeof s == sizeof kTestSentinelBits, "double is 64 bits");
+    memcpy(&s, &kTestSentinelBits, sizeof s);
+    const std::vector<double> h(count, s);
+    d.alloc(count);
+    if (count) d.upload(h.data(), count);
+    stream_sync();                                       // (h goes away)
+}
+
+inline long long rup_ll(long long v, long long m) { return (v + m - 1) / m * m; }
+
+}  // namespace
+
+extern "C" {
+
+/* Test entry: a batch of GEMM tasks through ONE gemm_tn_f64_batched call (include/sharp_hip.h). */
+int sharp_gemm_tn_f64_batch(int count, const int *M, const int *N, const int *K, const double *At, const double *Bt, int epilogue,
+                            int symmetric, int fast, int nn_square, int want_nn, int polite, int ldc_pad, double *C, double *nn) {
+    SHARP_API_BEGIN
+    ctx();
+    const std::string w = "sharp_gemm_tn_f64_batch";
+    SHARP_REQUIRE(count >= 1, w + ": count must be at least 1");
+    SHARP_REQUIRE(M && N && K && At && C, w + ": null M, N, K, At or C");
+    SHARP_REQUIRE(symmetric || Bt, w + ": null Bt for a product that is not symmetric");
+    SHARP_REQUIRE(epilogue >= 0 && epilogue <= 2, w + ": epilogue must be 0, 1 or 2");
+    SHARP_REQUIRE(!want_nn || (fast && symmetric && ldc_pad), w + ": want_nn needs fast, symmetric and ldc_pad");
+    SHARP_REQUIRE(!want_nn || nn, w + ": null nn with want_nn");
+    SHARP_REQUIRE(!nn_square || want_nn, w + ": nn_square without want_nn");
+    SHARP_REQUIRE(!polite || fast, w + ": polite applies to the fast kernel only");
+    // offsets of every task in the host operands, the padded device operands, C and nn
+    std::vector<size_t> oA(count + 1, 0), oB(count + 1, 0), dA(count + 1, 0), dB(count + 1, 0), oC(count + 1, 0), oNN(count + 1, 0);
+    int max_M = 0, max_N = 0;
+    for (int t = 0; t < count; ++t) {
+        SHARP_REQUIRE(M[t] >= 1 && N[t] >= 1 && K[t] >= 1, w + ": M, N and K of every task must be at least 1");
+        SHARP_REQUIRE(!symmetric || M[t] == N[t], w + ": symmetric needs M == N in every task");
+        const size_t lda = fast ? rup_ll(M[t], 128) : M[t], ldb = fast ? rup_ll(N[t], 128) : N[t], Kp = fast ? rup_ll(K[t], 16) : K[t];
+        const size_t ldc = ldc_pad ? rup_ll(N[t], 128) : N[t];
+        oA[t + 1] = oA[t] + static_cast<size_t>(K[t]) * M[t];
+        oB[t + 1] = oB[t] + static_cast<size_t>(K[t]) * N[t];
+        dA[t + 1] = dA[t] + Kp * lda;
+        dB[t + 1] = dB[t] + (symmetric ? 0 : Kp * ldb);
+        oC[t + 1] = oC[t] + static_cast<size_t>(M[t]) * ldc;
+        oNN[t + 1] = oNN[t] + (want_nn ? ldc / 128 * ldc : 0);
+        max_M = std::max(max_M, M[t]); max_N = std::max(max_N, N[t]);
+    }
+    SHARP_REQUIRE(dA[count] + dB[count] + oC[count] + oNN[count] <= (size_t(1) << 31), w + ": more than 16 GB of operands and results");
+    std::vector<double> ha(dA[count], 0.0), hb(dB[count], 0.0);
+    for (int t = 0; t < count; ++t) {
+        const size_t lda = fast ? rup_ll(M[t], 128) : M[t], ldb = fast ? rup_ll(N[t], 128) : N[t];
+        for (int k = 0; k < K[t]; ++k) {
+            std::copy_n(At + oA[t] + static_cast<size_t>(k) * M[t], M[t], ha.data() + dA[t] + k * lda);
+            if (!symmetric) std::copy_n(Bt + oB[t] + static_cast<size_t>(k) * N[t], N[t], hb.data() + dB[t] + k * ldb);
+        }
+    }
+    DevBuf<double> bufA(ha.size()), bufB(hb.size()), bufC, bufNN;
+    bufA.upload(ha.data(), ha.size());
+    if (!hb.empty()) bufB.upload(hb.data(), hb.size());
+    alloc_sentinel(bufC, oC[count]);
+    alloc_sentinel(bufNN, oNN[count]);
+    std::vector<GemmTask> tasks(count);
+    for (int t = 0; t < count; ++t) {
+        const long long lda = fast ? rup_ll(M[t], 128) : M[t], ldb = fast ? rup_ll(N[t], 128) : N[t];
+        const long long ldc = ldc_pad ? rup_ll(N[t], 128) : N[t];
+        const double *a = bufA.p + dA[t];
+        tasks[t] = GemmTask{a, symmetric ? a : bufB.p + dB[t], bufC.p + oC[t], M[t], N[t], K[t], lda, symmetric ? lda : ldb, ldc,
+                            epilogue, symmetric, fast, want_nn ? bufNN.p + oNN[t] : nullptr, nn_square};
+    }
+    DevBuf<GemmTask> dt(count);
+    dt.upload(tasks.data(), count);
+    {
+        struct Polite {
+            const bool on;
+            explicit Polite(bool o) : on(o) { if (on) ctx().polite = true; }
+            ~Polite() { if (on) ctx_unchecked().polite = false; }
+        } scope(polite != 0);
+        gemm_tn_f64_batched(dt.p, count, max_M, max_N, "test_gemm_batch", fast != 0, symmetric != 0);
+    }
+    bufC.download(C, oC[count]);
+    if (want_nn) bufNN.download(nn, oNN[count]);
+    stream_sync();
+    SHARP_API_END
+}
+
+/* Test entry: a batch of row-preparation tasks through ONE row_prep_batched call (include/sharp_hip.h). */
+int sharp_row_prep_batch(int count, const int *n, const int *p, const long long *lds, const int *mode, const double *src,
+                         int all_feature_rows, double *Cr, double *Ct, double *nrm, double *D) {
+    SHARP_API_BEGIN
+    ctx();
+    const std::string w = "sharp_row_prep_batch";
+    SHARP_REQUIRE(count >= 1, w + ": count must be at least 1");
+    SHARP_REQUIRE(n && p && lds && mode && src && Cr && Ct && nrm && D, w + ": null argument");
+    std::vector<size_t> oS(count + 1, 0), oCr(count + 1, 0), oCt(count + 1, 0), oN(count + 1, 0), oD(count + 1, 0);
+    int max_n = 0, max_p = 0;
+    for (int t = 0; t < count; ++t) {
+        SHARP_REQUIRE(n[t] >= 1 && p[t] >= 1 && lds[t] >= p[t], w + ": every task needs n >= 1, p >= 1 and lds >= p");
+        SHARP_REQUIRE(mode[t] >= 0 && mode[t] <= 2, w + ": mode must be 0, 1 or 2");
+        SHARP_REQUIRE(mode[t] == 0 || n[t] == p[t], w + ": modes 1 and 2 take a square matrix (n == p)");
+        SHARP_REQUIRE(!all_feature_rows || (mode[t] == 0 && p[t] <= 64 * RP_MAXV), w + ": all_feature_rows needs mode 0 and p <= 512 in every task");
+        const size_t nld = rup_ll(n[t], 128), p_pad = rup_ll(p[t], 16);
+        oS[t + 1] = oS[t] + static_cast<size_t>(n[t]) * lds[t];
+        oCr[t + 1] = oCr[t] + static_cast<size_t>(n[t]) * p[t];
+        oCt[t + 1] = oCt[t] + p_pad * nld;
+        oN[t + 1] = oN[t] + n[t];
+        oD[t + 1] = oD[t] + nld * nld;
+        max_n = std::max(max_n, n[t]); max_p = std::max(max_p, p[t]);
+    }
+    SHARP_REQUIRE(oS[count] + oCr[count] + oCt[count] + oD[count] <= (size_t(1) << 31), w + ": more than 16 GB of inputs and results");
+    DevBuf<double> dS(oS[count]), dCr, dCt, dN, dD;
+    dS.upload(src, oS[count]);
+    alloc_sentinel(dCr, oCr[count]);
+    alloc_sentinel(dCt, oCt[count]);
+    alloc_sentinel(dN, oN[count]);
+    alloc_sentinel(dD, oD[count]);
+    std::vector<RowPrepTask> tasks(count);
+    for (int t = 0; t < count; ++t)
+        tasks[t] = RowPrepTask{dS.p + oS[t], lds[t], n[t], p[t], static_cast<int>(rup_ll(n[t], 128)), static_cast<int>(rup_ll(p[t], 16)), mode[t],
+                               dCr.p + oCr[t], dCt.p + oCt[t], dN.p + oN[t], dD.p + oD[t]};
+    DevBuf<RowPrepTask> dt(count);
+    dt.upload(tasks.data(), count);
+    row_prep_batched(dt.p, count, max_n, max_p, all_feature_rows != 0);
+    dCr.download(Cr, oCr[count]);
+    dCt.download(Ct, oCt[count]);
+    dN.download(nrm, oN[count]);
+    dD.download(D, oD[count]);
     SHARP_API_END
 }
 

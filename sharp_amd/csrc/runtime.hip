@@ -340,6 +340,7 @@ static Knobs read_knobs() {
     v.ml_min_levels = num("SHARP_ML_MIN_LEVELS", 0);
     v.proj_host = num("SHARP_PROJ_HOST", 0) == 1;
     v.rp_pc_wgs = std::max(1, num("SHARP_RP_PC_WGS", 2));
+    v.gemm_slice = num("SHARP_GEMM_SLICE", 8);   // (tests/test_linalg_gpu.py: a slice small enough that a small batch needs several launches)
 #ifdef SHARP_LAB
     // lab builds (make LAB=1) only: alternative kernels and schedule experiments that were measured and not adopted (LAB_NOTES.md)
     if (const char *kv = env("SHARP_RP_KERNEL")) { if (!strcmp(kv, "sparse")) v.rp_kernel = 3; else if (!strcmp(kv, "split")) v.rp_kernel = 5; }
@@ -363,7 +364,6 @@ static Knobs read_knobs() {
     v.free_later = num("SHARP_FREE_LATER", 1) != 0;
     v.front_overlap = num("SHARP_FRONT_OVERLAP", 0);
     v.tail_priority = num("SHARP_TAIL_PRIORITY", 1) != 0;
-    v.gemm_slice = num("SHARP_GEMM_SLICE", 8);
 #endif
     if (const char *dl = env("SHARP_DEVICES")) {
         for (const char *q = dl; *q;) {
