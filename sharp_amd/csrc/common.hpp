@@ -270,6 +270,19 @@ void umap_models_drop_slot(int slot);
 
 inline void stream_sync() { SHARP_HIP_CHECK(hipStreamSynchronize(ctx().stream)); }
 
+// host functions that cross translation units stay out of the library's dynamic symbol table
+#define SHARP_LOCAL __attribute__((visibility("hidden")))
+
+// n rows of d values (row i at X + i * ld, host) packed on the device (n x d), on the library's stream
+SHARP_LOCAL inline void upload_rows(const double *X, long long n, int d, long long ld, DevBuf<double> &dst) {
+    dst.alloc(static_cast<size_t>(n) * d);
+    if (ld == d) {
+        dst.upload(X, static_cast<size_t>(n) * d);
+    } else {
+        SHARP_HIP_CHECK(hipMemcpy2DAsync(dst.p, d * sizeof(double), X, ld * sizeof(double), d * sizeof(double), n, hipMemcpyHostToDevice, ctx().stream));
+    }
+}
+
 // fn(0) .. fn(n-1) on the calling thread plus up to max_threads - 1 workers of a persistent pool (items handed out dynamically).
 // For the short host loops between kernels (per-fold relabelling and votes): starting std::threads anew cost more than the loops.
 // fn must not call HIP and must not throw.

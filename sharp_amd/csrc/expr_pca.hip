@@ -17,7 +17,7 @@
 #include "expr_pca.hpp"
 #include "graph_prim.hpp"
 #include "linalg.hpp"
-#include "tsne.hpp"
+#include "prepare.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -712,7 +712,7 @@ void expr_fit(const std::string &who, ExprData &D, int k, int oversample, int n_
     if (l == 1) lam.assign(1, G[0]), G[0] = 1.0;
     else {
         HostTimer ht("expr_eigen");
-        symmetric_eigen(l, G, lam);                          // (eigenvectors in G's columns)
+        symmetric_eigen("Rtsne", l, G, lam);   // (eigenvectors in G's columns; a refusal keeps the name it has always had)
     }
     std::vector<int> ord(l);
     for (int i = 0; i < l; ++i) ord[i] = i;

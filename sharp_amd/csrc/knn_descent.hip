@@ -6,11 +6,11 @@
 // -ffp-contract=off).  The lists are therefore a pure function of (X, K, the parameters, seed), whatever the launch split, the tile
 // filling or the lossy duplicate filter of the join do.
 //
-// This file writes its own copies of lex_less (tsne.hip) and the rank step of knn_merge_kernel, as umap_transform.hip did;
-// mix64, iota and the sorts are graph.hpp's.
+// lex_less, wave_sync and the rank step are knn_dev.hpp's; mix64, iota and the sorts are graph.hpp's.
 #include "knn_descent.hpp"
 #include "graph_prim.hpp"
-#include "tsne.hpp"
+#include "knn.hpp"
+#include "knn_dev.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -21,7 +21,6 @@
 namespace sharp {
 namespace {
 
-constexpr double KD_INF = 1.0e300;
 constexpr int KD_PC = 16;              // columns per panel of the gathered tile
 constexpr int KD_TS = KD_PC + 1;       // doubles per tile row (odd: lane l reads row l without bank conflicts inside a half wave)
 constexpr int KD_Q = 128;              // the join's candidate queue: below 64 waiting + at most 64 new
@@ -29,13 +28,6 @@ constexpr int KD_HASH = 512;           // slots of the join's per-row "already o
 constexpr int KD_MAXT = 32;            // projections
 constexpr double KD_XMAX = 1.0e100;    // |x| above this is refused: squared distances and projections stay finite below it
 constexpr unsigned long long KD_GOLD = 0x9E3779B97F4A7C15ull;
-
-__device__ __forceinline__ bool lex_less(double a, int ia, double b, int ib) { return a < b || (a == b && ia < ib); }
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // One wave's share of the workgroup's LDS: the row's list, the gathered tile, the row's own panel, the candidate queue and (join only)
 // the filter.  Bounded by K and the tile, never by d.
@@ -88,8 +80,10 @@ __device__ __forceinline__ double tile_dist(const double *__restrict__ X, int d,
     return s;
 }
 
-// knn_offer (tsne.hip) with the membership test a set needs: a candidate whose index the list already holds is dropped.  A pair's
+// knn_offer (knn_dev.hpp) with the membership test a set needs: a candidate whose index the list already holds is dropped.  A pair's
 // distance is a function of the pair, so a member would come with the bits it is stored with.
+// It keeps its own argmax tail: built on a tail shared with knn_offer, the join and offer kernels compiled to another instruction
+// stream (profiles/knn_home_kernels.txt).
 __device__ __forceinline__ void knn_offer_set(double v, int ci, bool valid, double *Ld, int *Li, int K, int lane, double &thr, int &widx,
                                               int &wpos) {
     unsigned long long m = __ballot(valid && lex_less(v, ci, thr, widx));
@@ -123,14 +117,12 @@ __device__ __forceinline__ void knn_offer_set(double v, int ci, bool valid, doub
     }
 }
 
-// the row's list, ranked by (distance, index), to out_idx / out_dist (knn_merge_kernel's rank step)
+// the row's list, ranked by (distance, index), to out_idx / out_dist
 __device__ __forceinline__ void write_ranked(const double *Ld, const int *Li, int K, long long i, int lane, int *__restrict__ out_idx,
                                              double *__restrict__ out_dist) {
     for (int p = lane; p < K; p += 64) {
         const double dp = Ld[p];
-        const int ip = Li[p];
-        int rank = 0;
-        for (int q = 0; q < K; ++q) rank += lex_less(Ld[q], Li[q], dp, ip) ? 1 : 0;
+        const int ip = Li[p], rank = knn_rank(Ld, Li, K, dp, ip);
         out_idx[i * K + rank] = ip;
         out_dist[i * K + rank] = dp;
     }
@@ -181,9 +173,9 @@ __global__ __launch_bounds__(256) void kd_offer_kernel(const double *__restrict_
     const long long r = static_cast<long long>(blockIdx.x) * 4 + wave, i = row0 + r;
     if (r >= rows || i >= n) return;   // (waves are independent: no workgroup barrier below)
     const WaveLds w = wave_lds(kd_smem, K, false, wave);
-    for (int p = lane; p < K; p += 64) { w.Ld[p] = KD_INF; w.Li[p] = INT_MAX; }
+    for (int p = lane; p < K; p += 64) { w.Ld[p] = KNN_INF; w.Li[p] = INT_MAX; }
     wave_sync();
-    double thr = KD_INF;
+    double thr = KNN_INF;
     int widx = INT_MAX, wpos = 0;
     if (WINDOWS) {
         for (int t = 0; t < T; ++t) {
@@ -486,13 +478,6 @@ unsigned long long check_seed(double seed, const char *who) {
     return static_cast<unsigned long long>(seed);
 }
 
-void upload(const double *X, long long n, int d, long long ld, DevBuf<double> &dst) {
-    dst.alloc(static_cast<size_t>(n) * d);
-    if (ld == d)
-        dst.upload(X, static_cast<size_t>(n) * d);
-    else
-        SHARP_HIP_CHECK(hipMemcpy2DAsync(dst.p, d * sizeof(double), X, ld * sizeof(double), d * sizeof(double), n, hipMemcpyHostToDevice, ctx().stream));
-}
 }  // namespace
 }  // namespace sharp
 
@@ -513,7 +498,7 @@ int sharp_knn_descent(const double *X, long long n, int d, long long ld, int K, 
     SHARP_REQUIRE(std::isfinite(delta) && delta >= 0.0 && delta <= 1.0, std::string(who) + ": delta must be in [0, 1]");
     const unsigned long long s = check_seed(seed, who);
     DevBuf<double> dX;
-    upload(X, n, d, ld, dX);
+    upload_rows(X, n, d, ld, dX);
     DevBuf<int> di;
     DevBuf<double> dd;
     KnnDescentInfo inf;
@@ -535,7 +520,7 @@ int sharp_knn_descent_start(const double *X, long long n, int d, long long ld, i
     SHARP_REQUIRE(max_rows_per_launch >= 0, std::string(who) + ": max_rows_per_launch must be >= 0");
     const unsigned long long s = check_seed(seed, who);
     DevBuf<double> dX;
-    upload(X, n, d, ld, dX);
+    upload_rows(X, n, d, ld, dX);
     DevBuf<int> di;
     DevBuf<double> dd;
     knn_descent_start(dX.p, n, d, K, n_projections, s, max_rows_per_launch, di, dd);
@@ -556,12 +541,12 @@ int sharp_knn_descent_join(const double *X, long long n, int d, long long ld, in
     SHARP_REQUIRE(max_rows_per_launch >= 0, std::string(who) + ": max_rows_per_launch must be >= 0");
     const unsigned long long s = check_seed(seed, who);
     DevBuf<double> dX;
-    upload(X, n, d, ld, dX);
+    upload_rows(X, n, d, ld, dX);
     // the caller's lists, validated on the device before an index is dereferenced (range, self, an index twice in a row)
     std::vector<double> zeros(static_cast<size_t>(n) * K, 0.0);
     DevBuf<int> given;
     DevBuf<double> unused;
-    tsne_upload_neighbours(index, zeros.data(), n, K, true, given, unused);
+    upload_neighbours(who, index, zeros.data(), n, K, true, given, unused);
     DevBuf<int> di;
     DevBuf<double> dd;
     knn_descent_lists(dX.p, n, d, K, given.p, max_rows_per_launch, di, dd);

@@ -28,7 +28,7 @@
 #include <vector>
 
 #include "snn.hpp"
-#include "tsne.hpp"
+#include "knn.hpp"
 #include "umap.hpp"
 
 namespace sharp {
@@ -829,14 +829,7 @@ int sharp_louvain_neighbors(const int *index, const double *distance, long long 
     SHARP_REQUIRE(level_cap >= max_levels, w + ": level_cap must be at least max_levels");
     DevBuf<int> idx;
     DevBuf<double> dist;
-    try {
-        tsne_upload_neighbours(index, distance, n, K, true, idx, dist);
-    } catch (const sharp::Error &e) {
-        std::string m = e.what();
-        for (const char *pre : {"Rtsne_neighbors:", "Rtsne:", "tsne_knn:"})
-            if (m.rfind(pre, 0) == 0) { m = w + ":" + m.substr(std::string(pre).size()); break; }
-        throw sharp::Error(e.code, m);
-    }
+    upload_neighbours(w.c_str(), index, distance, n, K, true, idx, dist);
     if (squared) umap_sqrt_lists(dist, n, K);
     Graph G;
     umap_graph(idx, dist, n, K, G);

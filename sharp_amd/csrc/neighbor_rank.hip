@@ -3,7 +3,7 @@
 // d2 the direct sum of (x_ic - x_lc)^2 in column order (DistEuclid::acc of dist_pairs.hpp without the root, knn_merge_kernel's re-rank:
 // bitwise the squared distance sharp_tsne_knn returns), ties to the lower index.  Matrix-free: no n x n array.
 //   nr_threshold_kernel   one wave per row: validates the row's K indices before one is dereferenced (range, self, twice: the word of
-//                         nn_check_kernel in tsne.hip), computes its K thresholds (d2(i, j), j), sorts them ascending and keeps the
+//                         nn_check_kernel in knn.hip), computes its K thresholds (d2(i, j), j), sorts them ascending and keeps the
 //                         permutation back to the caller's order
 //   nr_tile_kernel        sil_tile_kernel's pair loop (64 rows per workgroup, k-major panels of DK features through LDS, a 4 x 4 block of
 //                         pairs per lane, the features in order) with a counting epilogue: a finished pair is compared with its row's
@@ -22,7 +22,8 @@
 #include <vector>
 
 #include "dist_pairs.hpp"
-#include "graph.hpp"
+#include "knn.hpp"
+#include "knn_dev.hpp"
 
 namespace sharp {
 
@@ -32,11 +33,6 @@ constexpr long long kNrMaxN = 1ll << 24;     // rows: a count fits an int with r
 constexpr int kNrMaxK = 255;
 constexpr int kNrMaxParts = 32;              // workgroups per row tile and slice when the row tiles alone leave CUs idle
 constexpr double kNrXMax = 1.0e100;          // |x| above this is refused: a squared distance stays finite below it (knn_descent.hip's KD_XMAX)
-constexpr unsigned long long NR_OK = ~0ull;
-enum NrKind { NR_RANGE = 1, NR_SELF = 2, NR_TWICE = 3 };
-
-// tsne.hip: lex_less
-__device__ __forceinline__ bool lex_less(double a, int ia, double b, int ib) { return a < b || (a == b && ia < ib); }
 
 // One wave per row i.  index: n x K as the caller gave it.  td / tj [i * K + s]: the row's thresholds in ascending (d2, j) order,
 // pos[i * K + s]: the caller's column of the threshold at sorted place s.  An invalid row writes nothing and lowers *word to
@@ -54,15 +50,14 @@ __global__ __launch_bounds__(256) void nr_threshold_kernel(const double *__restr
     for (int p = lane; p < K; p += 64) {
         const int j = index[i * K + p];
         Li[p] = j;
-        if (j < 0 || j >= n) kind = min(kind, static_cast<int>(NR_RANGE));
-        else if (j == i) kind = min(kind, static_cast<int>(NR_SELF));
+        if (j < 0 || j >= n) kind = min(kind, static_cast<int>(NN_RANGE));
+        else if (j == i) kind = min(kind, static_cast<int>(NN_SELF));
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_sync();
     for (int p = lane; p < K; p += 64) {
         const int j = Li[p];
         for (int q = 0; q < p; ++q)
-            if (Li[q] == j) { kind = min(kind, static_cast<int>(NR_TWICE)); break; }
+            if (Li[q] == j) { kind = min(kind, static_cast<int>(NN_TWICE)); break; }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) kind = min(kind, __shfl_xor(kind, off));
@@ -76,13 +71,10 @@ __global__ __launch_bounds__(256) void nr_threshold_kernel(const double *__restr
         for (int c = 0; c < d; ++c) { const double t = X[i * d + c] - X[j * d + c]; s += t * t; }
         Ld[p] = s;
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_sync();
     for (int p = lane; p < K; p += 64) {
         const double dp = Ld[p];
-        const int ip = Li[p];
-        int place = 0;
-        for (int q = 0; q < K; ++q) place += lex_less(Ld[q], Li[q], dp, ip) ? 1 : 0;   // (the indices of a row differ: a permutation)
+        const int ip = Li[p], place = knn_rank(Ld, Li, K, dp, ip);
         td[i * K + place] = dp;
         tj[i * K + place] = ip;
         pos[i * K + place] = p;
@@ -240,11 +232,9 @@ int sharp_neighbor_ranks(const double *X, long long n, int d, long long ld, int 
                                                ", column " + std::to_string(q + 1) + ")");
     const int ni = static_cast<int>(n);
     const size_t ne = static_cast<size_t>(n) * K;
-    DevBuf<double> dx(static_cast<size_t>(n) * d), dtd(ne);
+    DevBuf<double> dx, dtd(ne);
     DevBuf<int> didx(ne), dtj(ne), dpos(ne), drank(ne);
-    if (ld == d) dx.upload(X, static_cast<size_t>(n) * d);
-    else SHARP_HIP_CHECK(hipMemcpy2DAsync(dx.p, static_cast<size_t>(d) * 8, X, static_cast<size_t>(ld) * 8, static_cast<size_t>(d) * 8,
-                                          static_cast<size_t>(n), hipMemcpyHostToDevice, c.stream));
+    upload_rows(X, n, d, ld, dx);
     didx.upload(index, ne);
     DevBuf<unsigned long long> word(1);
     SHARP_HIP_CHECK(hipMemsetAsync(word.p, 0xFF, sizeof(unsigned long long), c.stream));
@@ -254,19 +244,12 @@ int sharp_neighbor_ranks(const double *X, long long n, int d, long long ld, int 
                            didx.p, dtd.p, dtj.p, dpos.p, word.p);
         launch_check("nr_threshold_kernel");
     }
-    unsigned long long hw = NR_OK;
+    unsigned long long hw = NN_OK;
     word.download(&hw, 1);
-    if (hw != NR_OK) {
-        const std::string row = " (row " + std::to_string(hw >> 3) + ", counted from 0)";
-        switch (static_cast<int>(hw & 7)) {
-            case NR_RANGE: throw Error(SHARP_ERR_ARG, w + ": a neighbour index outside [0, n)" + row);
-            case NR_SELF: throw Error(SHARP_ERR_ARG, w + ": a row names itself as a neighbour" + row);
-            default: throw Error(SHARP_ERR_ARG, w + ": the same neighbour index twice in a row" + row);
-        }
-    }
+    if (hw != NN_OK) throw_list_fault(w, hw);
     const int W = nr_slice_width(K), slices = (K + W - 1) / W;
-    // rows per launch from tsne_knn's pair budget (about 8e9 pairs at d = 50: under 0.1 s a launch), every slice being a pass of its own
-    const double budget = 8e9 / (std::max(d, 4) / 50.0 + 0.25);
+    // rows per launch from the exact k-NN's pair budget, every slice being a pass of its own
+    const double budget = knn_pair_budget(d);
     long long rows = std::min<long long>(n, std::max<long long>(DT, static_cast<long long>(budget / static_cast<double>(n) / slices) / DT * DT));
     if (max_rows_per_launch > 0) rows = std::min<long long>(rows, max_rows_per_launch);
     // the column tiles dealt to parts when the row tiles of a launch alone leave CUs idle

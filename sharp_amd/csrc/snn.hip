@@ -19,6 +19,7 @@
 // No floating-point atomic anywhere; the slot order of a table and the order of the atomics do not reach the result.
 #include "snn.hpp"
 #include "graph_prim.hpp"
+#include "knn.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -27,8 +28,6 @@
 namespace sharp {
 namespace {
 
-enum : int { SNN_RANGE = 0, SNN_SELF = 1, SNN_TWICE = 2 };
-constexpr u64 SNN_OK = ~0ull;
 constexpr int kSub = 16;                     // lanes that walk one R(m) together
 
 // One thread per list entry, before anything dereferences an index: in [0, n), not the row itself, not named earlier in the row.
@@ -41,11 +40,11 @@ __global__ __launch_bounds__(256) void snn_check_degree_kernel(const int *__rest
     const int p = static_cast<int>(e - r * K);
     const int j = idx[e];
     int kind = 8;
-    if (j < 0 || j >= n) kind = SNN_RANGE;
-    else if (j == r) kind = SNN_SELF;
+    if (j < 0 || j >= n) kind = NN_RANGE;
+    else if (j == r) kind = NN_SELF;
     else {
         for (int q = 0; q < p; ++q)
-            if (idx[r * K + q] == j) { kind = SNN_TWICE; break; }
+            if (idx[r * K + q] == j) { kind = NN_TWICE; break; }
         atomicAdd(reinterpret_cast<u64 *>(&deg[j]), 1ull);
     }
     if (kind < 8) atomicMin(word, (static_cast<u64>(r) << 3) | static_cast<u64>(kind));
@@ -260,16 +259,9 @@ void build_reverse(const std::string &who, const DevBuf<int> &idx, long long n, 
     hipLaunchKernelGGL(snn_fill_ll_kernel, dim3(grid_for(n + 1, 256)), dim3(256), 0, c.stream, deg.p, n, 1ll, 0ll);
     hipLaunchKernelGGL(snn_check_degree_kernel, dim3(grid_for(ne, 256)), dim3(256), 0, c.stream, idx.p, n, K, ne, deg.p, word.p);
     launch_check("snn_check_degree_kernel");
-    u64 w = SNN_OK;
+    u64 w = NN_OK;
     word.download(&w, 1);
-    if (w != SNN_OK) {
-        const std::string row = " (row " + std::to_string(w >> 3) + ", counted from 0)";
-        switch (static_cast<int>(w & 7)) {
-            case SNN_RANGE: throw Error(SHARP_ERR_ARG, who + ": a neighbour index outside [0, n)" + row);
-            case SNN_SELF: throw Error(SHARP_ERR_ARG, who + ": a row names itself as a neighbour" + row);
-            default: throw Error(SHARP_ERR_ARG, who + ": the same neighbour index twice in a row" + row);
-        }
-    }
+    if (w != NN_OK) throw_list_fault(who, w);
     V.rptr.alloc(n + 1);
     Scratch tmp;
     exclusive_scan(deg.p, V.rptr.p, static_cast<size_t>(n + 1), tmp);

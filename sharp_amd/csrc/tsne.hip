@@ -1,12 +1,6 @@
 // tsne.hip -- exact t-SNE for visualization_SHARP (R/visualization_SHARP.R:94 hands x1 to Rtsne): DESIGN.md §10.
-//   input preparation   column means / sd (slab partials), X^T X on the f64 MFMA as slab partials summed in a fixed order, a host
-//                       symmetric eigensolver (Householder tridiagonalisation + implicit QL), the projection X V; centring and division
-//                       by the largest |entry|
-//   exact k-NN          distances ||w_i||^2 + ||w_j||^2 - 2 w_i.w_j of the centred rows w = x - mean on v_mfma_f64_16x16x4_f64 over streamed
-//                       column tiles, a per-row top-K in LDS behind a threshold filter, the chosen K re-ranked by a direct sum (x_i - x_j)^2
-//   given distances     Rtsne(is_distance = TRUE): R's dist vector expanded to the full matrix (dist.hip), one wave per row selecting its K
-//                       smallest entries through the same LDS list; given neighbours (Rtsne_neighbors): a validation kernel, then
-//                       the caller's lists as they are
+//   before it           input preparation (prepare.hip); the exact k-NN, the selection from given distances (Rtsne(is_distance = TRUE))
+//                       and the check of given neighbours (Rtsne_neighbors): knn.hip
 //   calibration         one wave per row, fp64 bisection on beta (bhtsne's rule)
 //   symmetrisation      COO (i, j, p) + (j, i, p), radix sort by (row, col), duplicates merged, normalised by a fixed-order sum -> CSR
 //   optimiser loop      attraction over the CSR rows (fp64); exact repulsion, a workgroup owning 256 rows and streaming every y_j through
@@ -24,472 +18,16 @@
 #include <string>
 #include <vector>
 
-#include "dist_pairs.hpp"
-#include "linalg.hpp"
+#include "knn.hpp"
+#include "prepare.hpp"
 #include "rrng.hpp"
 
 namespace sharp {
 namespace {
 
-typedef double v4f64 __attribute__((ext_vector_type(4)));
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// column statistics in a fixed order (the sum of a whole vector is graph.hpp's fixed_reduce)
-// ---------------------------------------------------------------------------------------------------------------------------
-// column sums of X (n x d, row i at X + i * ld) over slabs of rows: part[s * d + c]; with mu, sums of (x - mu)^2
-__global__ __launch_bounds__(256) void colsum_kernel(const double *__restrict__ X, long long n, int d, long long ld, long long rps,
-                                                     const double *__restrict__ mu, double *__restrict__ part) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= d) return;
-    const long long r0 = static_cast<long long>(blockIdx.y) * rps, r1 = r0 + rps < n ? r0 + rps : n;
-    double a = 0.0;
-    if (mu) {
-        const double m = mu[c];
-        for (long long r = r0; r < r1; ++r) { const double t = X[r * ld + c] - m; a += t * t; }
-    } else {
-        for (long long r = r0; r < r1; ++r) a += X[r * ld + c];
-    }
-    part[static_cast<long long>(blockIdx.y) * d + c] = a;
-}
-
-__global__ void slab_sum_kernel(const double *__restrict__ part, int nslab, long long len, double div, double *__restrict__ out) {
-    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (e >= len) return;
-    double a = 0.0;
-    for (int s = 0; s < nslab; ++s) a += part[s * len + e];
-    out[e] = a / div;
-}
-
-// column means (mu == nullptr) or sums of squared deviations / div: out[0..d), device
-void column_stat(const double *X, long long n, int d, long long ld, const double *mu, double div, DevBuf<double> &part, double *out) {
-    const int nslab = static_cast<int>(std::min<long long>(256, std::max<long long>(1, n / 256)));
-    const long long rps = (n + nslab - 1) / nslab;
-    part.ensure(static_cast<size_t>(nslab) * d);
-    hipLaunchKernelGGL(colsum_kernel, dim3(grid_for(d, 256), nslab), dim3(256), 0, ctx().stream, X, n, d, ld, rps, mu, part.p);
-    hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(d, 256)), dim3(256), 0, ctx().stream, part.p, nslab, static_cast<long long>(d), div, out);
-    launch_check("colsum_kernel");
-}
-
-// out[i * d + c] = (X[i * ld + c] - mu[c]) / (sd ? sd[c] : scal)
-__global__ __launch_bounds__(256) void affine_kernel(const double *X, long long n, int d, long long ld, const double *__restrict__ mu,
-                                                     const double *__restrict__ sd, double scal, double *out) {   // (in place when out == X, ld == d)
-    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (e >= n * d) return;
-    const long long r = e / d;
-    const int c = static_cast<int>(e - r * d);
-    double v = X[r * ld + c];
-    if (mu) v = v - mu[c];
-    out[e] = v / (sd ? sd[c] : scal);
-}
-
-// out (n x k) = Xc (n x d) . V (d x k), one thread per output, sequential over d
-__global__ __launch_bounds__(256) void project_kernel(const double *__restrict__ Xc, const double *__restrict__ V, long long n, int d, int k,
-                                                      double *__restrict__ out) {
-    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (e >= n * k) return;
-    const long long r = e / k;
-    const int j = static_cast<int>(e - r * k);
-    double a = 0.0;
-    for (int c = 0; c < d; ++c) a += Xc[r * d + c] * V[static_cast<long long>(c) * k + j];
-    out[e] = a;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// host symmetric eigensolver: Householder tridiagonalisation + implicit QL (the EISPACK tred2 / tql2 pair); V (n x n, row-major) holds
-// the matrix on entry and the eigenvectors (columns) on exit, w the eigenvalues in ascending order
-// ---------------------------------------------------------------------------------------------------------------------------
-void tred2(int n, std::vector<double> &V, std::vector<double> &d, std::vector<double> &e) {
-    auto A = [&](int i, int j) -> double & { return V[static_cast<size_t>(i) * n + j]; };
-    for (int j = 0; j < n; ++j) d[j] = A(n - 1, j);
-    for (int i = n - 1; i > 0; --i) {
-        double scale = 0.0, h = 0.0;
-        for (int k = 0; k < i; ++k) scale += std::fabs(d[k]);
-        if (scale == 0.0) {
-            e[i] = d[i - 1];
-            for (int j = 0; j < i; ++j) { d[j] = A(i - 1, j); A(i, j) = 0.0; A(j, i) = 0.0; }
-        } else {
-            for (int k = 0; k < i; ++k) { d[k] /= scale; h += d[k] * d[k]; }
-            double f = d[i - 1], g = std::sqrt(h);
-            if (f > 0) g = -g;
-            e[i] = scale * g;
-            h = h - f * g;
-            d[i - 1] = f - g;
-            for (int j = 0; j < i; ++j) e[j] = 0.0;
-            for (int j = 0; j < i; ++j) {
-                f = d[j];
-                A(j, i) = f;
-                g = e[j] + A(j, j) * f;
-                for (int k = j + 1; k <= i - 1; ++k) { g += A(k, j) * d[k]; e[k] += A(k, j) * f; }
-                e[j] = g;
-            }
-            f = 0.0;
-            for (int j = 0; j < i; ++j) { e[j] /= h; f += e[j] * d[j]; }
-            const double hh = f / (h + h);
-            for (int j = 0; j < i; ++j) e[j] -= hh * d[j];
-            for (int j = 0; j < i; ++j) {
-                f = d[j];
-                g = e[j];
-                for (int k = j; k <= i - 1; ++k) A(k, j) -= (f * e[k] + g * d[k]);
-                d[j] = A(i - 1, j);
-                A(i, j) = 0.0;
-            }
-        }
-        d[i] = h;
-    }
-    for (int i = 0; i < n - 1; ++i) {
-        A(n - 1, i) = A(i, i);
-        A(i, i) = 1.0;
-        const double h = d[i + 1];
-        if (h != 0.0) {
-            for (int k = 0; k <= i; ++k) d[k] = A(k, i + 1) / h;
-            for (int j = 0; j <= i; ++j) {
-                double g = 0.0;
-                for (int k = 0; k <= i; ++k) g += A(k, i + 1) * A(k, j);
-                for (int k = 0; k <= i; ++k) A(k, j) -= g * d[k];
-            }
-        }
-        for (int k = 0; k <= i; ++k) A(k, i + 1) = 0.0;
-    }
-    for (int j = 0; j < n; ++j) { d[j] = A(n - 1, j); A(n - 1, j) = 0.0; }
-    A(n - 1, n - 1) = 1.0;
-    e[0] = 0.0;
-}
-
-void tql2(int n, std::vector<double> &V, std::vector<double> &d, std::vector<double> &e) {
-    auto A = [&](int i, int j) -> double & { return V[static_cast<size_t>(i) * n + j]; };
-    for (int i = 1; i < n; ++i) e[i - 1] = e[i];
-    e[n - 1] = 0.0;
-    double f = 0.0, tst1 = 0.0;
-    const double eps = std::ldexp(1.0, -52);
-    for (int l = 0; l < n; ++l) {
-        tst1 = std::max(tst1, std::fabs(d[l]) + std::fabs(e[l]));
-        int m = l;
-        while (m < n - 1 && !(std::fabs(e[m]) <= eps * tst1)) ++m;
-        if (m > l) {
-            int guard = 0;
-            do {
-                double g = d[l];
-                double p = (d[l + 1] - g) / (2.0 * e[l]);
-                double r = std::hypot(p, 1.0);
-                if (p < 0) r = -r;
-                d[l] = e[l] / (p + r);
-                d[l + 1] = e[l] * (p + r);
-                const double dl1 = d[l + 1];
-                double h = g - d[l];
-                for (int i = l + 2; i < n; ++i) d[i] -= h;
-                f += h;
-                p = d[m];
-                double c = 1.0, c2 = c, c3 = c, s = 0.0, s2 = 0.0;
-                const double el1 = e[l + 1];
-                for (int i = m - 1; i >= l; --i) {
-                    c3 = c2; c2 = c; s2 = s;
-                    g = c * e[i];
-                    h = c * p;
-                    r = std::hypot(p, e[i]);
-                    e[i + 1] = s * r;
-                    s = e[i] / r;
-                    c = p / r;
-                    p = c * d[i] - s * g;
-                    d[i + 1] = h + s * (c * g + s * d[i]);
-                    for (int k = 0; k < n; ++k) {
-                        h = A(k, i + 1);
-                        A(k, i + 1) = s * A(k, i) + c * h;
-                        A(k, i) = c * A(k, i) - s * h;
-                    }
-                }
-                p = -s * s2 * c3 * el1 * e[l] / dl1;
-                e[l] = s * p;
-                d[l] = c * p;
-            } while (std::fabs(e[l]) > eps * tst1 && ++guard < 60);
-            SHARP_REQUIRE(guard < 60, "Rtsne: the PCA eigensolver did not converge (non-finite input?)");
-        }
-        d[l] += f;
-        e[l] = 0.0;
-    }
-}
-
-// the k leading eigenvectors of the symmetric G (d x d) as the columns of Vk (d x k, row-major); sign: the largest |component| positive
-void leading_eigenvectors(std::vector<double> G, int d, int k, std::vector<double> &Vk) {
-    std::vector<double> w(d), e(d);
-    tred2(d, G, w, e);
-    tql2(d, G, w, e);
-    std::vector<int> ord(d);
-    for (int i = 0; i < d; ++i) ord[i] = i;
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return w[a] > w[b]; });
-    Vk.assign(static_cast<size_t>(d) * k, 0.0);
-    for (int j = 0; j < k; ++j) {
-        const int src = ord[j];
-        int arg = 0;
-        for (int i = 1; i < d; ++i)
-            if (std::fabs(G[static_cast<size_t>(i) * d + src]) > std::fabs(G[static_cast<size_t>(arg) * d + src])) arg = i;
-        const double sg = G[static_cast<size_t>(arg) * d + src] < 0 ? -1.0 : 1.0;
-        for (int i = 0; i < d; ++i) Vk[static_cast<size_t>(i) * k + j] = sg * G[static_cast<size_t>(i) * d + src];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// exact k-NN
-// ---------------------------------------------------------------------------------------------------------------------------
-constexpr int KQ = 16;       // query rows per workgroup (one MFMA row block)
-constexpr int KCT = 64;      // candidates per column tile (4 waves x 16 MFMA columns)
-constexpr int KDT = KCT + 1; // LDS row of the distance tile
-constexpr double KNN_INF = 1.0e300;
-
-__device__ __forceinline__ bool lex_less(double a, int ia, double b, int ib) { return a < b || (a == b && ia < ib); }
-
-__global__ __launch_bounds__(256) void rownorm_kernel(const double *__restrict__ X, long long n, int d, double *__restrict__ nrm) {
-    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (i >= n) return;
-    double a = 0.0;
-    for (int c = 0; c < d; ++c) { const double t = X[i * d + c]; a += t * t; }
-    nrm[i] = a;
-}
-
-// Offers a tile of 64 candidates (lane l: distance v, index ci, valid) to one row's top-K list in LDS (Ld / Li, K entries, unsorted; the
-// row's current worst (thr, widx) at wpos).  A ballot of (dist, index) < worst leaves the few that enter; each replaces the worst and the
-// new worst is found by a wave-wide argmax.  Comparisons are lexicographic on (distance, index): ties go to the lower index.
-__device__ __forceinline__ void knn_offer(double v, int ci, bool valid, double *Ld, int *Li, int K, int lane, double &thr, int &widx, int &wpos) {
-    unsigned long long m = __ballot(valid && lex_less(v, ci, thr, widx));
-    while (m) {
-        const int bsel = __ffsll(static_cast<long long>(m)) - 1;
-        m &= m - 1;
-        const double vb = __shfl(v, bsel);
-        const int ib = __shfl(ci, bsel);
-        if (!lex_less(vb, ib, thr, widx)) continue;
-        if (lane == 0) { Ld[wpos] = vb; Li[wpos] = ib; }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        double bd = -1.0;
-        int bi = -1, bp = 0;
-        for (int p = lane; p < K; p += 64) {
-            const double dv = Ld[p];
-            const int iv = Li[p];
-            if (lex_less(bd, bi, dv, iv)) { bd = dv; bi = iv; bp = p; }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double od = __shfl_xor(bd, off);
-            const int oi = __shfl_xor(bi, off), op = __shfl_xor(bp, off);
-            if (lex_less(bd, bi, od, oi)) { bd = od; bi = oi; bp = op; }
-        }
-        thr = bd;
-        widx = bi;
-        wpos = bp;   // (lane 0's copy is the one used: a position holding the worst)
-    }
-}
-
-// Workgroup (blockIdx.x, blockIdx.y): KQ query rows [q0, q0 + 16) against the candidate columns of chunk blockIdx.y, tile by tile of KCT.
-// Wave w computes the 16 x 16 block of columns c0 + 16 w .. + 16 on the f64 MFMA (C/D: row (lane >> 4) + 4 r, column lane & 15) into the
-// LDS tile; then wave w offers them to rows 4w .. 4w + 3.  The chunk's top-K of every row (GEMM distances, unsorted; sentinels
-// (KNN_INF, INT_MAX) where the chunk holds fewer than K candidates) goes to part[(chunk * rows + r) * K ..].
-__global__ __launch_bounds__(256) void knn_kernel(const double *__restrict__ X, const double *__restrict__ nrm, long long n, int d, int K,
-                                                  long long row0, long long row_end, long long cj, int *__restrict__ part_idx,
-                                                  double *__restrict__ part_dist) {
-    extern __shared__ double smem[];
-    double *dt = smem;                              // [KQ][KDT]
-    double *Ld = dt + KQ * KDT;                     // [KQ][K]
-    int *Li = reinterpret_cast<int *>(Ld + KQ * K);   // [KQ][K]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long q0 = row0 + static_cast<long long>(blockIdx.x) * KQ, rows = row_end - row0;
-    const long long cbeg = static_cast<long long>(blockIdx.y) * cj, cend = cbeg + cj < n ? cbeg + cj : n;
-    for (int e = tid; e < KQ * K; e += 256) { Ld[e] = KNN_INF; Li[e] = INT_MAX; }
-    double thr[4];
-    int widx[4], wpos[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { thr[r] = KNN_INF; widx[r] = INT_MAX; wpos[r] = 0; }
-    const long long qa = q0 + (lane & 15);
-    const bool qa_ok = qa < row_end;
-    double nq[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const long long qq = q0 + (lane >> 4) + 4 * r;
-        nq[r] = qq < row_end ? nrm[qq] : 0.0;
-    }
-    __syncthreads();
-    for (long long c0 = cbeg; c0 < cend; c0 += KCT) {
-        const long long cb = c0 + wave * 16 + (lane & 15);
-        const bool cb_ok = cb < cend;
-        v4f64 acc = {0.0, 0.0, 0.0, 0.0};
-        for (int k0 = 0; k0 < d; k0 += 4) {
-            const int k = k0 + (lane >> 4);
-            const double a = (qa_ok && k < d) ? X[qa * d + k] : 0.0;
-            const double b = (cb_ok && k < d) ? X[cb * d + k] : 0.0;
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-        }
-        const double nc = cb_ok ? nrm[cb] : 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = (lane >> 4) + 4 * r;
-            dt[row * KDT + wave * 16 + (lane & 15)] = nq[r] + nc - 2.0 * acc[r];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int row = wave * 4 + rr;
-            const long long qq = q0 + row;
-            if (qq >= row_end) continue;
-            const long long ci = c0 + lane;
-            knn_offer(dt[row * KDT + lane], static_cast<int>(ci), ci < cend && ci != qq, Ld + row * K, Li + row * K, K, lane, thr[rr], widx[rr],
-                      wpos[rr]);
-        }
-        __syncthreads();
-    }
-    for (int e = tid; e < KQ * K; e += 256) {
-        const long long r = q0 - row0 + e / K;
-        if (r < rows) {
-            part_idx[(static_cast<long long>(blockIdx.y) * rows + r) * K + e % K] = Li[e];
-            part_dist[(static_cast<long long>(blockIdx.y) * rows + r) * K + e % K] = Ld[e];
-        }
-    }
-}
-
-// One wave per row of the launch: the K best of the chunks' lists (nc x K candidates, chunk after chunk), re-ranked by the direct sum
-// (x_i - x_j)^2 and sorted by (distance, index).  A row left with a sentinel (no finite distance to enough rows) sets *bad and writes
-// nothing it would have to read X for.
-__global__ __launch_bounds__(256) void knn_merge_kernel(const double *__restrict__ X, long long n, int d, int K, long long row0, long long rows,
-                                                        int nc, const int *__restrict__ part_idx, const double *__restrict__ part_dist,
-                                                        int *__restrict__ out_idx, double *__restrict__ out_dist, int *__restrict__ bad) {
-    extern __shared__ double smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double *Ld = smem + wave * K;                                  // [4][K] doubles, then [4][K] ints
-    int *Li = reinterpret_cast<int *>(smem + 4 * K) + wave * K;
-    const long long r = static_cast<long long>(blockIdx.x) * 4 + wave, qq = row0 + r;
-    if (r >= rows || qq >= n) return;
-    for (int p = lane; p < K; p += 64) { Ld[p] = KNN_INF; Li[p] = INT_MAX; }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    double thr = KNN_INF;
-    int widx = INT_MAX, wpos = 0;
-    for (int c = 0; c < nc; ++c) {
-        const long long base = (static_cast<long long>(c) * rows + r) * K;
-        for (int t = 0; t < K; t += 64) {
-            const bool in = t + lane < K;
-            const int ci = in ? part_idx[base + t + lane] : INT_MAX;
-            const double v = in ? part_dist[base + t + lane] : KNN_INF;
-            knn_offer(v, ci, in && ci >= 0 && ci < n, Ld, Li, K, lane, thr, widx, wpos);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (int p = lane; p < K; p += 64) {
-        const int j = Li[p];
-        double s = KNN_INF;
-        if (j >= 0 && j < n) {
-            s = 0.0;
-            for (int c = 0; c < d; ++c) { const double t = X[qq * d + c] - X[static_cast<long long>(j) * d + c]; s += t * t; }
-        } else {
-            *bad = 1;   // every writer stores the same value
-        }
-        Ld[p] = s;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (int p = lane; p < K; p += 64) {
-        const double dp = Ld[p];
-        const int ip = Li[p];
-        int rank = 0;
-        for (int q = 0; q < K; ++q) rank += lex_less(Ld[q], Li[q], dp, ip) ? 1 : 0;
-        out_idx[qq * K + rank] = ip < n ? ip : -1;
-        out_dist[qq * K + rank] = dp;
-    }
-}
-
-// *bad = 1 when a row norm is not finite or so large that a squared distance could overflow (NaN / Inf / huge input)
-__global__ __launch_bounds__(256) void norm_check_kernel(const double *__restrict__ nrm, long long n, int *__restrict__ bad) {
-    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (i < n && !(nrm[i] <= 0.125 * DBL_MAX)) *bad = 1;   // (false for NaN too)
-}
-
 __global__ __launch_bounds__(256) void dup_flag_kernel(const double *__restrict__ dist, long long n, int K, int *__restrict__ flag) {
     const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
     if (i < n && dist[i * K] == 0.0) *flag = 1;   // every writer stores the same value
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// neighbours that are given, or selected from given distances (DESIGN.md §10 "Given neighbours, given distances")
-// ---------------------------------------------------------------------------------------------------------------------------
-constexpr int NN_RS = 8;     // 64-wide loads in flight per lane before their offers (hclust_agglo.hip's HC_RS idea)
-constexpr unsigned long long NN_OK = ~0ull;
-enum NnKind { NN_RANGE = 1, NN_SELF = 2, NN_TWICE = 3, NN_DIST = 4 };
-
-// One wave per row r of the full symmetric matrix D (nld x nld, as dist_expand_kernel writes it): the K smallest (D[r][c], c) over
-// c < n, c != r, lexicographic (ties to the lower index), through knn_offer on an LDS list; then ranked by (distance, index) and written
-// as idx and dist2 = d * d.  Selection is on the distances as given.  A row left with a sentinel or a square that overflows sets *bad.
-__global__ __launch_bounds__(256) void knn_rows_kernel(const double *__restrict__ D, int n, int nld, int K, int *__restrict__ out_idx,
-                                                       double *__restrict__ out_dist2, int *__restrict__ bad) {
-    extern __shared__ double smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double *Ld = smem + wave * K;                                  // [4][K] doubles, then [4][K] ints
-    int *Li = reinterpret_cast<int *>(smem + 4 * K) + wave * K;
-    const int r = blockIdx.x * 4 + wave;
-    if (r >= n) return;
-    for (int p = lane; p < K; p += 64) { Ld[p] = KNN_INF; Li[p] = INT_MAX; }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    double thr = KNN_INF;
-    int widx = INT_MAX, wpos = 0;
-    const double *row = D + static_cast<long long>(r) * nld;
-    for (int c0 = 0; c0 < n; c0 += 64 * NN_RS) {
-        double v[NN_RS];
-#pragma unroll
-        for (int u = 0; u < NN_RS; ++u) { const int c = c0 + 64 * u + lane; v[u] = c < n ? row[c] : KNN_INF; }
-#pragma unroll
-        for (int u = 0; u < NN_RS; ++u) {
-            const int c = c0 + 64 * u + lane;
-            if (c0 + 64 * u < n) knn_offer(v[u], c, c < n && c != r, Ld, Li, K, lane, thr, widx, wpos);   // (wave-uniform condition)
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (int p = lane; p < K; p += 64) {
-        const double dp = Ld[p];
-        const int ip = Li[p];
-        int rank = 0;
-        for (int q = 0; q < K; ++q) rank += lex_less(Ld[q], Li[q], dp, ip) ? 1 : 0;
-        const double d2 = dp * dp;
-        if (ip >= n || !(d2 <= DBL_MAX)) { *bad = 1; continue; }   // every writer stores the same value
-        out_idx[static_cast<long long>(r) * K + rank] = ip;
-        out_dist2[static_cast<long long>(r) * K + rank] = d2;
-    }
-}
-
-// One wave per row of a caller's neighbour lists, before anything dereferences an index: every index in [0, n), none its own row, none
-// twice in a row, every distance finite and >= 0.  *word = min over the offending rows of (row << 3 | kind): the first offending row
-// and its lowest kind, whatever the scheduling.
-__global__ __launch_bounds__(256) void nn_check_kernel(const int *__restrict__ idx, const double *__restrict__ dist, long long n, int K,
-                                                       unsigned long long *__restrict__ word) {
-    extern __shared__ int sidx[];                                  // [4][K]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int *Li = sidx + wave * K;
-    const long long r = static_cast<long long>(blockIdx.x) * 4 + wave;
-    if (r >= n) return;
-    int kind = 8;
-    for (int p = lane; p < K; p += 64) {
-        const int j = idx[r * K + p];
-        const double d = dist[r * K + p];
-        Li[p] = j;
-        if (j < 0 || j >= n) kind = min(kind, static_cast<int>(NN_RANGE));
-        else if (j == r) kind = min(kind, static_cast<int>(NN_SELF));
-        if (!(d >= 0.0 && d <= DBL_MAX)) kind = min(kind, static_cast<int>(NN_DIST));   // (false for NaN too)
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (int p = lane; p < K; p += 64) {
-        const int j = Li[p];
-        for (int q = 0; q < p; ++q)
-            if (Li[q] == j) { kind = min(kind, static_cast<int>(NN_TWICE)); break; }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) kind = min(kind, __shfl_xor(kind, off));
-    if (lane == 0 && kind < 8) atomicMin(word, (static_cast<unsigned long long>(r) << 3) | static_cast<unsigned long long>(kind));
-}
-
-__global__ __launch_bounds__(256) void square_kernel(double *__restrict__ v, long long n, int *__restrict__ bad) {
-    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (e >= n) return;
-    const double s = v[e] * v[e];
-    if (!(s <= DBL_MAX)) *bad = 1;   // every writer stores the same value
-    v[e] = s;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1165,15 +703,6 @@ void optimise(TsneP &P, Work &w, const LoopArgs &a, std::vector<double> &itercos
 }
 
 // ---- stage helpers used by the entries -----------------------------------------------------------------------------------
-void upload_rows(const double *X, long long n, int d, long long ld, DevBuf<double> &dst) {
-    dst.alloc(static_cast<size_t>(n) * d);
-    if (ld == d) {
-        dst.upload(X, static_cast<size_t>(n) * d);
-    } else {
-        SHARP_HIP_CHECK(hipMemcpy2DAsync(dst.p, d * sizeof(double), X, ld * sizeof(double), d * sizeof(double), n, hipMemcpyHostToDevice, ctx().stream));
-    }
-}
-
 int perplexity_K(double perplexity) {
     SHARP_REQUIRE(std::isfinite(perplexity) && perplexity > 0, "Rtsne: perplexity must be positive");
     SHARP_REQUIRE(perplexity <= 85.0, "Rtsne: perplexity above 85 is not supported (at most 255 neighbours per row)");
@@ -1181,156 +710,6 @@ int perplexity_K(double perplexity) {
 }
 
 }  // namespace
-
-void symmetric_eigen(int d, std::vector<double> &V, std::vector<double> &w) {
-    std::vector<double> e(d);
-    w.assign(d, 0.0);
-    tred2(d, V, w, e);
-    tql2(d, V, w, e);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-void tsne_prepare(const double *X, long long n, int d, long long ld, bool pca, int initial_dims, bool pca_center, bool pca_scale, bool normalize,
-                  DevBuf<double> &out, int *d_out) {
-    Ctx &c = ctx();
-    DevBuf<double> raw, part, stat(static_cast<size_t>(2) * d + 2);
-    upload_rows(X, n, d, ld, raw);
-    int dd = d;
-    if (pca) {
-        KernelTimer t("tsne_pca");
-        const int k = std::min(initial_dims, d);
-        SHARP_REQUIRE(k >= 1, "Rtsne: initial_dims must be >= 1");
-        const double *mu = nullptr, *sd = nullptr;
-        if (pca_center) { column_stat(raw.p, n, d, d, nullptr, static_cast<double>(n), part, stat.p); mu = stat.p; }
-        if (pca_scale) {
-            // prcomp(scale. = TRUE): the sd (n - 1) around the centre used (the column mean, or 0 without centring: the root mean square)
-            DevBuf<double> zero;
-            if (!mu) { zero.alloc(d); zero.zero(); }
-            column_stat(raw.p, n, d, d, mu ? mu : zero.p, static_cast<double>(std::max<long long>(n - 1, 1)), part, stat.p + d);
-            std::vector<double> v(d);
-            SHARP_HIP_CHECK(hipMemcpyAsync(v.data(), stat.p + d, d * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-            stream_sync();
-            for (int j = 0; j < d; ++j) {
-                SHARP_REQUIRE(v[j] > 0 && std::isfinite(v[j]), "Rtsne: cannot rescale a constant/zero column to unit variance (column " + std::to_string(j + 1) + ")");
-                v[j] = std::sqrt(v[j]);
-            }
-            SHARP_HIP_CHECK(hipMemcpyAsync(stat.p + d, v.data(), d * sizeof(double), hipMemcpyHostToDevice, c.stream));
-            stream_sync();
-            sd = stat.p + d;
-        }
-        DevBuf<double> xc(static_cast<size_t>(n) * d);
-        hipLaunchKernelGGL(affine_kernel, dim3(grid_for(n * d, 256)), dim3(256), 0, c.stream, raw.p, n, d, static_cast<long long>(d), mu, sd, 1.0, xc.p);
-        launch_check("affine_kernel");
-        raw.release();
-        // X^T X: slab partials on the f64 MFMA (linalg.hip's TN GEMM, symmetric tiles), summed in slab order
-        const size_t dd2 = static_cast<size_t>(d) * d;
-        int nslab = static_cast<int>(std::min<long long>({64, std::max<long long>(1, n / 512),
-                                                          std::max<long long>(1, static_cast<long long>((512ull << 20) / (dd2 * sizeof(double))))}));
-        const long long rps = (n + nslab - 1) / nslab;
-        nslab = static_cast<int>((n + rps - 1) / rps);
-        DevBuf<double> gpart(dd2 * nslab), gram(dd2);
-        std::vector<GemmTask> tasks(nslab);
-        for (int s = 0; s < nslab; ++s) {
-            const long long r0 = s * rps, rows = std::min(rps, n - r0);
-            GemmTask &g = tasks[s];
-            g.At = xc.p + r0 * d;
-            g.Bt = g.At;
-            g.C = gpart.p + s * dd2;
-            g.M = g.N = d;
-            g.K = static_cast<int>(rows);
-            g.lda = g.ldb = g.ldc = d;
-            g.epilogue = 0;
-            g.symmetric = 1;
-            g.fast = 0;
-        }
-        DevBuf<GemmTask> dtasks(tasks.size());
-        dtasks.upload(tasks.data(), tasks.size());
-        gemm_tn_f64_batched(dtasks.p, nslab, d, d, "tsne_pca_gram", false, true);
-        hipLaunchKernelGGL(slab_sum_kernel, dim3(grid_for(static_cast<long long>(dd2), 256)), dim3(256), 0, c.stream, gpart.p, nslab,
-                           static_cast<long long>(dd2), 1.0, gram.p);
-        launch_check("slab_sum_kernel");
-        std::vector<double> G(dd2), Vk;
-        gram.download(G.data(), dd2);
-        {
-            HostTimer ht("tsne_pca_eigen");
-            leading_eigenvectors(std::move(G), d, k, Vk);
-        }
-        DevBuf<double> dV(Vk.size());
-        dV.upload(Vk.data(), Vk.size());
-        out.alloc(static_cast<size_t>(n) * k);
-        hipLaunchKernelGGL(project_kernel, dim3(grid_for(n * k, 256)), dim3(256), 0, c.stream, xc.p, dV.p, n, d, k, out.p);
-        launch_check("project_kernel");
-        stream_sync();
-        dd = k;
-    } else {
-        out = std::move(raw);
-    }
-    if (normalize) {
-        KernelTimer t("tsne_normalize");
-        column_stat(out.p, n, dd, dd, nullptr, static_cast<double>(n), part, stat.p);
-        hipLaunchKernelGGL(affine_kernel, dim3(grid_for(n * dd, 256)), dim3(256), 0, c.stream, out.p, n, dd, static_cast<long long>(dd), stat.p,
-                           nullptr, 1.0, out.p);
-        const unsigned nb = fixed_reduce_blocks(n * dd);
-        DevBuf<double> mx(nb);
-        fixed_reduce_parts(Fold::AbsMax, out.p, n * dd, mx.p);
-        std::vector<double> hm(nb);
-        mx.download(hm.data(), nb);
-        double m = 0.0;
-        for (double v : hm) m = std::max(m, v);
-        SHARP_REQUIRE(m > 0 && std::isfinite(m), "Rtsne: the normalised input is all zero or not finite");
-        hipLaunchKernelGGL(affine_kernel, dim3(grid_for(n * dd, 256)), dim3(256), 0, c.stream, out.p, n, dd, static_cast<long long>(dd), nullptr,
-                           nullptr, m, out.p);
-        launch_check("affine_kernel");
-    }
-    *d_out = dd;
-}
-
-void tsne_knn(const double *dX, long long n, int d, int K, DevBuf<int> &idx, DevBuf<double> &dist) {
-    Ctx &c = ctx();
-    SHARP_REQUIRE(K >= 1 && K <= 255 && n - 1 >= K, "tsne_knn: need 1 <= K <= 255 and K < n");
-    KernelTimer t("tsne_knn");
-    // The candidates are selected on w = x - column mean (fp64): distances do not change under a translation, but the error of
-    // ||x_i||^2 + ||x_j||^2 - 2 x_i.x_j scales with ||x||^2, and input far from the origin (Rtsne(pca = FALSE, normalize = FALSE),
-    // sharp_tsne_knn) would otherwise lose true neighbours to it.  The merge re-ranks the chosen K on the caller's values.
-    DevBuf<double> Xc(static_cast<size_t>(n) * d), mu(d), mupart;
-    column_stat(dX, n, d, d, nullptr, static_cast<double>(n), mupart, mu.p);
-    hipLaunchKernelGGL(affine_kernel, dim3(grid_for(n * d, 256)), dim3(256), 0, c.stream, dX, n, d, static_cast<long long>(d), mu.p, nullptr, 1.0,
-                       Xc.p);
-    launch_check("affine_kernel");
-    DevBuf<double> nrm(n);
-    DevBuf<int> bad(1);
-    bad.zero();
-    hipLaunchKernelGGL(rownorm_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, Xc.p, n, d, nrm.p);
-    hipLaunchKernelGGL(norm_check_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, nrm.p, n, bad.p);
-    launch_check("norm_check_kernel");
-    int hb = 0;
-    bad.download(&hb, 1);
-    SHARP_REQUIRE(hb == 0, "Rtsne: the (prepared) input holds NA / NaN / Inf, or values so large that squared distances overflow");
-    idx.alloc(static_cast<size_t>(n) * K);
-    dist.alloc(static_cast<size_t>(n) * K);
-    // Launches of about 8e9 candidate pairs at d = 50 (measured 1e11 pairs / s at d = 50: under 0.1 s each at any n): rows per launch
-    // from that budget, and the candidate columns cut into chunks so that a launch has >= ~1024 workgroups however few its rows are.
-    const double budget = 8e9 / (std::max(d, 4) / 50.0 + 0.25);
-    const long long rows = std::min((n + KQ - 1) / KQ * KQ, std::max<long long>(KQ, static_cast<long long>(budget / static_cast<double>(n)) / KQ * KQ));
-    const long long rb = (rows + KQ - 1) / KQ;
-    const long long nc0 = std::max<long long>(1, std::min<long long>((n + KCT - 1) / KCT, (1024 + rb - 1) / rb));
-    const long long cj = ((n + nc0 - 1) / nc0 + KCT - 1) / KCT * KCT;
-    const int nc = static_cast<int>((n + cj - 1) / cj);
-    DevBuf<int> pidx(static_cast<size_t>(nc) * rows * K);
-    DevBuf<double> pdist(static_cast<size_t>(nc) * rows * K);
-    const size_t lds = sizeof(double) * KQ * KDT + (sizeof(double) + sizeof(int)) * KQ * K;
-    const size_t lds_merge = (sizeof(double) + sizeof(int)) * 4 * K;
-    for (long long r0 = 0; r0 < n; r0 += rows) {
-        const long long r1 = std::min(n, r0 + rows);
-        hipLaunchKernelGGL(knn_kernel, dim3(grid_for(r1 - r0, KQ), nc), dim3(256), lds, c.stream, Xc.p, nrm.p, n, d, K, r0, r1, cj, pidx.p, pdist.p);
-        launch_check("knn_kernel");
-        hipLaunchKernelGGL(knn_merge_kernel, dim3(grid_for(r1 - r0, 4)), dim3(256), lds_merge, c.stream, dX, n, d, K, r0, r1 - r0, nc, pidx.p,
-                           pdist.p, idx.p, dist.p, bad.p);
-        launch_check("knn_merge_kernel");
-    }
-    bad.download(&hb, 1);
-    SHARP_REQUIRE(hb == 0, "Rtsne: fewer than K rows at a finite distance from some row (non-finite input?)");
-}
 
 void tsne_affinities(const DevBuf<int> &idx, const DevBuf<double> &dist, long long n, int K, double perplexity, TsneP &P) {
     Ctx &c = ctx();
@@ -1360,73 +739,6 @@ void tsne_affinities(const DevBuf<int> &idx, const DevBuf<double> &dist, long lo
     P.val.alloc(nnz);
     merged_to_csr<double>(keys.p, P.nnz, n, false, P.row_ptr.p, P.col.p, nullptr, vals.p, total.p, P.val.p);   // (no row is empty: K entries each)
     stream_sync();
-}
-
-void tsne_knn_dist(const double *d, int n, int K, DevBuf<int> &idx, DevBuf<double> &dist2) {
-    Ctx &c = ctx();
-    SHARP_REQUIRE(K >= 1 && K <= 255 && n - 1 >= K, "tsne_knn_dist: need 1 <= K <= 255 and K < n");
-    const size_t len = static_cast<size_t>(n) * (n - 1) / 2;
-    const int nld = dist_nld(n);
-    DevBuf<double> D(static_cast<size_t>(nld) * nld);
-    {
-        DevBuf<double> cond(len);
-        {
-            KernelTimer t("tsne_dist_upload");
-            cond.upload(d, len);
-        }
-        dist_expand(cond.p, n, D.p);
-        stream_sync();   // (the vector goes out of scope)
-    }
-    idx.alloc(static_cast<size_t>(n) * K);
-    dist2.alloc(static_cast<size_t>(n) * K);
-    DevBuf<int> bad(1);
-    bad.zero();
-    {
-        KernelTimer t("tsne_knn_dist");
-        hipLaunchKernelGGL(knn_rows_kernel, dim3(grid_for(n, 4)), dim3(256), (sizeof(double) + sizeof(int)) * 4 * K, c.stream, D.p, n, nld, K, idx.p,
-                           dist2.p, bad.p);
-        launch_check("knn_rows_kernel");
-    }
-    int hb = 0;
-    bad.download(&hb, 1);
-    SHARP_REQUIRE(hb == 0, "Rtsne: the distances are so large that their squares overflow");
-}
-
-void tsne_upload_neighbours(const int *index, const double *distance, long long n, int K, bool squared, DevBuf<int> &idx,
-                            DevBuf<double> &dist2) {
-    Ctx &c = ctx();
-    const size_t ne = static_cast<size_t>(n) * K;
-    idx.alloc(ne);
-    dist2.alloc(ne);
-    idx.upload(index, ne);
-    dist2.upload(distance, ne);
-    DevBuf<unsigned long long> word(1);
-    SHARP_HIP_CHECK(hipMemsetAsync(word.p, 0xFF, sizeof(unsigned long long), c.stream));
-    {
-        KernelTimer t("tsne_nn_check");
-        hipLaunchKernelGGL(nn_check_kernel, dim3(grid_for(n, 4)), dim3(256), sizeof(int) * 4 * K, c.stream, idx.p, dist2.p, n, K, word.p);
-        launch_check("nn_check_kernel");
-    }
-    unsigned long long w = NN_OK;
-    word.download(&w, 1);
-    if (w != NN_OK) {
-        const std::string row = " (row " + std::to_string(w >> 3) + ", counted from 0)";
-        switch (static_cast<int>(w & 7)) {
-            case NN_RANGE: throw Error(SHARP_ERR_ARG, "Rtsne_neighbors: a neighbour index outside [0, n)" + row);
-            case NN_SELF: throw Error(SHARP_ERR_ARG, "Rtsne_neighbors: a row names itself as a neighbour" + row);
-            case NN_TWICE: throw Error(SHARP_ERR_ARG, "Rtsne_neighbors: the same neighbour index twice in a row" + row);
-            default: throw Error(SHARP_ERR_ARG, "Rtsne_neighbors: a distance that is NA / NaN / Inf or negative" + row);
-        }
-    }
-    if (!squared) {
-        DevBuf<int> bad(1);
-        bad.zero();
-        hipLaunchKernelGGL(square_kernel, dim3(grid_for(n * K, 256)), dim3(256), 0, c.stream, dist2.p, n * K, bad.p);
-        launch_check("square_kernel");
-        int hb = 0;
-        bad.download(&hb, 1);
-        SHARP_REQUIRE(hb == 0, "Rtsne_neighbors: the distances are so large that their squares overflow");
-    }
 }
 
 void tsne_gradient(const TsneP &P, const double *dY_in, int dims, double *dGrad, double theta, double *Z) {
@@ -1462,6 +774,16 @@ void check_X(const double *X, long long n, int d, long long ld) {
             if (!std::isfinite(X[i * ld + c]))
                 throw sharp::Error(SHARP_ERR_ARG, "Rtsne: the input holds NA / NaN / Inf (row " + std::to_string(i + 1) + ", column " +
                                                       std::to_string(c + 1) + ")");
+}
+
+// Rtsne's searches: a K out of range is refused under the stage's name, everything behind it under Rtsne's
+void tsne_knn(const double *dX, long long n, int d, int K, DevBuf<int> &idx, DevBuf<double> &dist) {
+    SHARP_REQUIRE(K >= 1 && K <= 255 && n - 1 >= K, "tsne_knn: need 1 <= K <= 255 and K < n");
+    knn_self("Rtsne", dX, n, d, K, idx, dist);
+}
+void tsne_knn_dist(const double *d, int n, int K, DevBuf<int> &idx, DevBuf<double> &dist2) {
+    SHARP_REQUIRE(K >= 1 && K <= 255 && n - 1 >= K, "tsne_knn_dist: need 1 <= K <= 255 and K < n");
+    knn_from_dist("Rtsne", d, n, K, idx, dist2);
 }
 
 void check_loop_args(int dims, int max_iter, double momentum, double final_momentum, double eta, double exaggeration, const double *Y) {
@@ -1519,7 +841,7 @@ void run_tsne(const double *X, long long n, int d, long long ld, int dims, int i
     SHARP_REQUIRE(static_cast<double>(n - 1) >= 3.0 * perplexity, "Perplexity is too large.");
     DevBuf<double> Xp;
     int dp = 0;
-    tsne_prepare(X, n, d, ld, pca != 0, initial_dims, pca_center != 0, pca_scale != 0, normalize != 0, Xp, &dp);
+    prepare_input("Rtsne", X, n, d, ld, pca != 0, initial_dims, pca_center != 0, pca_scale != 0, normalize != 0, Xp, &dp);
     DevBuf<int> idx;
     DevBuf<double> dist;
     tsne_knn(Xp.p, n, dp, K, idx, dist);
@@ -1576,7 +898,7 @@ int sharp_tsne_prepare(const double *X, long long n, int d, long long ld, int pc
     check_X(X, n, d, ld);
     SHARP_REQUIRE(out && d_out, "sharp_tsne_prepare: null output");
     DevBuf<double> Xp;
-    tsne_prepare(X, n, d, ld, pca != 0, initial_dims, pca_center != 0, pca_scale != 0, normalize != 0, Xp, d_out);
+    prepare_input("Rtsne", X, n, d, ld, pca != 0, initial_dims, pca_center != 0, pca_scale != 0, normalize != 0, Xp, d_out);
     Xp.download(out, static_cast<size_t>(n) * *d_out);
     SHARP_API_END
 }
@@ -1660,7 +982,7 @@ int sharp_tsne_neighbors(const int *index, const double *distance, long long n, 
     check_loop_args(dims, max_iter, momentum, final_momentum, eta, exaggeration, Y);
     DevBuf<int> idx;
     DevBuf<double> dist;
-    tsne_upload_neighbours(index, distance, n, K, squared != 0, idx, dist);
+    upload_neighbours("Rtsne_neighbors", index, distance, n, K, squared != 0, idx, dist);
     run_from_neighbours(idx, dist, n, K, dims, perplexity, repulsion ? theta : 0.0,
                         LoopArgs{max_iter, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta, exaggeration}, Y_init, seed, Y,
                         itercosts, costs);
@@ -1709,7 +1031,7 @@ int sharp_tsne_affinities_nn(const int *index, const double *distance, long long
     SHARP_REQUIRE(row_ptr && col && val && nnz, "sharp_tsne_affinities_nn: null output");
     DevBuf<int> di;
     DevBuf<double> dd;
-    tsne_upload_neighbours(index, distance, n, K, squared != 0, di, dd);
+    upload_neighbours("Rtsne_neighbors", index, distance, n, K, squared != 0, di, dd);
     TsneP P;
     tsne_affinities(di, dd, n, K, perplexity, P);
     *nnz = P.nnz;

@@ -19,8 +19,9 @@
 #include <string>
 #include <vector>
 
+#include "knn.hpp"
+#include "prepare.hpp"
 #include "rrng.hpp"
-#include "tsne.hpp"
 
 namespace sharp {
 namespace {
@@ -104,8 +105,6 @@ __global__ __launch_bounds__(256) void sigma_kernel(const int *__restrict__ idx,
 // ---------------------------------------------------------------------------------------------------------------------------
 // epochs
 // ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double clip4(double v) { return fmin(4.0, fmax(-4.0, v)); }
-
 // One wave per row i, lanes over the slots s = edge * T + term of the row (T = 1 + negative_sample_rate), pass after pass of 64 in
 // slot order; a slot whose edge fires adds its term to the lane's sum, the lanes' sums are folded by a butterfly, and
 // Yout_i = Yin_i + alpha * sum.  x0 = mix(seed * 0x9E3779B97F4A7C15 + ep).
@@ -326,19 +325,6 @@ using namespace sharp;
 
 namespace {
 
-// t-SNE's stages name Rtsne in their refusals; a UMAP caller is told that umap refused
-template <typename F>
-void as_umap(const char *who, F f) {
-    try {
-        f();
-    } catch (const sharp::Error &e) {
-        std::string m = e.what();
-        for (const char *pre : {"Rtsne_neighbors:", "Rtsne:", "tsne_knn:"})
-            if (m.rfind(pre, 0) == 0) { m = std::string(who) + ":" + m.substr(std::string(pre).size()); break; }
-        throw sharp::Error(e.code, m);
-    }
-}
-
 void sqrt_lists(DevBuf<double> &dist, long long n, int K) { umap_sqrt_lists(dist, n, K); }
 
 struct UmapArgs {
@@ -407,7 +393,7 @@ void run_from_lists(DevBuf<int> &idx, DevBuf<double> &dist, long long n, int K, 
             Xp->download(hx.data(), hx.size());
             DevBuf<double> pc;
             int k = 0;
-            as_umap("umap", [&] { tsne_prepare(hx.data(), n, dp, dp, true, u.dims, true, false, false, pc, &k); });
+            prepare_input("umap", hx.data(), n, dp, dp, true, u.dims, true, false, false, pc, &k);
             SHARP_REQUIRE(k == u.dims, "umap: the PCA start has the wrong number of components");
             pc.download(y0.data(), ne);
         }
@@ -457,7 +443,7 @@ void check_lists(const int *index, const double *distance, long long n, int K, c
 // the caller's lists on the device, validated as sharp_tsne_neighbors validates them, as Euclidean distances
 void upload_lists(const char *who, const int *index, const double *distance, long long n, int K, bool squared, DevBuf<int> &idx,
                   DevBuf<double> &dist) {
-    as_umap(who, [&] { tsne_upload_neighbours(index, distance, n, K, true, idx, dist); });   // (true: nothing is squared there)
+    upload_neighbours(who, index, distance, n, K, true, idx, dist);   // (true: nothing is squared there)
     if (squared) sqrt_lists(dist, n, K);
 }
 
@@ -493,10 +479,10 @@ int sharp_umap(const double *X, long long n, int d, long long ld, int n_neighbor
     const int K = n_neighbors - 1;
     DevBuf<double> Xp;
     int dp = 0;
-    as_umap("umap", [&] { tsne_prepare(X, n, d, ld, pca > 0, pca, pca_center != 0, false, false, Xp, &dp); });
+    prepare_input("umap", X, n, d, ld, pca > 0, pca, pca_center != 0, false, false, Xp, &dp);
     DevBuf<int> idx;
     DevBuf<double> dist;
-    as_umap("umap", [&] { tsne_knn(Xp.p, n, dp, K, idx, dist); });
+    knn_self("umap", Xp.p, n, dp, K, idx, dist);
     sqrt_lists(dist, n, K);
     if (nn_index) {
         idx.download(nn_index, static_cast<size_t>(n) * K);

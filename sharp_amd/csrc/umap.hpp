@@ -1,11 +1,14 @@
 // umap.hpp -- the UMAP embedding beside t-SNE: the a / b curve fitted on the host, the fuzzy graph from k-NN lists (one
 // wave per row: rho, the bisection on sigma; the union A + A^T - A o A^T as a CSR), and the epoch optimiser (stateless schedule,
-// hashed negative samples, all rows updated at once from the old positions).  Input preparation, the exact k-NN and the validation of
-// given lists are t-SNE's (tsne.hpp).  The C ABI entries (sharp_umap*, include/sharp_hip.h) are thin wrappers over these.
+// hashed negative samples, all rows updated at once from the old positions).  Input preparation is prepare.hpp's, the exact k-NN and the
+// validation of given lists are knn.hpp's.  The C ABI entries (sharp_umap*, include/sharp_hip.h) are thin wrappers over these.
 #pragma once
 #include "graph.hpp"
 
 namespace sharp {
+
+// the clip of every gradient term of the epochs, umap's and the transform's
+__device__ __forceinline__ double clip4(double v) { return fmin(4.0, fmax(-4.0, v)); }
 
 // W = A + A^T - A o A^T, CSR on the device (rows sorted by column), wmax = max W
 using UmapGraph = Graph;

@@ -2,15 +2,14 @@
 // transform and uwot's umap_transform; no bit parity with either is claimed).
 //   model      a device-resident handle: the reference rows X_ref, their column mean mu, W = X_ref - mu, ||w_j||^2, the fitted map
 //              Y_ref, a, b, n_neighbors and the fit's n_epochs
-//   lists      the K nearest reference rows of every query row: 16 query rows per workgroup against 64-candidate tiles on the f64
-//              MFMA, the query block's A fragments loaded once per workgroup (registers while ceil(d / 4) <= 16, else an LDS panel),
-//              per-chunk partial lists, a one-wave-per-row merge that re-ranks on the direct sum and writes Euclidean distances
+//   lists      the K nearest reference rows of every query row: knn.hip's cross search
 //   weights    one wave per row: sigma by §13's bisection with rho = 0, the floor on the row's own mean, w = exp(-d / sigma), and the
 //              start y = sum w Y_ref[idx] / sum w
 //   epochs     one wave per row, lanes over the slots p * T + term; Y_ref is fixed and rows are independent, so the kernel runs the
 //              epochs [ep0, ep1) itself with y in registers: one launch for the whole range
 // A row's result depends on (the row, the model, the arguments, row_offset + q) alone: not on the rows beside it, the launch split or
 // the candidate chunking.  fp64 throughout, no floating-point atomics, every sum in an order fixed by the shape.
+#include "knn.hpp"
 #include "umap.hpp"
 
 #include <algorithm>
@@ -25,220 +24,6 @@
 
 namespace sharp {
 namespace {
-
-typedef double v4f64 __attribute__((ext_vector_type(4)));
-
-constexpr int KQ = 16;        // query rows per workgroup (one MFMA row block)           (tsne.hip: KQ, KCT, KDT, KNN_INF)
-constexpr int KCT = 64;       // candidates per tile (4 waves x 16 MFMA columns)
-constexpr int KDT = KCT + 1;  // LDS row of the distance tile
-constexpr double KNN_INF = 1.0e300;
-constexpr int KREG = 16;      // k-steps of four columns whose A fragments stay in registers
-constexpr size_t LDS_MAX = 160 * 1024;   // LDS of a gfx950 compute unit
-
-// ---- copies of small device helpers, each named after its original ---------------------------------------------------------------------
-// tsne.hip: lex_less
-__device__ __forceinline__ bool lex_less(double a, int ia, double b, int ib) { return a < b || (a == b && ia < ib); }
-
-// tsne.hip: knn_offer.  Offers a tile of 64 candidates (lane l: distance v, index ci, valid) to one row's top-K list in LDS (Ld / Li,
-// unsorted; the row's current worst (thr, widx) at wpos): each candidate below the worst replaces it and the new worst is found by a
-// wave-wide argmax.  Comparisons are lexicographic on (distance, index): ties go to the lower index.
-__device__ __forceinline__ void knn_offer(double v, int ci, bool valid, double *Ld, int *Li, int K, int lane, double &thr, int &widx, int &wpos) {
-    unsigned long long m = __ballot(valid && lex_less(v, ci, thr, widx));
-    while (m) {   // (at most 64 turns: one bit leaves per turn)
-        const int bsel = __ffsll(static_cast<long long>(m)) - 1;
-        m &= m - 1;
-        const double vb = __shfl(v, bsel);
-        const int ib = __shfl(ci, bsel);
-        if (!lex_less(vb, ib, thr, widx)) continue;
-        if (lane == 0) { Ld[wpos] = vb; Li[wpos] = ib; }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        double bd = -1.0;
-        int bi = -1, bp = 0;
-        for (int p = lane; p < K; p += 64) {
-            const double dv = Ld[p];
-            const int iv = Li[p];
-            if (lex_less(bd, bi, dv, iv)) { bd = dv; bi = iv; bp = p; }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double od = __shfl_xor(bd, off);
-            const int oi = __shfl_xor(bi, off), op = __shfl_xor(bp, off);
-            if (lex_less(bd, bi, od, oi)) { bd = od; bi = oi; bp = op; }
-        }
-        thr = bd;
-        widx = bi;
-        wpos = bp;
-    }
-}
-
-// umap.hip: clip4
-__device__ __forceinline__ double clip4(double v) { return fmin(4.0, fmax(-4.0, v)); }
-
-// tsne.hip: affine_kernel with a mean only.  out = X - mu, row-major n x d
-__global__ __launch_bounds__(256) void center_rows_kernel(const double *__restrict__ X, long long n, int d, const double *__restrict__ mu,
-                                                          double *__restrict__ out) {
-    const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (e < n * d) out[e] = X[e] - mu[e % d];
-}
-
-// tsne.hip: rownorm_kernel and norm_check_kernel in one.  *bad = 1 when a norm is not finite or so large that a squared distance could
-// overflow (NaN / Inf / huge input)
-__global__ __launch_bounds__(256) void rownorm_check_kernel(const double *__restrict__ X, long long n, int d, double *__restrict__ nrm,
-                                                            int *__restrict__ bad) {
-    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (i >= n) return;
-    double a = 0.0;
-    for (int c = 0; c < d; ++c) { const double t = X[i * d + c]; a += t * t; }
-    nrm[i] = a;
-    if (!(a <= 0.125 * DBL_MAX)) *bad = 1;   // (false for NaN too; every writer stores the same value)
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// lists
-// ---------------------------------------------------------------------------------------------------------------------------
-// Workgroup (blockIdx.x, blockIdx.y): the KQ query rows [q0, q0 + 16) of Q (nq x d, centred with the model's mean) against the reference
-// rows of chunk blockIdx.y, tile by tile of KCT.  The A operand of the f64 MFMA (row lane & 15, column 4 s + (lane >> 4) in k-step s)
-// is the same for every tile: a lane keeps its ceil(d / 4) values in registers, or, beyond KREG k-steps, the workgroup keeps them in an
-// LDS panel laid out [k-step][lane], which every wave reads at consecutive addresses.  The k-steps run in order in both forms, so a
-// pair's value depends on d and the two rows alone.  Wave w computes columns c0 + 16 w .. + 16 (C/D: row (lane >> 4) + 4 r, column
-// lane & 15) into the LDS tile and then offers the tile to rows 4 w .. 4 w + 3.  The chunk's top-K of every row (GEMM values, unsorted;
-// sentinels (KNN_INF, INT_MAX) where the chunk holds fewer than K candidates) goes to part[(chunk * rows + r) * K ..].
-template <bool PANEL>
-__global__ __launch_bounds__(256) void knn_cross_kernel(const double *__restrict__ Q, const double *__restrict__ qn, const double *__restrict__ W,
-                                                        const double *__restrict__ wn, long long nref, int d, int K, long long row0,
-                                                        long long row_end, long long cj, int *__restrict__ part_idx,
-                                                        double *__restrict__ part_dist) {
-    extern __shared__ double smem[];
-    double *dt = smem;                                // [KQ][KDT]
-    double *Ld = dt + KQ * KDT;                       // [KQ][K]
-    int *Li = reinterpret_cast<int *>(Ld + KQ * K);   // [KQ][K]
-    double *panel = reinterpret_cast<double *>(Li + KQ * K);   // [ksteps][64] (PANEL only; 16 K ints keep it 8-byte aligned)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long q0 = row0 + static_cast<long long>(blockIdx.x) * KQ, rows = row_end - row0;
-    const long long cbeg = static_cast<long long>(blockIdx.y) * cj, cend = cbeg + cj < nref ? cbeg + cj : nref;
-    const int ksteps = (d + 3) >> 2, kk = lane >> 4;
-    for (int e = tid; e < KQ * K; e += 256) { Ld[e] = KNN_INF; Li[e] = INT_MAX; }
-    double thr[4];
-    int widx[4], wpos[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { thr[r] = KNN_INF; widx[r] = INT_MAX; wpos[r] = 0; }
-    double a[KREG];
-    if (PANEL) {
-        for (int e = tid; e < ksteps * 64; e += 256) {
-            const long long qr = q0 + (e & 15);
-            const int k = 4 * (e >> 6) + ((e & 63) >> 4);
-            panel[e] = (qr < row_end && k < d) ? Q[qr * d + k] : 0.0;
-        }
-    } else {
-        const long long qa = q0 + (lane & 15);
-#pragma unroll
-        for (int s = 0; s < KREG; ++s) {
-            const int k = 4 * s + kk;
-            a[s] = (qa < row_end && k < d) ? Q[qa * d + k] : 0.0;
-        }
-    }
-    double nq[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const long long qq = q0 + kk + 4 * r;
-        nq[r] = qq < row_end ? qn[qq] : 0.0;
-    }
-    __syncthreads();
-    for (long long c0 = cbeg; c0 < cend; c0 += KCT) {
-        const long long cb = c0 + wave * 16 + (lane & 15);
-        const bool cb_ok = cb < cend;
-        const double *wrow = W + (cb_ok ? cb : cbeg) * d;
-        v4f64 acc = {0.0, 0.0, 0.0, 0.0};
-        if (PANEL) {
-            for (int s = 0; s < ksteps; ++s) {
-                const int k = 4 * s + kk;
-                const double b = (cb_ok && k < d) ? wrow[k] : 0.0;
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(panel[s * 64 + lane], b, acc, 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int s = 0; s < KREG; ++s) {
-                if (s < ksteps) {   // (wave-uniform)
-                    const int k = 4 * s + kk;
-                    const double b = (cb_ok && k < d) ? wrow[k] : 0.0;
-                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b, acc, 0, 0, 0);
-                }
-            }
-        }
-        const double nc = cb_ok ? wn[cb] : 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dt[(kk + 4 * r) * KDT + wave * 16 + (lane & 15)] = nq[r] + nc - 2.0 * acc[r];
-        __syncthreads();
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int row = wave * 4 + rr;
-            if (q0 + row >= row_end) continue;
-            const long long ci = c0 + lane;
-            knn_offer(dt[row * KDT + lane], static_cast<int>(ci), ci < cend, Ld + row * K, Li + row * K, K, lane, thr[rr], widx[rr], wpos[rr]);
-        }
-        __syncthreads();
-    }
-    for (int e = tid; e < KQ * K; e += 256) {
-        const long long r = q0 - row0 + e / K;
-        if (r < rows) {
-            part_idx[(static_cast<long long>(blockIdx.y) * rows + r) * K + e % K] = Li[e];
-            part_dist[(static_cast<long long>(blockIdx.y) * rows + r) * K + e % K] = Ld[e];
-        }
-    }
-}
-
-// tsne.hip: knn_merge_kernel, between two matrices.  One wave per query row of the launch: the K best of the chunks' lists (nc x K
-// candidates, chunk after chunk), re-ranked by the direct sum (q_c - x_jc)^2 in column order on the caller's values, sorted by
-// (distance, index) and written as Euclidean distances.  A row left with a sentinel sets *bad and reads nothing through it.
-__global__ __launch_bounds__(256) void knn_cross_merge_kernel(const double *__restrict__ Xq, const double *__restrict__ Xr, long long nq,
-                                                              long long nref, int d, int K, long long row0, long long rows, int nc,
-                                                              const int *__restrict__ part_idx, const double *__restrict__ part_dist,
-                                                              int *__restrict__ out_idx, double *__restrict__ out_dist, int *__restrict__ bad) {
-    extern __shared__ double smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double *Ld = smem + wave * K;                                  // [4][K] doubles, then [4][K] ints
-    int *Li = reinterpret_cast<int *>(smem + 4 * K) + wave * K;
-    const long long r = static_cast<long long>(blockIdx.x) * 4 + wave, qq = row0 + r;
-    if (r >= rows || qq >= nq) return;
-    for (int p = lane; p < K; p += 64) { Ld[p] = KNN_INF; Li[p] = INT_MAX; }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    double thr = KNN_INF;
-    int widx = INT_MAX, wpos = 0;
-    for (int c = 0; c < nc; ++c) {
-        const long long base = (static_cast<long long>(c) * rows + r) * K;
-        for (int t = 0; t < K; t += 64) {
-            const bool in = t + lane < K;
-            const int ci = in ? part_idx[base + t + lane] : INT_MAX;
-            const double v = in ? part_dist[base + t + lane] : KNN_INF;
-            knn_offer(v, ci, in && ci >= 0 && ci < nref, Ld, Li, K, lane, thr, widx, wpos);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (int p = lane; p < K; p += 64) {
-        const int j = Li[p];
-        double s = KNN_INF;
-        if (j >= 0 && j < nref) {
-            s = 0.0;
-            for (int c = 0; c < d; ++c) { const double t = Xq[qq * d + c] - Xr[static_cast<long long>(j) * d + c]; s += t * t; }
-        } else {
-            *bad = 1;   // every writer stores the same value
-        }
-        Ld[p] = s;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (int p = lane; p < K; p += 64) {
-        const double dp = Ld[p];
-        const int ip = Li[p];
-        int rank = 0;
-        for (int q = 0; q < K; ++q) rank += lex_less(Ld[q], Li[q], dp, ip) ? 1 : 0;
-        out_idx[qq * K + rank] = ip < nref ? ip : -1;
-        out_dist[qq * K + rank] = sqrt(dp);
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // weights and start
@@ -395,25 +180,8 @@ void upload_checked(const double *X, long long n, int d, long long ld, const std
             if (!std::isfinite(X[i * ld + c]))
                 throw Error(SHARP_ERR_ARG, who + ": " + arg + " holds NA / NaN / Inf (row " + std::to_string(i + 1) + ", column " +
                                                std::to_string(c + 1) + ")");
-    dst.alloc(static_cast<size_t>(n) * d);
-    SHARP_HIP_CHECK(hipMemcpy2DAsync(dst.p, sizeof(double) * d, X, sizeof(double) * ld, sizeof(double) * d, static_cast<size_t>(n),
-                                     hipMemcpyHostToDevice, ctx().stream));
+    upload_rows(X, n, d, ld, dst);
     stream_sync();
-}
-
-// out = X - mu and its squared row norms; refuses norms that are not finite or would overflow a squared distance
-void center_and_norm(const double *dX, long long n, int d, const double *mu, DevBuf<double> &out, DevBuf<double> &nrm, const std::string &msg) {
-    Ctx &c = ctx();
-    out.alloc(static_cast<size_t>(n) * d);
-    nrm.alloc(n);
-    DevBuf<int> bad(1);
-    bad.zero();
-    hipLaunchKernelGGL(center_rows_kernel, dim3(grid_for(n * d, 256)), dim3(256), 0, c.stream, dX, n, d, mu, out.p);
-    hipLaunchKernelGGL(rownorm_check_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, out.p, n, d, nrm.p, bad.p);
-    launch_check("rownorm_check_kernel");
-    int hb = 0;
-    bad.download(&hb, 1);
-    SHARP_REQUIRE(hb == 0, msg);
 }
 
 void check_run_args(const char *who, int E, int ep0, int ep1, double learning_rate, int negative_sample_rate, double repulsion_strength,
@@ -436,54 +204,6 @@ void check_run_args(const char *who, int E, int ep0, int ep1, double learning_ra
 // the stages on device buffers
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace {
-
-// the K nearest reference rows of every row of dXq (device, nq x d packed): idx / dist (device, nq x K, Euclidean)
-void knn_cross(const UmapModel &m, const double *dXq, long long nq, int K, int max_rows, DevBuf<int> &idx, DevBuf<double> &dist, const char *who) {
-    Ctx &c = ctx();
-    const std::string w(who);
-    const long long n = m.n;
-    const int d = m.d;
-    SHARP_REQUIRE(K >= 1 && K <= 255, w + ": K must be in 1 .. 255");
-    SHARP_REQUIRE(K <= n, w + ": K must not exceed the model's number of reference rows");
-    SHARP_REQUIRE(nq >= 1 && nq < INT_MAX, w + ": nq must be in 1 .. 2^31 - 1");
-    SHARP_REQUIRE(max_rows >= 0, w + ": max_rows_per_launch must be >= 0 (0: the library's choice)");
-    const int ksteps = (d + 3) / 4;
-    const bool panel = ksteps > KREG;
-    const size_t lds = sizeof(double) * KQ * KDT + (sizeof(double) + sizeof(int)) * KQ * K + (panel ? sizeof(double) * 64 * ksteps : 0);
-    SHARP_REQUIRE(lds <= LDS_MAX, w + ": d is too large for the query panel at this K (reduce the data first)");
-    KernelTimer t("umap_knn_cross");
-    DevBuf<double> Qc, qn;
-    center_and_norm(dXq, nq, d, m.mu.p, Qc, qn, w + ": Xq holds NA / NaN / Inf, or values so large that squared distances overflow");
-    idx.alloc(static_cast<size_t>(nq) * K);
-    dist.alloc(static_cast<size_t>(nq) * K);
-    // tsne_knn's launch budget (about 8e9 candidate pairs at d = 50) and chunk rule (>= ~1024 workgroups a launch); neither changes a
-    // row's list: a pair's value depends on d and its two rows, and every comparison is exact
-    const double budget = 8e9 / (std::max(d, 4) / 50.0 + 0.25);
-    long long rows = std::min((nq + KQ - 1) / KQ * KQ, std::max<long long>(KQ, static_cast<long long>(budget / static_cast<double>(n)) / KQ * KQ));
-    if (max_rows > 0) rows = std::min(rows, std::max<long long>(KQ, max_rows / KQ * KQ));
-    const long long rb = (rows + KQ - 1) / KQ;
-    const long long nc0 = std::max<long long>(1, std::min<long long>((n + KCT - 1) / KCT, (1024 + rb - 1) / rb));
-    const long long cj = ((n + nc0 - 1) / nc0 + KCT - 1) / KCT * KCT;
-    const int nc = static_cast<int>((n + cj - 1) / cj);
-    DevBuf<int> pidx(static_cast<size_t>(nc) * rows * K), bad(1);
-    DevBuf<double> pdist(static_cast<size_t>(nc) * rows * K);
-    bad.zero();
-    const size_t lds_merge = (sizeof(double) + sizeof(int)) * 4 * K;
-    auto kern = panel ? knn_cross_kernel<true> : knn_cross_kernel<false>;
-    if (lds > 65536) SHARP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    for (long long r0 = 0; r0 < nq; r0 += rows) {
-        const long long r1 = std::min(nq, r0 + rows);
-        hipLaunchKernelGGL(kern, dim3(grid_for(r1 - r0, KQ), nc), dim3(256), lds, c.stream, Qc.p, qn.p, m.W.p, m.wn.p, n, d, K, r0, r1, cj, pidx.p,
-                           pdist.p);
-        launch_check("knn_cross_kernel");
-        hipLaunchKernelGGL(knn_cross_merge_kernel, dim3(grid_for(r1 - r0, 4)), dim3(256), lds_merge, c.stream, dXq, m.X.p, nq, n, d, K, r0, r1 - r0,
-                           nc, pidx.p, pdist.p, idx.p, dist.p, bad.p);
-        launch_check("knn_cross_merge_kernel");
-    }
-    int hb = 0;
-    bad.download(&hb, 1);   // (synchronises: the temporaries go out of scope)
-    SHARP_REQUIRE(hb == 0, w + ": fewer than K reference rows at a finite distance from some row");
-}
 
 void transform_weights(const UmapModel &m, const int *idx, const double *dist, long long nq, int K, double *sigma, double *w, double *Y0) {
     Ctx &c = ctx();
@@ -603,7 +323,7 @@ int sharp_knn_cross(int handle, const double *Xq, long long nq, long long ld, in
     DevBuf<double> dXq, dd;
     DevBuf<int> di;
     upload_checked(Xq, nq, m->d, ld, who, "Xq", dXq);
-    knn_cross(*m, dXq.p, nq, K, max_rows_per_launch, di, dd, who);
+    knn_cross(who, m->W.p, m->wn.p, m->X.p, m->mu.p, m->n, m->d, dXq.p, nq, K, max_rows_per_launch, di, dd);
     di.download(idx, static_cast<size_t>(nq) * K);
     dd.download(dist, static_cast<size_t>(nq) * K);
     SHARP_API_END
@@ -667,7 +387,7 @@ int sharp_umap_transform(int handle, const double *Xq, long long nq, long long l
     DevBuf<double> dXq, dist;
     DevBuf<int> idx;
     upload_checked(Xq, nq, m->d, ld, who, "Xq", dXq);
-    knn_cross(*m, dXq.p, nq, K, 0, idx, dist, who.c_str());
+    knn_cross(who.c_str(), m->W.p, m->wn.p, m->X.p, m->mu.p, m->n, m->d, dXq.p, nq, K, 0, idx, dist);
     dXq.release();
     if (nn_index) {
         idx.download(nn_index, static_cast<size_t>(nq) * K);

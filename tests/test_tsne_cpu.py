@@ -233,3 +233,18 @@ def test_figure_from_given_coordinates(tmp_path, filetype):
     for f in (f1, f2):
         assert os.path.getsize(f) > 1000
         assert open(f, "rb").read(4) == magic
+
+
+def test_the_refusal_tests_unspoiled_lists_are_sound():
+    """the premise of tests/test_neighbour_refusals_gpu.py: before a list is spoiled, the lists of its input pass the host check and
+    name, in every row, K different rows in range, none of them the row itself"""
+    from sharp_amd.tsne import _neighbour_arrays
+    from test_neighbour_refusals_gpu import K, N, gaussian
+
+    idx, dist = ref.knn(gaussian(), K)
+    index, distance = _neighbour_arrays(idx, dist, "Rtsne_neighbors")
+    assert index.shape == distance.shape == (N, K) and index.dtype == np.int32 and distance.dtype == np.float64
+    assert ((index >= 0) & (index < N)).all() and (index != np.arange(N)[:, None]).all()
+    s = np.sort(index, axis=1)
+    assert (s[:, 1:] != s[:, :-1]).all(), "an index twice in a row"
+    assert np.isfinite(distance).all() and (distance >= 0).all()
