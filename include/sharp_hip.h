@@ -668,6 +668,39 @@ int sharp_expr_spmm_genes(const int *const *colptr, const int *const *rowidx, co
 int sharp_expr_orth(const double *Y, long long rows, int l, double *Q);
 int sharp_expr_row_caps(int *chunk, int *slab_rows);
 
+/* ---- Variable-gene selection and gene subsets (sharp_amd/csrc/hvg.hip, expr_pca.hip) -----------------------------------
+ * The *_sub_* entries are the three above with a gene subset: genes = n_genes strictly ascending indices within [0, m) (anything else
+ * is refused by name); NULL and 0 mean all genes, which is what the entries above pass.  The whole blocks are uploaded and validated,
+ * the cells' sums L_c are taken over all m genes and the transform runs; then the entries of the other genes are dropped and the kept
+ * genes renumbered by their position in `genes`, and the fit is the one above on n_genes genes (Omega keyed by the new index; l <=
+ * min(n, n_genes)): loadings, center, scale_out, gene_var (mean, var, nnz) have n_genes rows.  cell_sum stays the sum over all genes.
+ * sharp_expr_pca_transform_sub_csc: the new cells have m genes, the fit's loadings / center / scale n_genes rows.
+ * sharp_expr_hvg_csc: raw counts (a negative value is refused), n >= 2.  mu, var = the gene statistics above of the untransformed
+ * values; over the N genes with var > 0 (1 <= N <= 2^20), x = log10 mu, y = log10 var, fit = a local quadratic (tricube weights,
+ * bandwidth = the q-th smallest |x_j - x_i|, q = min(N, max(3, ceil(span N))), span in (0, 1], no robustness iterations; the
+ * degree falls to 1 / 0 when the pivot p2 / p1 of the unpivoted LDL^T of the moment matrix is <= 2^-30 S0; bandwidth 0: the mean
+ * of y over the points with x_j = x_i); sigma^2 = 10^fit, clip = mu + sigma sqrt(n), variances_norm = (sum over the stored
+ * entries of (min(x, clip) - mu)^2 + (n - stored) mu^2) / ((n - 1) sigma^2), 0 for a constant gene.  The first min(n_top_genes, N)
+ * genes by variances_norm descending (ties: the lower gene) are selected: rank (0-based, -1: not selected), highly_variable (0 / 1),
+ * genes (the selected, ascending; room for min(n_top_genes, m)), *n_selected, *q, degree_counts (3: fits of degree 0, 1, 2).
+ * variances_expected = sigma^2 (0 for a constant gene).  Bitwise reproducible like the entries above.
+ * sharp_hvg_loess (stage entry for the tests): the fit at every one of the caller's points (1 <= npts <= 2^20, finite), with its
+ * bandwidth and degree, in the caller's order. */
+int sharp_expr_pca_sub_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks,
+                           int m, int n_components, int oversample, int n_iter, double normalize_total, int log1p, int scale, long long seed,
+                           double *scores, double *loadings, double *singular_values, double *sdev, double *center, double *scale_out,
+                           double *gene_var, double *total_var, const int *genes, int n_genes);
+int sharp_expr_stats_sub_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks,
+                             int m, double normalize_total, int log1p, double *mean, double *var, long long *nnz, double *cell_sum,
+                             const int *genes, int n_genes);
+int sharp_expr_pca_transform_sub_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb,
+                                     int nblocks, int m, double normalize_total, int log1p, const double *loadings, const double *center,
+                                     const double *scale, int n_components, double *scores, const int *genes, int n_genes);
+int sharp_expr_hvg_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks, int m,
+                       int n_top_genes, double span, double *means, double *variances, double *variances_expected, double *variances_norm,
+                       int *rank, int *highly_variable, int *genes, int *n_selected, int *q, int *degree_counts);
+int sharp_hvg_loess(const double *x, const double *y, int npts, double span, double *fit, double *bandwidth, int *degree);
+
 /* ---- synthetic inputs (bench / tests; not part of the reference) ------------ */
 /* Counter-based generator, value = f(seed, gene, cell): bit-identical to
  * oracle_synth_value().  Fills dX (fp32, m x ncell column-major, leading dim ld). */
@@ -865,6 +898,20 @@ void sharp_C_expr_stats_csc(int *pcat, int *icat, double *xcat, int *nblocks, do
                             double *mean, double *var, double *nnz, double *cell_sum, int *status);
 void sharp_C_expr_pca_transform_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, double *normalize_total, int *log1p,
                                     double *loadings, double *center, double *scale, int *n_components, double *scores, int *status);
+/* the *_sub_* entries and sharp_expr_hvg_csc in the same convention: genes 0-based, *n_genes = 0 for all genes (genes is then a buffer
+ * of length >= 1 that is left alone) */
+void sharp_C_expr_pca_sub_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, int *n_components, int *oversample,
+                              int *n_iter, double *normalize_total, int *log1p, int *scale, double *seed, double *scores, double *loadings,
+                              double *singular_values, double *sdev, double *center, double *scale_out, double *gene_var, double *total_var,
+                              int *genes, int *n_genes, int *status);
+void sharp_C_expr_stats_sub_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, double *normalize_total, int *log1p,
+                                double *mean, double *var, double *nnz, double *cell_sum, int *genes, int *n_genes, int *status);
+void sharp_C_expr_pca_transform_sub_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, double *normalize_total,
+                                        int *log1p, double *loadings, double *center, double *scale, int *n_components, double *scores,
+                                        int *genes, int *n_genes, int *status);
+void sharp_C_expr_hvg_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, int *n_top_genes, double *span, double *means,
+                          double *variances, double *variances_expected, double *variances_norm, int *rank, int *highly_variable, int *genes,
+                          int *n_selected, int *q, int *degree_counts, int *status);
 
 #ifdef __cplusplus
 }

@@ -815,6 +815,69 @@ sharp_gene_stats <- function(scExp, normalize.total = 1e4, log1p = TRUE) {
     list(mean = r$mean, var = r$var, nnz = r$nnz, cell.sum = r$cell_sum)
 }
 
+# Variable-gene selection and gene subsets (DESIGN.md 22).  genes: 1-based, strictly ascending indices, or a logical mask of length m.
+.sharp_genes0 <- function(genes, m, who) {
+    if (is.logical(genes)) {
+        if (length(genes) != m) stop(paste0(who, ": the genes mask must have one entry per gene"))
+        genes <- which(genes)
+    }
+    genes <- as.integer(genes)
+    if (length(genes) < 1) stop(paste0(who, ": genes is empty (it must keep at least one gene)"))
+    genes - 1L                                   # (the library refuses unsorted, repeated and out-of-range genes by name)
+}
+# the n.top.genes most variable genes of raw counts: list(means, variances, variances.expected, variances.norm, rank (1-based among
+# the selected, NA otherwise), highly.variable, genes (1-based, ascending: what sharp_expression_pca_genes takes), n.selected, q,
+# degree.counts)
+sharp_highly_variable_genes <- function(scExp, n.top.genes = 2000L, span = 0.3) {
+    b <- .sharp_csc_cat(scExp, "sharp_highly_variable_genes")
+    top <- as.integer(n.top.genes)
+    r <- .C("sharp_C_expr_hvg_csc", as.integer(b$p), as.integer(b$i), b$x, b$nb, b$ncb, b$m, top, as.double(span), means = double(b$m),
+            variances = double(b$m), ve = double(b$m), vn = double(b$m), rank = integer(b$m), hv = integer(b$m),
+            genes = integer(max(min(top, b$m), 1L)), ns = integer(1), q = integer(1), dc = integer(3), status = integer(1))
+    .sharp_check(r$status)
+    list(means = r$means, variances = r$variances, variances.expected = r$ve, variances.norm = r$vn,
+         rank = ifelse(r$rank < 0L, NA_integer_, r$rank + 1L), highly.variable = r$hv != 0L, genes = r$genes[seq_len(r$ns)] + 1L,
+         n.selected = r$ns, span = span, q = r$q, degree.counts = r$dc)
+}
+# sharp_expression_pca on the genes `genes` alone: the cells are normalised by their sums over all genes, then the others are dropped
+sharp_expression_pca_genes <- function(scExp, genes, n.components = 50L, oversample = 10L, n.iter = 4L, normalize.total = 1e4, log1p = TRUE,
+                                       scale = FALSE, seed = 0) {
+    b <- .sharp_csc_cat(scExp, "sharp_expression_pca_genes")
+    g <- .sharp_genes0(genes, b$m, "sharp_expression_pca_genes")
+    n <- sum(b$ncb); k <- as.integer(n.components); mk <- length(g)
+    r <- .C("sharp_C_expr_pca_sub_csc", as.integer(b$p), as.integer(b$i), b$x, b$nb, b$ncb, b$m, k, as.integer(oversample),
+            as.integer(n.iter), as.double(if (is.null(normalize.total)) 0 else normalize.total), as.integer(log1p), as.integer(scale),
+            as.double(seed), scores = double(n * k), loadings = double(mk * k), sv = double(k), sdev = double(k), center = double(mk),
+            scale = double(mk), gene_var = double(mk), total_var = double(1), g, mk, status = integer(1))
+    .sharp_check(r$status)
+    list(scores = t(matrix(r$scores, nrow = k)), loadings = t(matrix(r$loadings, nrow = k)), singular.values = r$sv, sdev = r$sdev,
+         center = r$center, scale = r$scale, gene.var = r$gene_var, total.var = r$total_var, normalize.total = normalize.total, log1p = log1p,
+         genes = g + 1L, n.genes.in = b$m)
+}
+# the scores of new cells (with all n.genes.in genes) in a fit of sharp_expression_pca_genes
+sharp_expression_pca_genes_transform <- function(scExp.new, fit) {
+    b <- .sharp_csc_cat(scExp.new, "sharp_expression_pca_genes_transform")
+    if (b$m != fit$n.genes.in) stop("the new cells and the fit do not have the same genes")
+    g <- as.integer(fit$genes) - 1L
+    n <- sum(b$ncb); k <- ncol(fit$loadings)
+    r <- .C("sharp_C_expr_pca_transform_sub_csc", as.integer(b$p), as.integer(b$i), b$x, b$nb, b$ncb, b$m,
+            as.double(if (is.null(fit$normalize.total)) 0 else fit$normalize.total), as.integer(fit$log1p), as.double(t(fit$loadings)),
+            as.double(fit$center), as.double(fit$scale), as.integer(k), scores = double(max(n * k, 1)), g, length(g), status = integer(1))
+    .sharp_check(r$status)
+    t(matrix(r$scores[seq_len(n * k)], nrow = k))
+}
+# sharp_gene_stats of the genes `genes` alone; cell.sum stays the sum over all genes
+sharp_gene_stats_genes <- function(scExp, genes, normalize.total = 1e4, log1p = TRUE) {
+    b <- .sharp_csc_cat(scExp, "sharp_gene_stats_genes")
+    g <- .sharp_genes0(genes, b$m, "sharp_gene_stats_genes")
+    mk <- length(g)
+    r <- .C("sharp_C_expr_stats_sub_csc", as.integer(b$p), as.integer(b$i), b$x, b$nb, b$ncb, b$m,
+            as.double(if (is.null(normalize.total)) 0 else normalize.total), as.integer(log1p), mean = double(mk), var = double(mk),
+            nnz = double(mk), cell_sum = double(sum(b$ncb)), g, mk, status = integer(1))
+    .sharp_check(r$status)
+    list(mean = r$mean, var = r$var, nnz = r$nnz, cell.sum = r$cell_sum)
+}
+
 # the same on any symmetric graph: a dgCMatrix-like triple (row_ptr 0-based with n + 1 values, col 0-based, val)
 sharp_louvain_graph <- function(row_ptr, col, val, resolution = 1, seed = 10, tol = 1e-7, max_levels = 20L, max_rounds = 200L,
                                 max_fails = 4L, ret_levels = FALSE) {

@@ -13,4 +13,5 @@ from .mapquality import continuity, knn_recall, neighbor_ranks, trustworthiness 
 from .community import louvain, louvain_graph, louvain_neighbors, louvain_snn, modularity  # noqa: F401
 from .snn import snn, snn_graph  # noqa: F401
 from .expr_pca import expression_pca, expression_pca_transform, gene_stats  # noqa: F401
+from .hvg import highly_variable_genes  # noqa: F401
 from . import dist  # noqa: F401,E402  (the multi-GPU module; calling it is R's dist() on the GPU, sharp_amd/tree.py)

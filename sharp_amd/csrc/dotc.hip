@@ -484,4 +484,42 @@ void sharp_C_expr_pca_transform_csc(int *pcat, int *icat, double *xcat, int *nbl
                                            loadings, center, scale, *n_components, scores);
 }
 
+/* Gene subsets and variable-gene selection: *n_genes = 0 stands for all genes */
+void sharp_C_expr_pca_sub_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, int *n_components, int *oversample,
+                              int *n_iter, double *normalize_total, int *log1p, int *scale, double *seed, double *scores, double *loadings,
+                              double *singular_values, double *sdev, double *center, double *scale_out, double *gene_var, double *total_var,
+                              int *genes, int *n_genes, int *status) {
+    const CscList L(pcat, icat, xcat, *nblocks, ncb, status);
+    if (!L.ok) return;
+    *status = sharp_expr_pca_sub_csc(L.cp.data(), L.ri.data(), L.vx.data(), L.nc.data(), *nblocks, *m, *n_components, *oversample, *n_iter,
+                                     *normalize_total, *log1p, *scale, as_ll(seed), scores, loadings, singular_values, sdev, center,
+                                     scale_out, gene_var, total_var, *n_genes ? genes : nullptr, *n_genes);
+}
+void sharp_C_expr_stats_sub_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, double *normalize_total, int *log1p,
+                                double *mean, double *var, double *nnz, double *cell_sum, int *genes, int *n_genes, int *status) {
+    const CscList L(pcat, icat, xcat, *nblocks, ncb, status);
+    if (!L.ok) return;
+    std::vector<long long> z(*m > 0 ? static_cast<size_t>(*m) : 1, 0);
+    *status = sharp_expr_stats_sub_csc(L.cp.data(), L.ri.data(), L.vx.data(), L.nc.data(), *nblocks, *m, *normalize_total, *log1p, mean, var,
+                                       z.data(), cell_sum, *n_genes ? genes : nullptr, *n_genes);
+    if (*status == 0)
+        for (int g = 0; g < (*n_genes ? *n_genes : *m); ++g) nnz[g] = static_cast<double>(z[g]);
+}
+void sharp_C_expr_pca_transform_sub_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, double *normalize_total,
+                                        int *log1p, double *loadings, double *center, double *scale, int *n_components, double *scores,
+                                        int *genes, int *n_genes, int *status) {
+    const CscList L(pcat, icat, xcat, *nblocks, ncb, status);
+    if (!L.ok) return;
+    *status = sharp_expr_pca_transform_sub_csc(L.cp.data(), L.ri.data(), L.vx.data(), L.nc.data(), *nblocks, *m, *normalize_total, *log1p,
+                                               loadings, center, scale, *n_components, scores, *n_genes ? genes : nullptr, *n_genes);
+}
+void sharp_C_expr_hvg_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, int *n_top_genes, double *span, double *means,
+                          double *variances, double *variances_expected, double *variances_norm, int *rank, int *highly_variable, int *genes,
+                          int *n_selected, int *q, int *degree_counts, int *status) {
+    const CscList L(pcat, icat, xcat, *nblocks, ncb, status);
+    if (!L.ok) return;
+    *status = sharp_expr_hvg_csc(L.cp.data(), L.ri.data(), L.vx.data(), L.nc.data(), *nblocks, *m, *n_top_genes, *span, means, variances,
+                                 variances_expected, variances_norm, rank, highly_variable, genes, n_selected, q, degree_counts);
+}
+
 }  // extern "C"

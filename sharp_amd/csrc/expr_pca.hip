@@ -3,6 +3,9 @@
 //   upload     the blocks' stored entries side by side (cell-major: cptr, ridx, t), validated by expr_validate_kernel before anything
 //              dereferences an index (range, strictly ascending within a cell, finite, >= 0 under a transform), the cells' sums
 //              L_c, then t = log1p(x T / L_c) in place
+//   subset     with a gene list: after the transform the entries of the other genes are dropped and the kept genes
+//              renumbered (a count per cell, one wave each; the scan; a fill that keeps the stored order); everything below then works
+//              on the kept genes
 //   transpose  the gene-major copy (gptr, gcell, gval) by one stable radix sort of (gene << 32 | cell) keys on the gene bits: a gene's
 //              entries stand in ascending cell order; a gene's entries are cut into chunks of kExprChunk
 //   stats      mu and var per gene in two passes over the gene-major copy: one wave per chunk (64 strided sums, then the butterfly), a
@@ -87,6 +90,46 @@ __global__ __launch_bounds__(256) void expr_transform_kernel(const long long *__
     }
 }
 
+// cnt[c] = the cell's entries whose gene is kept (remap[gene] >= 0): one wave per cell
+__global__ __launch_bounds__(256) void expr_subset_count_kernel(const long long *__restrict__ cptr, const int *__restrict__ ridx, long long n,
+                                                                const int *__restrict__ remap, long long *__restrict__ cnt) {
+    const long long c = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (c >= n) return;
+    const int lane = threadIdx.x & 63;
+    const long long e = cptr[c + 1];
+    int k = 0;
+    for (long long p = cptr[c] + lane; p < e; p += 64) k += remap[ridx[p]] >= 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) k += __shfl_xor(k, off);
+    if (lane == 0) cnt[c] = k;
+}
+
+// the kept entries of cell c, in stored order and renumbered, into [nptr[c], nptr[c + 1]): 64 entries at a time, each kept one placed
+// behind the kept ones of the lower lanes
+__global__ __launch_bounds__(256) void expr_subset_fill_kernel(const long long *__restrict__ cptr, const int *__restrict__ ridx,
+                                                               const double *__restrict__ val, long long n, const int *__restrict__ remap,
+                                                               const long long *__restrict__ nptr, int *__restrict__ ridx2,
+                                                               double *__restrict__ val2) {
+    const long long c = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (c >= n) return;
+    const int lane = threadIdx.x & 63;
+    const long long e = cptr[c + 1];
+    long long o = nptr[c];
+    for (long long p0 = cptr[c]; p0 < e; p0 += 64) {
+        const long long p = p0 + lane;
+        int r = -1;
+        double v = 0.0;
+        if (p < e) { r = remap[ridx[p]]; v = val[p]; }
+        const u64 keep = __ballot(r >= 0);
+        if (r >= 0) {
+            const long long at = o + __popcll(keep & ((1ull << lane) - 1ull));
+            ridx2[at] = r;
+            val2[at] = v;
+        }
+        o += __popcll(keep);
+    }
+}
+
 // keys[p] = (gene << 32 | cell) of every stored entry
 __global__ __launch_bounds__(256) void expr_keys_kernel(const long long *__restrict__ cptr, const int *__restrict__ ridx, long long n,
                                                         u64 *__restrict__ keys) {
@@ -126,14 +169,6 @@ __global__ __launch_bounds__(256) void expr_chgene_kernel(const long long *__res
     if (g >= m) return;
     const long long e = chptr[g + 1];
     for (long long ch = chptr[g]; ch < e; ++ch) chgene[ch] = g;
-}
-
-// the entries [b, e) of chunk ch
-__device__ __forceinline__ void chunk_range(const long long *__restrict__ gptr, const long long *__restrict__ chptr, int g, long long ch,
-                                            long long &b, long long &e) {
-    b = gptr[g] + (ch - chptr[g]) * kExprChunk;
-    const long long ge = gptr[g + 1];
-    e = b + kExprChunk < ge ? b + kExprChunk : ge;
 }
 
 // One wave per chunk.  PASS 0: the chunk's sum, its non-zero values, its smallest and its largest value.  PASS 1: its sum of (t - mu_g)^2.
@@ -406,8 +441,6 @@ __global__ __launch_bounds__(256) void expr_flip_kernel(double *__restrict__ X, 
     if (e < rows * k) X[e] *= sign[e % k];
 }
 
-unsigned wave_grid(long long items) { return grid_for(items, 4); }
-
 // G (host, l x l) = Y^T Y
 void gram(const double *Y, long long rows, int l, std::vector<double> &G) {
     Ctx &c = ctx();
@@ -467,8 +500,11 @@ void column_sums(const double *col, long long rows, int l, double *red, double *
     for (int j = 0; j < l; ++j) fixed_reduce(Fold::Sum, col + static_cast<long long>(j) * rows, rows, red, out + j);
 }
 
-double bytes_needed(long long n, long long m, long long nnz, bool genes, int l) {
+// m: the genes of the copies that the fit works on; m_in > 0: a subset of m_in genes, whose count, scan, fill and table stand beside the
+// full cell-major copy
+double bytes_needed(long long n, long long m, long long nnz, bool genes, int l, long long m_in) {
     double b = static_cast<double>(nnz) * 12.0 + static_cast<double>(n) * 16.0 + 67108864.0;
+    if (m_in > 0) b += static_cast<double>(nnz) * 12.0 + static_cast<double>(n) * 24.0 + static_cast<double>(m_in) * 4.0;
     if (genes) b += static_cast<double>(nnz) * 28.0 + static_cast<double>(nnz / kExprChunk + m) * 32.0 + static_cast<double>(m) * 80.0;
     if (l > 0) {
         const double rows = static_cast<double>(std::max(n, m));
@@ -476,11 +512,6 @@ double bytes_needed(long long n, long long m, long long nnz, bool genes, int l) 
         b += std::min(rows / kExprSlabRows + 1.0, static_cast<double>(kGramBatch)) * l * l * 8.0;
     }
     return b;
-}
-
-void check_options(const std::string &who, double normalize_total, int m) {
-    SHARP_REQUIRE(m >= 1 && m <= kExprMaxM, who + ": need 1 <= m <= 16777216 genes");
-    SHARP_REQUIRE(std::isfinite(normalize_total) && normalize_total >= 0.0, who + ": normalize_total must be finite and >= 0 (0: off)");
 }
 
 void check_l(const std::string &who, int k, int oversample, long long n, int m) {
@@ -491,7 +522,48 @@ void check_l(const std::string &who, int k, int oversample, long long n, int m) 
                   who + ": n_components + oversample must be <= min(cells, genes)");
 }
 
-long long total_cells(const std::string &who, const ExprBlocks &B) {
+// Drops the entries of the genes that `genes` does not keep and renumbers the kept ones by their position in it: a count
+// per cell, the scan, a fill into fresh buffers.  genes was checked by expr_check_genes.
+void expr_subset(ExprData &D, const int *genes, int mk) {
+    Ctx &c = ctx();
+    KernelTimer timer("expr_subset");
+    const long long n = D.n;
+    std::vector<int> map(D.m, -1);
+    for (int i = 0; i < mk; ++i) map[genes[i]] = i;
+    DevBuf<int> remap(D.m);
+    remap.upload(map.data(), map.size());
+    DevBuf<long long> cnt(n + 1), nptr(n + 1);
+    Scratch tmp;
+    SHARP_HIP_CHECK(hipMemsetAsync(cnt.p + n, 0, sizeof(long long), c.stream));      // (the scan's extra slot)
+    hipLaunchKernelGGL(expr_subset_count_kernel, dim3(wave_grid(n)), dim3(256), 0, c.stream, D.cptr.p, D.ridx.p, n, remap.p, cnt.p);
+    launch_check("expr_subset_count_kernel");
+    exclusive_scan(cnt.p, nptr.p, static_cast<size_t>(n + 1), tmp);
+    long long kept = 0;
+    SHARP_HIP_CHECK(hipMemcpyAsync(&kept, nptr.p + n, sizeof(long long), hipMemcpyDeviceToHost, c.stream));
+    stream_sync();
+    DevBuf<int> ridx2(std::max<long long>(kept, 1));
+    DevBuf<double> t2(std::max<long long>(kept, 1));
+    hipLaunchKernelGGL(expr_subset_fill_kernel, dim3(wave_grid(n)), dim3(256), 0, c.stream, D.cptr.p, D.ridx.p, D.t.p, n, remap.p, nptr.p,
+                       ridx2.p, t2.p);
+    launch_check("expr_subset_fill_kernel");
+    stream_sync();                                           // (the old copy, map and the temporaries go)
+    D.cptr = std::move(nptr);
+    D.ridx = std::move(ridx2);
+    D.t = std::move(t2);
+    D.nnz = kept;
+    D.m = mk;
+}
+
+}  // namespace
+
+unsigned wave_grid(long long items) { return grid_for(items, 4); }
+
+void expr_check_options(const std::string &who, double normalize_total, int m) {
+    SHARP_REQUIRE(m >= 1 && m <= kExprMaxM, who + ": need 1 <= m <= 16777216 genes");
+    SHARP_REQUIRE(std::isfinite(normalize_total) && normalize_total >= 0.0, who + ": normalize_total must be finite and >= 0 (0: off)");
+}
+
+long long expr_total_cells(const std::string &who, const ExprBlocks &B) {
     SHARP_REQUIRE(B.nblocks >= 1 && B.colptr && B.rowidx && B.val && B.ncb, who + ": need a list of at least one block");
     long long n = 0;
     for (int b = 0; b < B.nblocks; ++b) {
@@ -502,12 +574,23 @@ long long total_cells(const std::string &who, const ExprBlocks &B) {
     return n;
 }
 
-}  // namespace
+int expr_check_genes(const std::string &who, const int *genes, int n_genes, int m) {
+    if (!genes && n_genes == 0) return m;
+    SHARP_REQUIRE(genes && n_genes >= 1, who + ": genes is empty (it must keep at least one gene)");
+    for (int i = 0; i < n_genes; ++i) {
+        SHARP_REQUIRE(genes[i] >= 0 && genes[i] < m, who + ": genes holds an index outside [0, m) (position " + std::to_string(i) + ", counted from 0)");
+        if (i == 0) continue;
+        SHARP_REQUIRE(genes[i] != genes[i - 1], who + ": genes holds a gene twice (position " + std::to_string(i) + ", counted from 0)");
+        SHARP_REQUIRE(genes[i] > genes[i - 1], who + ": genes must be ascending (position " + std::to_string(i) + ", counted from 0)");
+    }
+    return n_genes;
+}
 
 void expr_load(const std::string &who, const ExprBlocks &B, double normalize_total, bool lg, bool genes, bool scale, int l_work,
-               long long min_cells, ExprData &D) {
-    check_options(who, normalize_total, B.m);
-    const long long n = total_cells(who, B);
+               long long min_cells, ExprData &D, const ExprExtra &extra) {
+    expr_check_options(who, normalize_total, B.m);
+    const long long n = expr_total_cells(who, B);
+    const int mk = expr_check_genes(who, extra.genes, extra.n_genes, B.m);
     SHARP_REQUIRE(n >= min_cells, who + ": need at least " + std::to_string(min_cells) + " cells in all");
     // the cells' offsets, from the blocks' own column pointers (checked here: the host reads the stored entries by them)
     std::vector<long long> cp(static_cast<size_t>(n) + 1);
@@ -530,15 +613,15 @@ void expr_load(const std::string &who, const ExprBlocks &B, double normalize_tot
     Ctx &c = ctx();
     size_t free_b = 0, total_b = 0;
     SHARP_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    const double need = bytes_needed(n, B.m, nnz, genes, l_work);
+    const double need = bytes_needed(n, mk, nnz, genes, l_work, extra.genes ? B.m : 0);
     SHARP_REQUIRE(need <= static_cast<double>(free_b), who + ": the expression data (" + std::to_string(nnz) + " stored entries" +
                                                           (genes ? ", two copies" : "") + ") and the workspaces need about " +
                                                           std::to_string(static_cast<long long>(need / 1048576.0)) +
                                                           " MB; the device has " + std::to_string(free_b >> 20) + " MB free");
     D.n = n;
-    D.m = B.m;
+    D.m = D.m_in = B.m;
     D.nnz = nnz;
-    const bool check_neg = normalize_total > 0.0 || lg;
+    const bool check_neg = normalize_total > 0.0 || lg || extra.refuse_negative;
     {
         KernelTimer timer("expr_upload");
         D.cptr.alloc(n + 1);
@@ -565,19 +648,28 @@ void expr_load(const std::string &who, const ExprBlocks &B, double normalize_tot
                 case EX_RANGE: throw Error(SHARP_ERR_ARG, who + ": a gene index outside [0, m)" + cell);
                 case EX_ORDER: throw Error(SHARP_ERR_ARG, who + ": gene indices must be strictly ascending within a cell" + cell);
                 case EX_FINITE: throw Error(SHARP_ERR_ARG, who + ": a value that is NaN or infinite" + cell);
-                default: throw Error(SHARP_ERR_ARG, who + ": a negative value under normalize_total / log1p" + cell);
+                default:
+                    throw Error(SHARP_ERR_ARG, who + (extra.refuse_negative ? ": a negative value where counts are expected" :
+                                                                              ": a negative value under normalize_total / log1p") + cell);
             }
         }
         hipLaunchKernelGGL(expr_cell_sums_kernel, dim3(wave_grid(n)), dim3(256), 0, c.stream, D.cptr.p, D.t.p, n, D.lsum.p);
-        if (check_neg)
+        if (normalize_total > 0.0 || lg)
             hipLaunchKernelGGL(expr_transform_kernel, dim3(wave_grid(n)), dim3(256), 0, c.stream, D.cptr.p, D.lsum.p, n, normalize_total, lg ? 1 : 0,
                                D.t.p);
         launch_check("expr_transform_kernel");
+        if (extra.want_tsum) {
+            D.tsum.alloc(std::max<long long>(n, 1));
+            hipLaunchKernelGGL(expr_cell_sums_kernel, dim3(wave_grid(n)), dim3(256), 0, c.stream, D.cptr.p, D.t.p, n, D.tsum.p);
+            launch_check("expr_cell_sums_kernel");
+        }
     }
+    if (extra.genes) expr_subset(D, extra.genes, mk);
     if (!genes) return;
-    const int m = B.m;
+    const int m = D.m;
     {
         KernelTimer timer("expr_transpose");
+        const long long nnz = D.nnz;                         // (the kept entries under a subset)
         D.gptr.alloc(m + 1);
         D.gcell.alloc(std::max<long long>(nnz, 1));
         D.gval.alloc(std::max<long long>(nnz, 1));
@@ -762,66 +854,95 @@ int sharp_expr_pca_csc(const int *const *colptr, const int *const *rowidx, const
                        int n_components, int oversample, int n_iter, double normalize_total, int log1p, int scale, long long seed,
                        double *scores, double *loadings, double *singular_values, double *sdev, double *center, double *scale_out,
                        double *gene_var, double *total_var) {
+    return sharp_expr_pca_sub_csc(colptr, rowidx, val, ncb, nblocks, m, n_components, oversample, n_iter, normalize_total, log1p, scale, seed,
+                                  scores, loadings, singular_values, sdev, center, scale_out, gene_var, total_var, nullptr, 0);
+}
+
+int sharp_expr_pca_sub_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks,
+                           int m, int n_components, int oversample, int n_iter, double normalize_total, int log1p, int scale, long long seed,
+                           double *scores, double *loadings, double *singular_values, double *sdev, double *center, double *scale_out,
+                           double *gene_var, double *total_var, const int *genes, int n_genes) {
     SHARP_API_BEGIN
     const std::string w("expression_pca");
     SHARP_REQUIRE(scores && loadings && singular_values && sdev && center && scale_out && gene_var && total_var, w + ": null output");
     const ExprBlocks B{colptr, rowidx, val, ncb, nblocks, m};
-    check_options(w, normalize_total, m);
-    const long long n = total_cells(w, B);
+    expr_check_options(w, normalize_total, m);
+    const long long n = expr_total_cells(w, B);
     SHARP_REQUIRE(n >= 2, w + ": need at least 2 cells in all");
-    check_l(w, n_components, oversample, n, m);
+    const int mk = expr_check_genes(w, genes, n_genes, m);
+    check_l(w, n_components, oversample, n, mk);
     SHARP_REQUIRE(n_iter >= 0 && n_iter <= 1000, w + ": n_iter must be in 0 .. 1000");
     ctx();
     ExprData D;
-    expr_load(w, B, normalize_total, log1p != 0, true, scale != 0, n_components + oversample, 2, D);
+    ExprExtra extra;
+    extra.genes = genes;
+    extra.n_genes = n_genes;
+    expr_load(w, B, normalize_total, log1p != 0, true, scale != 0, n_components + oversample, 2, D, extra);
     ExprFit F;
     expr_fit(w, D, n_components, oversample, n_iter, static_cast<u64>(seed), F);
     const int k = n_components;
     F.scores.download(scores, static_cast<size_t>(n) * k);
-    F.loadings.download(loadings, static_cast<size_t>(m) * k);
+    F.loadings.download(loadings, static_cast<size_t>(mk) * k);
     for (int j = 0; j < k; ++j) {
         singular_values[j] = F.s[j];
         sdev[j] = F.s[j] / std::sqrt(static_cast<double>(n - 1));
     }
-    D.mu.download(center, m);
-    D.sd.download(scale_out, m);
-    D.var.download(gene_var, m);
+    D.mu.download(center, mk);
+    D.sd.download(scale_out, mk);
+    D.var.download(gene_var, mk);
     *total_var = D.total_var;
     SHARP_API_END
 }
 
 int sharp_expr_stats_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks, int m,
                          double normalize_total, int log1p, double *mean, double *var, long long *nnz, double *cell_sum) {
+    return sharp_expr_stats_sub_csc(colptr, rowidx, val, ncb, nblocks, m, normalize_total, log1p, mean, var, nnz, cell_sum, nullptr, 0);
+}
+
+int sharp_expr_stats_sub_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks,
+                             int m, double normalize_total, int log1p, double *mean, double *var, long long *nnz, double *cell_sum,
+                             const int *genes, int n_genes) {
     SHARP_API_BEGIN
     const std::string w("gene_stats");
     SHARP_REQUIRE(mean && var && nnz && cell_sum, w + ": null output");
     const ExprBlocks B{colptr, rowidx, val, ncb, nblocks, m};
-    check_options(w, normalize_total, m);
-    SHARP_REQUIRE(total_cells(w, B) >= 2, w + ": need at least 2 cells in all");
+    expr_check_options(w, normalize_total, m);
+    SHARP_REQUIRE(expr_total_cells(w, B) >= 2, w + ": need at least 2 cells in all");
+    const int mk = expr_check_genes(w, genes, n_genes, m);
     ctx();
     ExprData D;
-    expr_load(w, B, normalize_total, log1p != 0, true, false, 0, 2, D);
-    D.mu.download(mean, m);
-    D.var.download(var, m);
-    D.gnnz.download(nnz, m);
-    hipLaunchKernelGGL(expr_cell_sums_kernel, dim3(wave_grid(D.n)), dim3(256), 0, ctx().stream, D.cptr.p, D.t.p, D.n, D.lsum.p);
-    launch_check("expr_cell_sums_kernel");
-    D.lsum.download(cell_sum, D.n);
+    ExprExtra extra;
+    extra.genes = genes;
+    extra.n_genes = n_genes;
+    extra.want_tsum = true;                                  // (over all genes, so before any subset)
+    expr_load(w, B, normalize_total, log1p != 0, true, false, 0, 2, D, extra);
+    D.mu.download(mean, mk);
+    D.var.download(var, mk);
+    D.gnnz.download(nnz, mk);
+    D.tsum.download(cell_sum, D.n);
     SHARP_API_END
 }
 
 int sharp_expr_pca_transform_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks,
                                  int m, double normalize_total, int log1p, const double *loadings, const double *center, const double *scale,
                                  int n_components, double *scores) {
+    return sharp_expr_pca_transform_sub_csc(colptr, rowidx, val, ncb, nblocks, m, normalize_total, log1p, loadings, center, scale, n_components,
+                                            scores, nullptr, 0);
+}
+
+int sharp_expr_pca_transform_sub_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb,
+                                     int nblocks, int m, double normalize_total, int log1p, const double *loadings, const double *center,
+                                     const double *scale, int n_components, double *scores, const int *genes, int n_genes) {
     SHARP_API_BEGIN
     const std::string w("expression_pca_transform");
     SHARP_REQUIRE(loadings && center && scale && scores, w + ": null loadings / center / scale / scores");
     const ExprBlocks B{colptr, rowidx, val, ncb, nblocks, m};
-    check_options(w, normalize_total, m);
-    const long long n = total_cells(w, B);
+    expr_check_options(w, normalize_total, m);
+    const long long n = expr_total_cells(w, B);
     SHARP_REQUIRE(n_components >= 1 && n_components <= kExprMaxL, w + ": need 1 <= n_components <= 128");
-    std::vector<double> wt(m);
-    for (int g = 0; g < m; ++g) {
+    const int mk = expr_check_genes(w, genes, n_genes, m);   // (loadings, center and scale have a row per kept gene)
+    std::vector<double> wt(mk);
+    for (int g = 0; g < mk; ++g) {
         SHARP_REQUIRE(std::isfinite(scale[g]) && scale[g] > 0.0 && std::isfinite(center[g]),
                       w + ": the fit's scale must be positive and its center finite (gene " + std::to_string(g) + ", counted from 0)");
         wt[g] = 1.0 / scale[g];
@@ -829,12 +950,15 @@ int sharp_expr_pca_transform_csc(const int *const *colptr, const int *const *row
     ctx();
     if (n == 0) return SHARP_OK;
     ExprData D;
-    expr_load(w, B, normalize_total, log1p != 0, false, false, n_components, 0, D);
+    ExprExtra extra;
+    extra.genes = genes;
+    extra.n_genes = n_genes;
+    expr_load(w, B, normalize_total, log1p != 0, false, false, n_components, 0, D, extra);
     const int k = n_components;
-    DevBuf<double> V(static_cast<size_t>(m) * k), mu(m), dw(m), Y(static_cast<size_t>(n) * k);
+    DevBuf<double> V(static_cast<size_t>(mk) * k), mu(mk), dw(mk), Y(static_cast<size_t>(n) * k);
     V.upload(loadings, V.n);
-    mu.upload(center, m);
-    dw.upload(wt.data(), m);
+    mu.upload(center, mk);
+    dw.upload(wt.data(), mk);
     expr_spmm_cells(D, mu.p, dw.p, V.p, k, Y.p);
     Y.download(scores, Y.n);
     SHARP_API_END
@@ -847,8 +971,8 @@ int sharp_expr_spmm_cells(const int *const *colptr, const int *const *rowidx, co
     SHARP_REQUIRE(Bm && Y, w + ": null B / Y");
     SHARP_REQUIRE(l >= 1 && l <= kExprMaxL, w + ": need 1 <= l <= 128 columns");
     const ExprBlocks B{colptr, rowidx, val, ncb, nblocks, m};
-    check_options(w, normalize_total, m);
-    SHARP_REQUIRE(total_cells(w, B) >= 2, w + ": need at least 2 cells in all");
+    expr_check_options(w, normalize_total, m);
+    SHARP_REQUIRE(expr_total_cells(w, B) >= 2, w + ": need at least 2 cells in all");
     ctx();
     ExprData D;
     expr_load(w, B, normalize_total, log1p != 0, true, scale != 0, l, 2, D);
@@ -866,8 +990,8 @@ int sharp_expr_spmm_genes(const int *const *colptr, const int *const *rowidx, co
     SHARP_REQUIRE(Q && Z, w + ": null Q / Z");
     SHARP_REQUIRE(l >= 1 && l <= kExprMaxL, w + ": need 1 <= l <= 128 columns");
     const ExprBlocks B{colptr, rowidx, val, ncb, nblocks, m};
-    check_options(w, normalize_total, m);
-    SHARP_REQUIRE(total_cells(w, B) >= 2, w + ": need at least 2 cells in all");
+    expr_check_options(w, normalize_total, m);
+    SHARP_REQUIRE(expr_total_cells(w, B) >= 2, w + ": need at least 2 cells in all");
     ctx();
     ExprData D;
     expr_load(w, B, normalize_total, log1p != 0, true, scale != 0, l, 2, D);

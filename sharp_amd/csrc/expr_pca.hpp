@@ -25,13 +25,23 @@ struct ExprBlocks {
     int nblocks, m;
 };
 
+// what expr_load does beyond §21's options
+struct ExprExtra {
+    const int *genes = nullptr;                  // keep these genes (strictly ascending, within [0, m)), renumbered by their position
+    int n_genes = 0;                             // (nullptr and 0: all genes)
+    bool refuse_negative = false;                // raw counts are expected: a negative value is refused without a transform too
+    bool want_tsum = false;                      // the cells' sums of the transformed values over all genes, into ExprData::tsum
+};
+
 struct ExprData {
     long long n = 0, nnz = 0, nch = 0;
-    int m = 0;
+    int m = 0;                                   // the genes of the copies below: the kept ones under a subset
+    int m_in = 0;                                // the genes of the blocks
     DevBuf<long long> cptr;                      // n + 1: a cell's entries
     DevBuf<int> ridx;                            // nnz: their genes, ascending within a cell
     DevBuf<double> t;                            // nnz: the transformed values
-    DevBuf<double> lsum;                         // n: the cells' sums before the transform
+    DevBuf<double> lsum;                         // n: the cells' sums before the transform, over all genes
+    DevBuf<double> tsum;                         // n: the cells' sums after it, over all genes (ExprExtra::want_tsum)
     DevBuf<long long> gptr;                      // m + 1: a gene's entries in the gene-major copy
     DevBuf<int> gcell;                           // nnz: their cells, ascending within a gene
     DevBuf<double> gval;                         // nnz
@@ -44,13 +54,31 @@ struct ExprData {
 
 // validates and uploads the blocks, transforms the values; genes: also the gene-major copy, the chunks and the statistics (scale: w = 1 /
 // sd).  l_work: the columns of the dense workspaces the caller will hold, for the refusal before anything is allocated.
+// extra.genes: the entries of the other genes are dropped after the transform (the cells' sums L_c are over all genes) and before the
+// gene-major copy is built; from there on D.m = extra.n_genes.
 void expr_load(const std::string &who, const ExprBlocks &B, double normalize_total, bool log1p, bool genes, bool scale, int l_work,
-               long long min_cells, ExprData &D);
+               long long min_cells, ExprData &D, const ExprExtra &extra = ExprExtra());
+// the genes kept of m: n_genes when `genes` is a strictly ascending list within [0, m), m for (nullptr, 0); anything else is refused by name
+int expr_check_genes(const std::string &who, const int *genes, int n_genes, int m);
+// the checks of the options and of the block list that need no device; the second returns the cells in all
+void expr_check_options(const std::string &who, double normalize_total, int m);
+long long expr_total_cells(const std::string &who, const ExprBlocks &B);
 // Y (n x l) = A Bm, Bm m x l on the device: Y[c, :] = sum over the cell's entries of t_gc w_g Bm[g, :] - mu^T diag(w) Bm
 void expr_spmm_cells(const ExprData &D, const double *mu, const double *w, const double *Bm, int l, double *Y);
 // Z (m x l) = A^T Q, Q n x l on the device
 void expr_spmm_genes(const ExprData &D, const double *Q, int l, double *Z);
 // Y (rows x l, device) -> Q with orthonormal columns, in place (CholeskyQR2)
 void expr_orth(const std::string &who, double *Y, long long rows, int l);
+
+
+// the entries [b, e) of chunk ch of gene g
+__device__ __forceinline__ void chunk_range(const long long *__restrict__ gptr, const long long *__restrict__ chptr, int g, long long ch,
+                                            long long &b, long long &e) {
+    b = gptr[g] + (ch - chptr[g]) * kExprChunk;
+    const long long ge = gptr[g + 1];
+    e = b + kExprChunk < ge ? b + kExprChunk : ge;
+}
+
+unsigned wave_grid(long long items);             // workgroups of four waves, one item per wave
 
 }  // namespace sharp

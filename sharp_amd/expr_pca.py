@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import SharpError, check, f64, i64, lib
+from ._lib import SharpError, check, f64, i32, i64, lib
 from .api import _csc_int_slots, _csc_pointer_lists, _is_sparse
 
 __all__ = ["expression_pca", "expression_pca_transform", "gene_stats"]
@@ -80,6 +80,33 @@ def _pointers(blocks):
     return _csc_pointer_lists(cps, ris, vxs) + (i64(ncb), len(blocks)), (cps, ris, vxs, ncb)
 
 
+def _genes(genes, m, who):
+    """genes= as the library takes it: (None, 0) for all genes, else (a strictly ascending int32 array within [0, m), its length); a bool
+    mask of length m stands for the indices it marks.  Unsorted, repeated, out-of-range and empty genes are refused by name."""
+    if genes is None:
+        return None, 0
+    g = np.asarray(genes)
+    if g.ndim != 1:
+        raise SharpError(f"{who}: genes must be a one-dimensional array of gene indices or a bool mask of length m")
+    if g.dtype == np.bool_:
+        if g.size != m:
+            raise SharpError(f"{who}: the genes mask has {g.size} entries, the blocks have {m} genes")
+        g = np.flatnonzero(g)
+    elif g.size and not np.issubdtype(g.dtype, np.integer):
+        raise SharpError(f"{who}: genes must hold integers or be a bool mask")
+    if g.size == 0:
+        raise SharpError(f"{who}: genes is empty (it must keep at least one gene)")
+    g = g.astype(np.int64)
+    if g.min() < 0 or g.max() >= m:
+        raise SharpError(f"{who}: genes holds an index outside [0, m) (position {int(np.flatnonzero((g < 0) | (g >= m))[0])}, counted from 0)")
+    d = np.diff(g)
+    if (d <= 0).any():                                          # (the first offending position decides the name, as in the library)
+        at = int(np.flatnonzero(d <= 0)[0])
+        what = "holds a gene twice" if d[at] == 0 else "must be ascending"
+        raise SharpError(f"{who}: genes {what} (position {at + 1}, counted from 0)")
+    return np.ascontiguousarray(g, np.int32), int(g.size)
+
+
 def _row_caps():
     """(the entries of a gene that one wave sums, the rows of a slab of the Gram): sharp_expr_row_caps; needs no device"""
     a, b = C.c_int(), C.c_int()
@@ -87,7 +114,8 @@ def _row_caps():
     return a.value, b.value
 
 
-def expression_pca(scExp, n_components=50, oversample=10, n_iter=4, normalize_total=1e4, log1p=True, center=True, scale=False, seed=0):
+def expression_pca(scExp, n_components=50, oversample=10, n_iter=4, normalize_total=1e4, log1p=True, center=True, scale=False, seed=0,
+                   genes=None):
     """The n_components leading principal components of the cells.  Each cell is scaled to normalize_total counts (None: not), log1p is
     taken (log1p=False: not), every gene is centred and, with scale, divided by its standard deviation (a constant gene gets weight 0).
     l = n_components + oversample columns (at most 128, at most min(cells, genes)) are iterated n_iter times; seed picks the start.
@@ -95,7 +123,10 @@ def expression_pca(scExp, n_components=50, oversample=10, n_iter=4, normalize_to
     take, and what expression_pca_transform gives for the same cells), "loadings" (genes x n_components, orthonormal columns, each
     one's largest entry positive), "singular_values", "sdev" (singular values / sqrt(cells -
     1)), "center", "scale" (1 without scale), "gene_var", "total_var", and the options}.  Input of rank below l is refused:
-    "numerical rank below n_components + oversample"."""
+    "numerical rank below n_components + oversample".
+    genes (strictly ascending indices, or a bool mask of length m; e.g. highly_variable_genes()["genes"]) fits the PCA on those genes
+    alone: the cells are normalised by their sums over ALL genes, then the other genes are dropped on the device.  loadings, center,
+    scale and gene_var then have one row per kept gene, and the fit carries "genes", "n_genes_in" (m) and "n_genes" (the kept)."""
     who = "expression_pca"
     if not center:
         raise SharpError(f"{who}: center = False is not supported (an uncentred variant is out of scope)")
@@ -114,24 +145,30 @@ def expression_pca(scExp, n_components=50, oversample=10, n_iter=4, normalize_to
     blocks, m, n = _blocks(scExp, who, total > 0 or log1p)
     if n < 2:
         raise SharpError(f"{who}: need at least 2 cells in all")
-    if k + oversample > min(n, m):
+    g, mk = _genes(genes, m, who)
+    mk = mk if g is not None else m
+    if k + oversample > min(n, mk):
         raise SharpError(f"{who}: n_components + oversample must be <= min(cells, genes)")
     _lib.ensure_init()
     args, keep = _pointers(blocks)
-    scores, loadings = np.zeros((n, k)), np.zeros((m, k))
-    sv, sdev, mu, sd, var, tv = np.zeros(k), np.zeros(k), np.zeros(m), np.zeros(m), np.zeros(m), C.c_double()
-    check(lib().sharp_expr_pca_csc(*args, m, k, oversample, n_iter, total, int(log1p), int(bool(scale)), seed, f64(scores), f64(loadings),
-                                   f64(sv), f64(sdev), f64(mu), f64(sd), f64(var), C.byref(tv)))
+    scores, loadings = np.zeros((n, k)), np.zeros((mk, k))
+    sv, sdev, mu, sd, var, tv = np.zeros(k), np.zeros(k), np.zeros(mk), np.zeros(mk), np.zeros(mk), C.c_double()
+    out = (f64(scores), f64(loadings), f64(sv), f64(sdev), f64(mu), f64(sd), f64(var), C.byref(tv))
+    if g is None:
+        check(lib().sharp_expr_pca_csc(*args, m, k, oversample, n_iter, total, int(log1p), int(bool(scale)), seed, *out))
+    else:
+        check(lib().sharp_expr_pca_sub_csc(*args, m, k, oversample, n_iter, total, int(log1p), int(bool(scale)), seed, *out, i32(g), mk))
     del keep
     return {"scores": scores, "loadings": loadings, "singular_values": sv, "sdev": sdev, "center": mu, "scale": sd, "gene_var": var,
             "total_var": tv.value, "n_components": k, "oversample": oversample, "n_iter": n_iter,
             "normalize_total": total if total > 0 else None, "log1p": log1p, "centered": True, "scaled": bool(scale), "seed": seed,
-            "n_cells": n, "n_genes": m}
+            "n_cells": n, "n_genes": mk, "n_genes_in": m, "genes": None if g is None else g.astype(np.int64)}
 
 
 def expression_pca_transform(scExp_new, fit):
     """The scores of new cells in a fit of expression_pca(): the cells go through the fit's transform, centre, scale and loadings.  A
-    cell's row depends on that cell and the fit alone, so block-wise calls give the bits of one call."""
+    cell's row depends on that cell and the fit alone, so block-wise calls give the bits of one call.  A fit on a gene subset
+    (fit["genes"]) takes new cells with all fit["n_genes_in"] genes and drops the others as the fit did."""
     who = "expression_pca_transform"
     try:
         V, mu, sd = (np.ascontiguousarray(fit[key], np.float64) for key in ("loadings", "center", "scale"))
@@ -141,31 +178,46 @@ def expression_pca_transform(scExp_new, fit):
     if V.ndim != 2 or mu.shape != (V.shape[0],) or sd.shape != (V.shape[0],) or not 1 <= V.shape[1] <= _MAX_L:
         raise SharpError(f"{who}: the fit's loadings, center and scale do not belong together")
     blocks, m, n = _blocks(scExp_new, who, total > 0 or log1p)
-    if m != V.shape[0]:
-        raise SharpError(f"{who}: the new cells have {m} genes, the fit has {V.shape[0]}")
+    sub = fit.get("genes") if hasattr(fit, "get") else None
+    m_fit = V.shape[0] if sub is None else fit.get("n_genes_in")
+    if sub is not None and (not isinstance(m_fit, (int, np.integer)) or m_fit < 1):
+        raise SharpError(f"{who}: fit must be what expression_pca() returned")
+    if m != m_fit:
+        raise SharpError(f"{who}: the new cells have {m} genes, the fit has {m_fit}")
+    g, mk = _genes(sub, m, who)
+    if g is not None and mk != V.shape[0]:
+        raise SharpError(f"{who}: the fit's loadings, center and scale do not belong together")
     k = V.shape[1]
     scores = np.zeros((n, k))
     if n == 0:
         return scores
     _lib.ensure_init()
     args, keep = _pointers(blocks)
-    check(lib().sharp_expr_pca_transform_csc(*args, m, total, int(log1p), f64(V), f64(mu), f64(sd), k, f64(scores)))
+    if g is None:
+        check(lib().sharp_expr_pca_transform_csc(*args, m, total, int(log1p), f64(V), f64(mu), f64(sd), k, f64(scores)))
+    else:
+        check(lib().sharp_expr_pca_transform_sub_csc(*args, m, total, int(log1p), f64(V), f64(mu), f64(sd), k, f64(scores), i32(g), mk))
     del keep
     return scores
 
 
-def gene_stats(scExp, normalize_total=1e4, log1p=True):
+def gene_stats(scExp, normalize_total=1e4, log1p=True, genes=None):
     """Per gene, after the transform of expression_pca(): {"mean", "var" (n - 1 in the denominator), "nnz" (cells with a non-zero
-    value)}, and per cell "cell_sum" -- what a caller needs to pick variable genes and subset the matrix before the PCA.  mean and var
-    are the fit's center and gene_var bit for bit."""
+    value)}, and per cell "cell_sum".  mean and var are the fit's center and gene_var bit for bit.  genes (as in expression_pca):
+    the statistics of those genes alone, the bits of the full call's rows; cell_sum stays the sum over all genes."""
     who = "gene_stats"
     total, log1p = _options(normalize_total, log1p, who)
     blocks, m, n = _blocks(scExp, who, total > 0 or log1p)
     if n < 2:
         raise SharpError(f"{who}: need at least 2 cells in all")
+    g, mk = _genes(genes, m, who)
+    mk = mk if g is not None else m
     _lib.ensure_init()
     args, keep = _pointers(blocks)
-    mu, var, nnz, cs = np.zeros(m), np.zeros(m), np.zeros(m, np.int64), np.zeros(n)
-    check(lib().sharp_expr_stats_csc(*args, m, total, int(log1p), f64(mu), f64(var), i64(nnz), f64(cs)))
+    mu, var, nnz, cs = np.zeros(mk), np.zeros(mk), np.zeros(mk, np.int64), np.zeros(n)
+    if g is None:
+        check(lib().sharp_expr_stats_csc(*args, m, total, int(log1p), f64(mu), f64(var), i64(nnz), f64(cs)))
+    else:
+        check(lib().sharp_expr_stats_sub_csc(*args, m, total, int(log1p), f64(mu), f64(var), i64(nnz), f64(cs), i32(g), mk))
     del keep
     return {"mean": mu, "var": var, "nnz": nnz, "cell_sum": cs, "normalize_total": total if total > 0 else None, "log1p": log1p}
