@@ -701,6 +701,34 @@ int sharp_expr_hvg_csc(const int *const *colptr, const int *const *rowidx, const
                        int *rank, int *highly_variable, int *genes, int *n_selected, int *q, int *degree_counts);
 int sharp_hvg_loess(const double *x, const double *y, int npts, double span, double *fit, double *bandwidth, int *degree);
 
+/* ---- batch integration of PCA scores (the specification is the project's own, modelled on Harmony) ---- */
+/* sharp_harmony: Z n x d (rows of d values, finite, no zero row; 2 <= d <= 128), batch the dense codes 0 .. n_batches - 1 (2 <= n_batches
+ * <= 4096, every code present), 2 <= n_clusters <= min(n, 256), sigma > 0, theta >= 0, lam > 0, 1 <= n_blocks <= 1024.  A soft k-means
+ * on the unit rows with a penalty on batch-pure clusters (up to max_iter_cluster rounds over n_blocks hashed blocks of cells), then a
+ * per-cluster ridge correction of the original Z, up to max_iter times.  Out: Z_corr (n x d, the caller's row order), Y (n_clusters x d),
+ * objective and rounds (max_iter slots each, n_iter filled), n_iter, converged, and R (n x n_clusters, or NULL).  Every sum's order is
+ * fixed by the input's shape: two calls give the same bits.
+ * Stage entries for the tests, every array in the caller's order:
+ * sharp_harmony_assign: for the cells [i0, i1), R[i, k] = exp(-(D_ik - min_k D_ik) / sigma) * P[batch[i], k] normalised over k, with
+ *   D_ik = 2 (1 - Y_k . Zhat_i) and P (n_batches x n_clusters) or NULL for 1; argmax != 0: a[i] = the k of the largest Y_k . Zhat_i (ties to
+ *   the lower k) instead.  The other rows of R / a are left as they are.
+ * sharp_harmony_sums: O (n_blocks x n_batches x n_clusters) = the per-block column sums of R by batch, with block(i) = h(0, i) mod
+ *   n_blocks of the seed; S (n_batches x n_clusters x d) = sum over the batch's cells of R[i, k] X[i, :].
+ * sharp_harmony_correct: Z_corr[i, :] = Z[i, :] - sum_k R[i, k] W[batch[i], k, :], W n_batches x n_clusters x d.
+ * sharp_harmony_ridge: W (n_batches x n_clusters x d) from N (n_batches x n_clusters, finite, >= 0) and S (n_batches x n_clusters x d):
+ *   the host function that the whole call runs between its sums and its correction, W_k = 0 where s <= 0; needs no device.
+ * sharp_harmony_caps: the cells of a slab of the sums and the doubles of Y that the assign kernel stages at a time; needs no device. */
+int sharp_harmony(const double *Z, long long n, int d, const int *batch, int n_batches, int n_clusters, double sigma, double theta, double lam,
+                  int max_iter, int max_iter_cluster, int n_blocks, double epsilon_cluster, double epsilon_harmony, int init_iter, long long seed,
+                  double *Z_corr, double *Y, double *objective, int *rounds, int *n_iter, int *converged, double *R);
+int sharp_harmony_assign(const double *Zhat, const double *Y, const int *batch, const double *P, long long n, int d, int K, int B, long long i0,
+                         long long i1, double sigma, int argmax, double *R, int *a);
+int sharp_harmony_sums(const double *R, const double *X, const int *batch, long long n, int d, int K, int B, long long seed, int n_blocks, double *O,
+                       double *S);
+int sharp_harmony_correct(const double *Z, const double *R, const int *batch, const double *W, long long n, int d, int K, int B, double *Z_corr);
+int sharp_harmony_ridge(const double *N, const double *S, int B, int K, int d, double lam, double *W);
+int sharp_harmony_caps(int *slab, int *lds_tile);
+
 /* ---- synthetic inputs (bench / tests; not part of the reference) ------------ */
 /* Counter-based generator, value = f(seed, gene, cell): bit-identical to
  * oracle_synth_value().  Fills dX (fp32, m x ncell column-major, leading dim ld). */
@@ -912,6 +940,12 @@ void sharp_C_expr_pca_transform_sub_csc(int *pcat, int *icat, double *xcat, int 
 void sharp_C_expr_hvg_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, int *n_top_genes, double *span, double *means,
                           double *variances, double *variances_expected, double *variances_norm, int *rank, int *highly_variable, int *genes,
                           int *n_selected, int *q, int *degree_counts, int *status);
+/* sharp_harmony in the same convention: Z = as.double(t(Z)) (rows of d values), n and seed as double, batch 0-based; *want_R = 0: R is a
+ * buffer of length >= 1 that is left alone */
+void sharp_C_harmony(double *Z, double *n, int *d, int *batch, int *n_batches, int *n_clusters, double *sigma, double *theta, double *lam,
+                     int *max_iter, int *max_iter_cluster, int *n_blocks, double *epsilon_cluster, double *epsilon_harmony, int *init_iter,
+                     double *seed, double *Z_corr, double *Y, double *objective, int *rounds, int *n_iter, int *converged, int *want_R, double *R,
+                     int *status);
 
 #ifdef __cplusplus
 }

@@ -878,6 +878,33 @@ sharp_gene_stats_genes <- function(scExp, genes, normalize.total = 1e4, log1p = 
     list(mean = r$mean, var = r$var, nnz = r$nnz, cell.sum = r$cell_sum)
 }
 
+# A Harmony-style batch integration of PCA scores (DESIGN.md 23): Z cells x d (what sharp_expression_pca's $scores holds), batch one
+# label per cell of any kind (factor() orders them).  list(Z.corr (cells x d, Z's row order), Y (n.clusters x d), objective, rounds, n.iter,
+# converged, n.clusters, n.batches, batch.levels, and R (cells x n.clusters) with ret.R).  Nothing here is an index, so nothing is 1-based.
+sharp_harmony <- function(Z, batch, n.clusters = NULL, sigma = 0.1, theta = 2, lam = 1, max.iter = 10L, max.iter.cluster = 20L,
+                          n.blocks = 20L, epsilon.cluster = 1e-5, epsilon.harmony = 1e-4, init.iter = 10L, seed = 1, ret.R = FALSE) {
+    Z <- as.matrix(Z)
+    n <- nrow(Z); d <- ncol(Z)
+    if (length(batch) != n) stop("sharp_harmony: batch must hold one label per cell")
+    f <- factor(batch)
+    B <- nlevels(f)
+    K <- as.integer(if (is.null(n.clusters)) min(round(n / 30), 100) else n.clusters)
+    it <- as.integer(max.iter)
+    r <- .C("sharp_C_harmony", as.double(t(Z)), as.double(n), as.integer(d), as.integer(f) - 1L, as.integer(B), K, as.double(sigma),
+            as.double(theta), as.double(lam), it, as.integer(max.iter.cluster), as.integer(n.blocks), as.double(epsilon.cluster),
+            as.double(epsilon.harmony), as.integer(init.iter), as.double(seed), Zc = double(n * d), Y = double(max(K, 1L) * d),
+            objective = double(max(it, 1L)), rounds = integer(max(it, 1L)), n_iter = integer(1), converged = integer(1), as.integer(ret.R),
+            R = double(if (ret.R) n * max(K, 1L) else 1L), status = integer(1))
+    .sharp_check(r$status)
+    out <- list(Z.corr = t(matrix(r$Zc, nrow = d)), Y = t(matrix(r$Y, nrow = d)), objective = r$objective[seq_len(r$n_iter)],
+                rounds = r$rounds[seq_len(r$n_iter)], n.iter = r$n_iter, converged = r$converged != 0L, n.clusters = K, n.batches = B,
+                batch.levels = levels(f))
+    if (ret.R) out$R <- t(matrix(r$R, nrow = K))
+    out
+}
+# the block number of every cell of a list of genes x cells blocks, in sharp_expression_pca's order: the batch of sharp_harmony
+sharp_batch_of_blocks <- function(blocks) rep(seq_along(blocks), vapply(blocks, ncol, 1L))
+
 # the same on any symmetric graph: a dgCMatrix-like triple (row_ptr 0-based with n + 1 values, col 0-based, val)
 sharp_louvain_graph <- function(row_ptr, col, val, resolution = 1, seed = 10, tol = 1e-7, max_levels = 20L, max_rounds = 200L,
                                 max_fails = 4L, ret_levels = FALSE) {

@@ -522,4 +522,14 @@ void sharp_C_expr_hvg_csc(int *pcat, int *icat, double *xcat, int *nblocks, doub
                                  variances_expected, variances_norm, rank, highly_variable, genes, n_selected, q, degree_counts);
 }
 
+/* The batch integration of PCA scores: the plain entry's bits */
+void sharp_C_harmony(double *Z, double *n, int *d, int *batch, int *n_batches, int *n_clusters, double *sigma, double *theta, double *lam,
+                     int *max_iter, int *max_iter_cluster, int *n_blocks, double *epsilon_cluster, double *epsilon_harmony, int *init_iter,
+                     double *seed, double *Z_corr, double *Y, double *objective, int *rounds, int *n_iter, int *converged, int *want_R, double *R,
+                     int *status) {
+    *status = sharp_harmony(Z, as_ll(n), *d, batch, *n_batches, *n_clusters, *sigma, *theta, *lam, *max_iter, *max_iter_cluster, *n_blocks,
+                            *epsilon_cluster, *epsilon_harmony, *init_iter, as_ll(seed), Z_corr, Y, objective, rounds, n_iter, converged,
+                            *want_R ? R : nullptr);
+}
+
 }  // extern "C"
