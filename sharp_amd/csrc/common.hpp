@@ -48,6 +48,13 @@ void set_error(const std::string &msg);
         return SHARP_ERR;                                    \
     }                                                        \
     return SHARP_OK;
+// What an entry point does before or after its guarded body (an upload, a device list), under the same guard: SHARP_OK, or the
+// error's code with its text in sharp_last_error().
+inline int api_guarded(const std::function<void()> &step) {
+    SHARP_API_BEGIN
+    step();
+    SHARP_API_END
+}
 
 // An expression block resident in HBM: genes x cells, column-major (a cell is a contiguous vector of ld values), stored as fp32
 // (counts and every other fp32-exact input: half the bytes of the one pass over X) or as fp64 (TPM / CPM-like doubles, which fp32
