@@ -763,6 +763,37 @@ int sharp_gemm_tn_f64_batch(int count, const int *M, const int *N, const int *K,
 int sharp_row_prep_batch(int count, const int *n, const int *p, const long long *lds, const int *mode, const double *src,
                          int all_feature_rows, double *Cr, double *Ct, double *nrm, double *D);
 
+/* Test entry for a whole BATCH of get_opt_hclust tasks (tests/test_hclust_batch_gpu.py): ONE call of the batch driver that every base
+ * clustering, wMetaC and sMetaC goes through, over `count` tasks given as parallel arrays.  Task t is the n[t] x p[t] row-major matrix
+ * that follows its predecessors' n x p values in mats; kind[t] says what it is (0 feature rows, 1 symmetric similarity with p == n; no
+ * guess is made); hmethod .. height_Ntimes as sharp_get_opt_hclust takes them, per task and without defaults.  Every matrix is uploaded
+ * to a device buffer of its own.
+ * Outputs, each concatenated in task order with nk_t = 1 where N_cluster[t] > 0, else max(1, min(maxN, n - 1) - minN + 1):
+ * f (sum n), v (sum nk n, level-major per task; only with want_v, else it may be null), msil and CHind (sum nk), height (sum (n - 1)),
+ * and per task optN, nk, branch, rc (0 or SHARP_WARN_RANGE) and sequential (1: the sequential agglomeration kernel did the task,
+ * 0: the bulk-synchronous one).  Every output is filled with the sentinel before the call -- the NaN of the linalg batch entries for
+ * doubles, INT_MIN for ints -- so what the batch did not write shows.  Where N_cluster[t] > 0, CHind keeps the NaN the batch leaves
+ * (the Euclidean index is sharp_get_opt_hclust's own work) and optN is the largest label.
+ * nested: every output array holds TWO sets, one after the other.  The second receives the same tasks run again as batches started
+ * from the first batch's progress callback -- the tasks reported finished since the previous callback, while later chunks are in
+ * flight -- which is how a fold's wMetaC runs inside SHARP_large.  The tasks of the last chunk are never reported that way: their
+ * entries of the second set keep the sentinel, as does the whole set when the batch is one chunk.  Refused for count > 4 x CUs.
+ *
+ * sharp_hclust_batch_plan: what the calling context's last batch did (any caller's, not only the entry's), one row of 16 ints per
+ * chunk in the order the chunks were set up: 0 i0, 1 i1 (tasks [i0, i1)), 2 slot (set of buffers), 3 pipe (one of several chunks in
+ * flight), 4 split (the chunk asked for the round-per-launch agglomeration), 5 NS (ranges, each on its own stream), 6 ml (many-levels
+ * statistics), 7 max_n, 8 max_kpad, 9 the sequential fallback was deferred to the statistics phase, 10 form of the bulk-synchronous
+ * agglomeration (0 none: sequential kernel only, 1 round per launch, 2 one launch of 1024 threads, 3 one launch of 512 threads, 4 an
+ * experiment of the lab build),
+ * 11 gs (state in global memory: max_n > 4096), 12 nested (started from another batch's progress callback; i0, i1 count within that
+ * batch), 13 max_nk, and for form 1 (else 0) 14 wpt (workgroups per task in the rebuild launches; SHARP_HC_WPT) and 15 finish_at (the
+ * round from which one launch finishes the rest, -1 never; SHARP_HC_FINISH_AT).  rows receives at most cap_rows rows, *n_rows the number held.  Written on the host; no device work. */
+int sharp_get_opt_hclust_batch(int count, const int *n, const int *p, const int *kind, const int *hmethod, const int *N_cluster,
+                               const int *minN, const int *maxN, const double *sil_thre, const double *height_Ntimes, const double *mats,
+                               int want_v, int nested, int *f, int *v, double *msil, double *CHind, double *height, int *optN, int *nk,
+                               int *branch, int *rc, int *sequential);
+int sharp_hclust_batch_plan(int *rows, int cap_rows, int *n_rows);
+
 /* ---- device memory helpers for non-torch hosts (R glue, tests) -------------- */
 int sharp_dev_alloc(long long bytes, void **dptr);
 int sharp_dev_free(void *dptr);

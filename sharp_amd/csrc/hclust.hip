@@ -8,7 +8,10 @@
 #include "hclust_task.hpp"
 
 #include <algorithm>
+#include <array>
+#include <climits>
 #include <cmath>
+#include <cstring>
 #include <limits>
 
 #include "linalg.hpp"
@@ -111,6 +114,7 @@ struct ChunkJob {
     bool one_range = false;                    // everything on the current stream (a batch prepared ahead of time, hc_prefetch_begin)
     int scratch_slot = 0;                      // whose S0 / S1 / img / remaining the agglomeration uses (set 0 unless the batch is nested)
     int prev_slot = 1, next_slot = 1;          // pipelined: the slots of the chunk before and after this one (two or three slots in rotation)
+    int plan_row = -1;                         // this chunk's row of the slot's plan record (plan_add), -1: not recorded
     int next2_slot = -1;                       // three slots: the chunk after the next, whose distance GEMM the statistics also let pass
     hipEvent_t mid_event = nullptr;            // recorded behind round `mid_round` of the round-per-launch agglomeration (if it gets that far)
     int mid_round = 8;
@@ -135,6 +139,18 @@ PipeEvents &pipe_events() {
         }
     }
     return e;
+}
+
+// What the last get_opt_hclust_batch of the calling slot did, one row per chunk (sharp_hclust_batch_plan; include/sharp_hip.h names the
+// columns): written on the host as the chunks are set up and their agglomeration is enqueued, no device work.  A batch started from the
+// progress callback of another adds its row (nested = 1) to the outer batch's record.
+struct BatchPlan { std::vector<std::array<int, kHcPlanCols>> rows; };
+BatchPlan &batch_plan() { return per_slot<BatchPlan>(); }
+void plan_add(ChunkJob &J, bool nested) {
+    std::vector<std::array<int, kHcPlanCols>> &rows = batch_plan().rows;
+    J.plan_row = static_cast<int>(rows.size());
+    rows.push_back({static_cast<int>(J.i0), static_cast<int>(J.i1), J.slot, J.pipe, J.split, J.NS, J.ml, J.max_n, J.max_kpad, 0, 0,
+                    J.max_n > HR_MAXN, nested, J.max_nk, 0, 0});
 }
 
 // Descriptors, workspace and uploads of a chunk (before its first phase).
@@ -394,12 +410,17 @@ void enqueue_chunk(ChunkJob &J, int phases) {
         {
             const bool use_rnn = !knobs().hc_seq;
             KernelTimer tm("hclust");
-            if (use_rnn && hclust_bulk_synchronous(agglo, J.split, W0.img, W0.remaining, J.mid_event, J.mid_round)) J.mid_recorded = true;
+            HcAggloDid did;
+            if (use_rnn && hclust_bulk_synchronous(agglo, J.split, W0.img, W0.remaining, J.mid_event, J.mid_round, &did)) J.mid_recorded = true;
             // When the sequential kernel is only the fallback, a pipelined chunk with a successor launches it with its statistics
             // phase: its (normally idle) workgroups would otherwise take CU slots from the successor's distance GEMM, which is on the
             // critical path.
             if (!use_rnn || !(J.pipe && J.has_next)) launch_sequential(use_rnn);
             else J.seq_pending = true;
+            if (J.plan_row >= 0 && s == 0) {                // (the ranges of a chunk are equal to within one task: the first one's form)
+                std::array<int, kHcPlanCols> &row = batch_plan().rows[J.plan_row];
+                row[9] = J.seq_pending; row[10] = did.form; row[14] = did.wpt; row[15] = did.finish_at;
+            }
         }
         if (J.pipe) SHARP_HIP_CHECK(hipEventRecord(EV.hc[J.slot], st));
         if (J.pipe && knobs().step_marks)
@@ -428,7 +449,7 @@ void enqueue_chunk(ChunkJob &J, int phases) {
         SHARP_HIP_CHECK(hipLaunchHostFunc(chunk_stream, [](void *) { step_mark("    (device) a chunk's statistics end"); }, nullptr));
 }
 
-void finish_chunk(const std::vector<HcTask> &tasks, ChunkJob &J, bool want_v, std::vector<HcResult> &out) {
+void finish_chunk(const std::vector<HcTask> &tasks, ChunkJob &J, bool want_v, std::vector<HcResult> &out, bool want_status) {
     Ctx &c = ctx();
     Workspace &W = ws(J.slot);
     const size_t i0 = J.i0;
@@ -438,16 +459,16 @@ void finish_chunk(const std::vector<HcTask> &tasks, ChunkJob &J, bool want_v, st
     if (J.pipe) SHARP_HIP_CHECK(hipStreamWaitEvent(c.stream, pipe_events().done[J.slot], 0));
     W.h_out.ensure(std::max<long long>(oOut, 1)); W.h_height.ensure(std::max<long long>(oM, 1));
     double *h_out = W.h_out.p, *h_height = W.h_height.p;
-    if (c.profiling) {      // which agglomeration kernel did the work (tests assert on it)
-        int fallback = T;
-        if (!knobs().hc_seq) {
-            std::vector<int> st(T);
-            W.status.download(st.data(), T);
-            fallback = 0;
-            for (int v : st) fallback += v != 0;
+    if (c.profiling || want_status) {      // which agglomeration kernel did the work (tests assert on it)
+        std::vector<int> st(T, 1);
+        if (!knobs().hc_seq) W.status.download(st.data(), T);
+        int fallback = 0;
+        for (int v : st) fallback += v != 0;
+        if (c.profiling) {
+            c.stats["host:hclust_tasks_bulk_synchronous"].launches += T - fallback;
+            c.stats["host:hclust_tasks_sequential"].launches += fallback;
         }
-        c.stats["host:hclust_tasks_bulk_synchronous"].launches += T - fallback;
-        c.stats["host:hclust_tasks_sequential"].launches += fallback;
+        if (want_status) for (int t = 0; t < T; ++t) out[i0 + t].sequential = st[t] != 0;
     }
     HostTimer ht_tail("hc_download_select");
     W.out.download(h_out, oOut);
@@ -514,12 +535,18 @@ struct AfterAgglo { std::function<void(hipEvent_t)> fn; bool fired = false; };
 AfterAgglo &after_agglo() { return per_slot<AfterAgglo>(); }
 }  // namespace
 void hc_release_workspaces() { release_workspaces_of_slot(); }
+int hc_batch_plan_fetch(int *rows, int cap_rows) {
+    const std::vector<std::array<int, kHcPlanCols>> &have = batch_plan().rows;
+    for (size_t r = 0; r < have.size() && r < static_cast<size_t>(cap_rows); ++r) std::copy(have[r].begin(), have[r].end(), rows + r * kHcPlanCols);
+    return static_cast<int>(have.size());
+}
 void hc_set_after_last_agglomeration(std::function<void(hipEvent_t)> fn) { after_agglo().fn = std::move(fn); after_agglo().fired = false; }
 bool hc_after_last_agglomeration_fired() { return after_agglo().fired; }
 
 void get_opt_hclust_batch(const std::vector<HcTask> &tasks, bool want_v, std::vector<HcResult> &out,
-                          const std::function<void(size_t)> *progress, const std::function<hipEvent_t(size_t)> *prepare) {
+                          const std::function<void(size_t)> *progress, const std::function<hipEvent_t(size_t)> *prepare, bool want_status) {
     out.assign(tasks.size(), HcResult());
+    if (g_batch_depth == 0) batch_plan().rows.clear();
     if (tasks.empty()) return;
     ctx();
     if (g_batch_depth > 0) {
@@ -531,8 +558,9 @@ void get_opt_hclust_batch(const std::vector<HcTask> &tasks, bool want_v, std::ve
         J.i0 = 0; J.i1 = tasks.size();
         J.slot = 2; J.scratch_slot = 2; J.one_range = true;
         setup_chunk(tasks, J);
+        plan_add(J, true);
         enqueue_chunk(J, PH_ALL);
-        finish_chunk(tasks, J, want_v, out);
+        finish_chunk(tasks, J, want_v, out, want_status);
         return;
     }
     size_t free_b = 0, total_b = 0;
@@ -597,9 +625,9 @@ void get_opt_hclust_batch(const std::vector<HcTask> &tasks, bool want_v, std::ve
         for (const auto &b : bounds) {
             ChunkJob J;
             J.i0 = b.first; J.i1 = b.second;
-            { HostTimer ht("hc_single_setup"); setup_chunk(tasks, J); }
+            { HostTimer ht("hc_single_setup"); setup_chunk(tasks, J); plan_add(J, false); }
             { HostTimer ht("hc_single_enqueue"); enqueue_chunk(J, PH_ALL); }
-            { HostTimer ht("hc_single_finish"); finish_chunk(tasks, J, want_v, out); }
+            { HostTimer ht("hc_single_finish"); finish_chunk(tasks, J, want_v, out, want_status); }
         }
         return;
     }
@@ -620,7 +648,7 @@ void get_opt_hclust_batch(const std::vector<HcTask> &tasks, bool want_v, std::ve
     ChunkJob jobs[3];
     size_t fetched = 0;                                                     // chunks 0 .. fetched - 1 are finished
     auto fetch_upto = [&](size_t upto) {                                    // finish chunks in order, report
-        for (; fetched < upto; ++fetched) { finish_chunk(tasks, jobs[fetched % R], want_v, out); step_mark("chunk fetched", static_cast<int>(fetched)); }
+        for (; fetched < upto; ++fetched) { finish_chunk(tasks, jobs[fetched % R], want_v, out, want_status); step_mark("chunk fetched", static_cast<int>(fetched)); }
     };
     auto start_chunk = [&](size_t j) {                                      // descriptors, uploads, rows and distance matrices of chunk j
         ChunkJob &J = jobs[j % R];
@@ -630,6 +658,7 @@ void get_opt_hclust_batch(const std::vector<HcTask> &tasks, bool want_v, std::ve
         J.pipe = true; J.first = j == 0; J.has_next = j + 1 < nb;
         if (prepare) J.input_ready = (*prepare)(J.i1);                    // (whatever prepare_ahead has not asked for already)
         setup_chunk(tasks, J);
+        plan_add(J, false);
         enqueue_chunk(J, PH_DIST);
     };
     const bool stats_last = R == 3;
@@ -723,7 +752,7 @@ void hc_prefetch_finish(HcPrefetch &P, bool want_v, std::vector<HcResult> &out) 
     out.assign(P.tasks.size(), HcResult());
     if (!P.agglo_enqueued) hc_prefetch_agglomerate(P);
     enqueue_chunk(P.J, PH_STATS);
-    finish_chunk(P.tasks, P.J, want_v, out);
+    finish_chunk(P.tasks, P.J, want_v, out, false);
 }
 
 // stats::hclust alone: one distance task through setup_chunk / enqueue_chunk (rows copied as they are, agglomeration), no statistics
@@ -838,6 +867,93 @@ int sharp_get_opt_hclust(const double *mat, int n, int p, int hmethod, int N_clu
     catch (const sharp::Error &e) { sharp::set_error(e.what()); return e.code; }
     catch (const std::exception &e) { sharp::set_error(e.what()); return SHARP_ERR; }
     return warn;
+}
+
+/* Test entry: `count` tasks through ONE get_opt_hclust_batch call (include/sharp_hip.h). */
+int sharp_get_opt_hclust_batch(int count, const int *n, const int *p, const int *kind, const int *hmethod, const int *N_cluster,
+                               const int *minN, const int *maxN, const double *sil_thre, const double *height_Ntimes, const double *mats,
+                               int want_v, int nested, int *f, int *v, double *msil, double *CHind, double *height, int *optN, int *nk,
+                               int *branch, int *rc, int *sequential) {
+    SHARP_API_BEGIN
+    ctx();
+    const std::string w = "sharp_get_opt_hclust_batch";
+    SHARP_REQUIRE(count >= 1, w + ": count must be at least 1");
+    SHARP_REQUIRE(n && p && kind && hmethod && N_cluster && minN && maxN && sil_thre && height_Ntimes && mats, w + ": null input");
+    SHARP_REQUIRE(f && msil && CHind && height && optN && nk && branch && rc && sequential && (v || !want_v), w + ": null output");
+    SHARP_REQUIRE(!nested || static_cast<size_t>(count) <= static_cast<size_t>(ctx().num_cu) * 4, w + ": nested needs count <= 4 * CUs");
+    // offsets of every task in the matrices and in each output; the sets of outputs (two with `nested`) follow one another
+    std::vector<size_t> oMat(count + 1, 0), oF(count + 1, 0), oV(count + 1, 0), oK(count + 1, 0), oH(count + 1, 0);
+    for (int t = 0; t < count; ++t) {
+        SHARP_REQUIRE(n[t] >= 1 && p[t] >= 1, w + ": n and p of every task must be at least 1");
+        SHARP_REQUIRE(kind[t] == 0 || (kind[t] == 1 && p[t] == n[t]), w + ": kind must be 0 (feature rows) or 1 (similarity, p == n)");
+        const int nk_t = N_cluster[t] > 0 ? 1 : std::max(1, std::min(maxN[t], n[t] - 1) - minN[t] + 1);
+        oMat[t + 1] = oMat[t] + static_cast<size_t>(n[t]) * p[t];
+        oF[t + 1] = oF[t] + n[t];
+        oV[t + 1] = oV[t] + static_cast<size_t>(nk_t) * n[t];
+        oK[t + 1] = oK[t] + nk_t;
+        oH[t + 1] = oH[t] + n[t] - 1;
+    }
+    const size_t sets = nested ? 2 : 1;
+    double nan_sentinel;
+    const unsigned long long bits = 0x7ff8c0de5eed0001ULL;     // (the sentinel of the linalg batch entries)
+    std::memcpy(&nan_sentinel, &bits, sizeof bits);
+    std::fill_n(f, sets * oF[count], INT_MIN);
+    if (want_v) std::fill_n(v, sets * oV[count], INT_MIN);
+    std::fill_n(msil, sets * oK[count], nan_sentinel);
+    std::fill_n(CHind, sets * oK[count], nan_sentinel);
+    std::fill_n(height, sets * oH[count], nan_sentinel);
+    for (int *o : {optN, nk, branch, rc, sequential}) std::fill_n(o, sets * count, INT_MIN);
+    // every matrix in a device buffer of its own, as sharp_get_opt_hclust uploads its one
+    std::vector<DevBuf<double>> dm(count);
+    std::vector<HcTask> tasks(count);
+    for (int t = 0; t < count; ++t) {
+        dm[t].alloc(oMat[t + 1] - oMat[t]);
+        dm[t].upload(mats + oMat[t], oMat[t + 1] - oMat[t]);
+        HcTask &tk = tasks[t];
+        tk.d_mat = dm[t].p; tk.n = n[t]; tk.p = p[t]; tk.ld = p[t];
+        tk.symmetric = kind[t] == 1;
+        tk.prm.hmethod = hmethod[t]; tk.prm.N_cluster = N_cluster[t]; tk.prm.minN = minN[t]; tk.prm.maxN = maxN[t];
+        tk.prm.sil_thre = sil_thre[t]; tk.prm.height_Ntimes = height_Ntimes[t];
+    }
+    // results of tasks [t0, t0 + res.size()) into output set `set`: what a result does not hold stays the sentinel
+    auto store = [&](const std::vector<HcResult> &res, size_t t0, size_t set) {
+        for (size_t i = 0; i < res.size(); ++i) {
+            const HcResult &R = res[i];
+            const size_t t = t0 + i;
+            auto fits = [](size_t have, size_t room) { return std::min(have, room); };
+            std::copy_n(R.f.begin(), fits(R.f.size(), oF[t + 1] - oF[t]), f + set * oF[count] + oF[t]);
+            if (want_v) std::copy_n(R.v.begin(), fits(R.v.size(), oV[t + 1] - oV[t]), v + set * oV[count] + oV[t]);
+            std::copy_n(R.msil.begin(), fits(R.msil.size(), oK[t + 1] - oK[t]), msil + set * oK[count] + oK[t]);
+            std::copy_n(R.CHind.begin(), fits(R.CHind.size(), oK[t + 1] - oK[t]), CHind + set * oK[count] + oK[t]);
+            std::copy_n(R.height.begin(), fits(R.height.size(), oH[t + 1] - oH[t]), height + set * oH[count] + oH[t]);
+            const size_t o = set * count + t;
+            if (R.f.empty()) continue;                      // (a task the batch never reached)
+            optN[o] = R.optN; nk[o] = R.nk; branch[o] = R.branch; rc[o] = R.rc;
+            if (R.sequential >= 0) sequential[o] = R.sequential;
+        }
+    };
+    std::vector<HcResult> res;
+    // nested: the tasks that the outer batch reports finished run again, from its progress callback, as a batch of their own (slot 2)
+    size_t redone = 0;
+    const std::function<void(size_t)> progress = [&](size_t done) {
+        if (done <= redone) return;
+        std::vector<HcTask> part(tasks.begin() + redone, tasks.begin() + done);
+        std::vector<HcResult> again;
+        get_opt_hclust_batch(part, want_v != 0, again, nullptr, nullptr, true);
+        store(again, redone, 1);
+        redone = done;
+    };
+    get_opt_hclust_batch(tasks, want_v != 0, res, nested ? &progress : nullptr, nullptr, true);
+    store(res, 0, 0);
+    stream_sync();                                          // (dm goes away)
+    SHARP_API_END
+}
+
+int sharp_hclust_batch_plan(int *rows, int cap_rows, int *n_rows) {
+    SHARP_API_BEGIN
+    SHARP_REQUIRE(n_rows && (rows || cap_rows == 0) && cap_rows >= 0, "sharp_hclust_batch_plan: null argument");
+    *n_rows = hc_batch_plan_fetch(rows, cap_rows);
+    SHARP_API_END
 }
 
 /* the decision log (hclust.hpp says what a row holds) */

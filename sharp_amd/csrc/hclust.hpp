@@ -58,6 +58,7 @@ struct HcResult {
     std::vector<double> msil, CHind, height;
     double maxsil = 0;
     int optN = 0, nk = 0, branch = 0;
+    int sequential = -1;      // (only with want_status) 1: the sequential kernel did the task, 0: the bulk-synchronous one
 };
 
 // Observations per clustering task.  Up to kHcLdsMaxN (sequential kernel) / 4096 (bulk-synchronous kernel) the agglomeration state
@@ -73,9 +74,16 @@ constexpr int kHcMaxN = 16384;
 // prepare (optional; pipelined chunks only): called on the calling thread before a chunk's work is enqueued, with the number of leading
 // tasks whose inputs that chunk needs; it enqueues whatever still has to produce them (on the caller's stream) and returns the event behind
 // it, which the chunk's stream waits for.  Without it every chunk waits for the caller's stream as it stands at the call.
+// want_status (the test entry sharp_get_opt_hclust_batch): every chunk's per-task status also comes back (HcResult::sequential), one more
+// small download per chunk, which the production callers do not ask for.
 void get_opt_hclust_batch(const std::vector<HcTask> &tasks, bool want_v, std::vector<HcResult> &out,
                           const std::function<void(size_t)> *progress = nullptr,
-                          const std::function<hipEvent_t(size_t)> *prepare = nullptr);
+                          const std::function<hipEvent_t(size_t)> *prepare = nullptr, bool want_status = false);
+
+// The plan record: what the calling slot's last get_opt_hclust_batch did, one row of kHcPlanCols ints per chunk in the order the chunks
+// were set up (columns: include/sharp_hip.h, sharp_hclust_batch_plan).  Host only.
+constexpr int kHcPlanCols = 16;
+int hc_batch_plan_fetch(int *rows, int cap_rows);      // copies at most cap_rows rows; returns the number of rows held
 
 // One-shot hook for the NEXT get_opt_hclust_batch call of this device slot that runs as pipelined chunks: fn(ev) is called once, on the
 // host, right after the LAST chunk's agglomeration has been enqueued; ev is recorded behind that agglomeration.  For work that needs

@@ -1025,7 +1025,7 @@ void launch_rnn(K kern, dim3 grid, int threads, size_t lds_launch, const HcAgglo
 // matrices, D stays pristine); whatever it abandons (exact ties, centroid/median, n > 4096) is done by the
 // sequential NN-list kernel, which skips the tasks whose status is 0 -- no host round trip in between.
 bool hclust_bulk_synchronous(const HcAggloRange &r, bool split_chunk, DevBuf<unsigned char> &img, DevBuf<int> &remaining,
-                             hipEvent_t mid_event, int mid_round) {
+                             hipEvent_t mid_event, int mid_round, HcAggloDid *did) {
     Ctx &c = ctx();
     hipStream_t st = c.stream;
     const int Ts = r.tasks, max_n = r.max_n;
@@ -1039,6 +1039,7 @@ bool hclust_bulk_synchronous(const HcAggloRange &r, bool split_chunk, DevBuf<uns
     // then at its memory limit either way and the per-round launches only add their gaps).  SHARP_HC_SPLIT = 1 / 0 forces
     // the choice; it is made for the whole chunk (a range of a larger chunk stays one launch).
     const bool split = split_chunk || gs;
+    if (did) did->form = (!mono || gs) && split ? 1 : 4;
     if ((!mono || gs) && split) {
         // workgroups per task in the rebuild launches: eight when there are tens of tasks (measured, 25 - 136 tasks of 2000);
         // a lone big task (a per-block or cross-block sMetaC of thousands of clusters) gets up to a quarter of the chip
@@ -1060,6 +1061,7 @@ bool hclust_bulk_synchronous(const HcAggloRange &r, bool split_chunk, DevBuf<uns
         const int max_rounds = max_n + 8;               // every round merges at least one pair
         // after `finish_at` rounds (about a quarter of the clusters left at the usual 10 % per round) the rest runs in ONE launch
         const int finish_at = knobs().hc_finish_at;
+        if (did) { did->wpt = wpt; did->finish_at = finish_at >= 0 ? finish_at : -1; }
         auto kc = gs ? hclust_rnn_kernel<1024, 3, true> : hclust_rnn_kernel<1024, 3, false>;
         if (finish_at >= 0) allow_dynamic_lds(kc, ldsl);
         for (int round = 0; round < max_rounds; ++round) {
@@ -1110,6 +1112,7 @@ bool hclust_bulk_synchronous(const HcAggloRange &r, bool split_chunk, DevBuf<uns
 #endif
     } else if (Ts <= c.num_cu && !knobs().hc_half) {
         auto k0 = hclust_rnn_kernel<1024, 0>;
+        if (did) did->form = 2;
         // one workgroup per CU: everything the CU has beyond the state stages the pair members' entries
         const size_t ldsl = std::max(lds, HR_LDS_CU);
         allow_dynamic_lds(k0, ldsl);
@@ -1118,6 +1121,7 @@ bool hclust_bulk_synchronous(const HcAggloRange &r, bool split_chunk, DevBuf<uns
         // (also SHARP_HC_HALF=1 with at most one task per CU: the eight-wave form then leaves half of every CU's registers and LDS to a
         // workgroup of the next chunk's distance GEMM -- an experiment)
         auto k0 = hclust_rnn_kernel<512, 0>;
+        if (did) did->form = 3;
         const size_t ldsl = std::max(lds, HR_LDS_CU / 2);      // two workgroups per CU
         allow_dynamic_lds(k0, ldsl);
         launch_rnn(k0, dim3(Ts), 512, ldsl, r, nullptr, lds, 0, nullptr);

@@ -182,8 +182,14 @@ struct HcAggloRange {
 // Bulk-synchronous agglomeration (hclust_rnn_kernel): chooses between the one-launch forms and one round per pair of launches (`split`,
 // or always beyond HR_MAXN observations).  img / remaining: scratch of the round-per-launch form, grown here since only that form needs
 // it.  mid_event (optional) is recorded behind round `mid_round` of the round-per-launch form; returns whether it was recorded.
+// did (optional) receives what was launched, for the plan record (sharp_hclust_batch_plan).
+struct HcAggloDid {
+    int form = 0;             // 1 round per launch, 2 one launch of 1024 threads, 3 one launch of 512 threads, 4 an experiment of the lab build
+    int wpt = 0;              // round per launch: workgroups per task in the rebuild launches (else 0)
+    int finish_at = 0;        // round per launch: the round from which one launch finishes the rest, -1 never (else 0)
+};
 SHARP_HC_LOCAL bool hclust_bulk_synchronous(const HcAggloRange &r, bool split, DevBuf<unsigned char> &img, DevBuf<int> &remaining,
-                                            hipEvent_t mid_event, int mid_round);
+                                            hipEvent_t mid_event, int mid_round, HcAggloDid *did = nullptr);
 // Sequential NN-list agglomeration (hclust_kernel).  only_if (optional, per task of the range): tasks whose entry is 0 are skipped.
 // gstate: the range's per-task state of hc_seq_state_bytes(max_n) each, for max_n > kHcLdsMaxN (else unused).
 SHARP_HC_LOCAL void hclust_sequential(const HcAggloRange &r, const int *only_if, unsigned char *gstate);

@@ -335,6 +335,8 @@ static Knobs read_knobs() {
     v.hc_chunk = num("SHARP_HC_CHUNK", 0);
     v.hc_first_chunk = num("SHARP_HC_FIRST_CHUNK", 0);
     v.hc_ranges = num("SHARP_HC_RANGES", 0);
+    v.hc_wpt = num("SHARP_HC_WPT", 0);              // (the round-per-launch agglomeration's geometry: tests/test_hclust_batch_gpu.py)
+    v.hc_finish_at = num("SHARP_HC_FINISH_AT", 15);
     v.hc_nn_gemm = num("SHARP_HC_NN_GEMM", 1) != 0;
     v.stats_lane = num("SHARP_STATS_LANE", 1) != 0;
     v.ml_min_levels = num("SHARP_ML_MIN_LEVELS", 0);
@@ -352,8 +354,6 @@ static Knobs read_knobs() {
     v.rp_ap_wgs = std::max(1, num("SHARP_RP_AP_WGS", 4));
     v.rp_shape = num("SHARP_RP_SHAPE", 0);
     if (const char *ps = env("SHARP_RP_PC_SHAPE")) v.rp_pc_shape = (*ps == 'a' || *ps == 'A') ? 1 : (*ps == 'b' || *ps == 'B') ? 2 : 0;
-    v.hc_wpt = num("SHARP_HC_WPT", 0);
-    v.hc_finish_at = num("SHARP_HC_FINISH_AT", 15);
     v.mean_early = num("SHARP_MEAN_EARLY", 0) != 0;
     v.hc_prep_early = num("SHARP_HC_PREP_EARLY", 1) != 0;
     v.hc_tri = num("SHARP_HC_TRI", 0) != 0;
