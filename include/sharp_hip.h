@@ -794,6 +794,31 @@ int sharp_get_opt_hclust_batch(int count, const int *n, const int *p, const int 
                                int *branch, int *rc, int *sequential);
 int sharp_hclust_batch_plan(int *rows, int cap_rows, int *n_rows);
 
+/* Test entries for the meta-clustering stage (sharp_amd/csrc/meta.hip; tests/test_meta_gpu.py).  Doubles are filled with the sentinel NaN
+ * above and ints with INT_MIN over the WHOLE capacity the caller states, before anything else is done, so the caller sees what was
+ * written, that nothing was written behind it, and after a refusal that nothing was written at all.  A buffer that is too small for
+ * what the call produced is refused ("an output buffer is too small"), never written past.
+ *
+ * sharp_wMetaC_batch: `count` wMetaC tasks given as parallel arrays through ONE wmetac_batch call, with the soft matrix and the
+ * intermediates -- how the folds of SHARP_large reach that driver.  Task t is the N[t] x C[t] column-major label matrix that follows its
+ * predecessors' N x C values in labels; hmethod .. height_Ntimes as sharp_wMetaC takes them, per task and without defaults.  labels may
+ * be null: the driver then refuses the tasks as it refuses an empty label matrix.
+ * cap[8]: the capacities, in values, of rc, allC, ncl, finalC, w1, S, tf, x0 in that order.  Outputs, each concatenated in task order:
+ * rc (0 or the warning bits of sharp_wMetaC), allC and ncl (count each), finalC and w1 (sum N), S (sum allC^2, row-major per task),
+ * tf (sum allC) and x0 (sum N ncl, column-major per task).
+ *
+ * sharp_cluster_means: means (nC x p row-major, cap values) = the mean row of every cluster of the host matrix E (n rows of p values,
+ * leading dimension ld >= p), through ONE cluster_means_dev call -- sMetaC's centroids, the tails of SHARP_large and
+ * sharp_calinski_harabasz.  uid[n]: the cluster of every row, 0 .. nC - 1, every cluster with at least one row.
+ *
+ * sharp_ensemble_mean: viE (n x p row-major, cap values) = (sum over k of E[:, k p .. (k + 1) p)) / K for the host matrix E (n rows of
+ * K p values, leading dimension ldE >= K p), through ONE ensemble_mean_dev call. */
+int sharp_wMetaC_batch(int count, const int *N, const int *C, const int *hmethod, const int *enN_cluster, const int *minN, const int *maxN,
+                       const double *sil_thre, const double *height_Ntimes, const int *labels, const long long *cap, int *rc, int *allC,
+                       int *ncl, int *finalC, double *w1, double *S, int *tf, double *x0);
+int sharp_cluster_means(const double *E, long long ld, int n, int p, const int *uid, int nC, double *means, long long cap);
+int sharp_ensemble_mean(const double *E, long long ldE, int n, int p, int K, double *viE, long long cap);
+
 /* ---- device memory helpers for non-torch hosts (R glue, tests) -------------- */
 int sharp_dev_alloc(long long bytes, void **dptr);
 int sharp_dev_free(void *dptr);

@@ -8,10 +8,12 @@
 #include "meta.hpp"
 
 #include <algorithm>
+#include <climits>
 #include <thread>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <unordered_map>
 
 #include "linalg.hpp"
@@ -181,6 +183,13 @@ struct MetaWs {
     DevBuf<GemmTask> gemm;
 };
 MetaWs &mws() { return per_slot<MetaWs>(); }
+
+double nan_sentinel() {   // what the test entries fill their outputs with (as the linalg and get_opt_hclust batch entries do)
+    const unsigned long long bits = 0x7ff8c0de5eed0001ULL;
+    double v;
+    std::memcpy(&v, &bits, sizeof bits);
+    return v;
+}
 
 }  // namespace
 
@@ -390,8 +399,7 @@ void wmetac_batch(const std::vector<WmTask> &tasks, bool want_x0, bool want_debu
     }
 }
 
-void cluster_means_dev(const double *d_E, long long ld, int n, int p, const std::vector<int> &uid, int nC, double *d_means,
-                       const int *row_of_cell) {
+void cluster_means_dev(const double *d_E, long long ld, int n, int p, const std::vector<int> &uid, int nC, double *d_means) {
     Ctx &c = ctx();
     MetaWs &W = mws();
     std::vector<int> start(nC + 1, 0), members(n);
@@ -399,7 +407,7 @@ void cluster_means_dev(const double *d_E, long long ld, int n, int p, const std:
     for (int t = 0; t < nC; ++t) start[t + 1] += start[t];
     {
         std::vector<int> fill(start.begin(), start.end() - 1);
-        for (int i = 0; i < n; ++i) members[fill[uid[i]]++] = row_of_cell ? row_of_cell[i] : i;   // ascending cell index inside a cluster
+        for (int i = 0; i < n; ++i) members[fill[uid[i]]++] = i;   // ascending cell index inside a cluster
     }
     W.start.ensure(nC + 1); W.members.ensure(n);
     W.start.upload(start.data(), nC + 1);
@@ -534,6 +542,95 @@ int sharp_sMetaC(const int *labels, const double *sE1, long long n, int p, int h
     catch (const sharp::Error &e) { sharp::set_error(e.what()); return e.code; }
     catch (const std::exception &e) { sharp::set_error(e.what()); return SHARP_ERR; }
     return warn;
+}
+
+/* Test entry: `count` wMetaC tasks through ONE wmetac_batch call (include/sharp_hip.h). */
+int sharp_wMetaC_batch(int count, const int *N, const int *C, const int *hmethod, const int *enN_cluster, const int *minN, const int *maxN,
+                       const double *sil_thre, const double *height_Ntimes, const int *labels, const long long *cap, int *rc, int *allC,
+                       int *ncl, int *finalC, double *w1, double *S, int *tf, double *x0) {
+    SHARP_API_BEGIN
+    ctx();
+    const std::string w = "sharp_wMetaC_batch";
+    SHARP_REQUIRE(count >= 1, w + ": count must be at least 1");
+    SHARP_REQUIRE(N && C && hmethod && enN_cluster && minN && maxN && sil_thre && height_Ntimes && cap, w + ": null input");
+    SHARP_REQUIRE(rc && allC && ncl && finalC && w1 && S && tf && x0, w + ": null output");
+    for (int q = 0; q < 8; ++q) SHARP_REQUIRE(cap[q] >= 0, w + ": negative capacity");
+    // every output is the sentinel over its whole capacity; a refusal below leaves it so
+    int *const iout[5] = {rc, allC, ncl, finalC, tf};
+    const long long icap[5] = {cap[0], cap[1], cap[2], cap[3], cap[6]};
+    for (int q = 0; q < 5; ++q) std::fill_n(iout[q], icap[q], INT_MIN);
+    std::fill_n(w1, cap[4], nan_sentinel());
+    std::fill_n(S, cap[5], nan_sentinel());
+    std::fill_n(x0, cap[7], nan_sentinel());
+    const std::string small = w + ": an output buffer is too small";
+    // labels == null goes to the driver as it is: the refusal under test is the driver's
+    std::vector<WmTask> tasks(count);
+    long long oLab = 0, sumN = 0;
+    for (int t = 0; t < count; ++t) {
+        WmTask &tk = tasks[t];
+        tk.nC = labels ? labels + oLab : nullptr;
+        tk.N = N[t]; tk.C = C[t];
+        tk.prm.hmethod = hmethod[t]; tk.prm.N_cluster = enN_cluster[t]; tk.prm.minN = minN[t]; tk.prm.maxN = maxN[t];
+        tk.prm.sil_thre = sil_thre[t]; tk.prm.height_Ntimes = height_Ntimes[t];
+        oLab += static_cast<long long>(std::max(N[t], 0)) * std::max(C[t], 0);
+        sumN += std::max(N[t], 0);
+    }
+    SHARP_REQUIRE(cap[0] >= count && cap[1] >= count && cap[2] >= count && cap[3] >= sumN && cap[4] >= sumN, small);
+    std::vector<WmResult> res;
+    wmetac_batch(tasks, true, true, res);
+    long long nS = 0, nTf = 0, nX = 0;
+    for (const WmResult &R : res) { nS += static_cast<long long>(R.S.size()); nTf += static_cast<long long>(R.tf.size()); nX += static_cast<long long>(R.x0.size()); }
+    SHARP_REQUIRE(cap[5] >= nS && cap[6] >= nTf && cap[7] >= nX, small);
+    for (int t = 0; t < count; ++t) {
+        const WmResult &R = res[t];
+        rc[t] = R.rc; allC[t] = R.allC; ncl[t] = R.ncl;
+        finalC = std::copy(R.finalC.begin(), R.finalC.end(), finalC);
+        w1 = std::copy(R.w1.begin(), R.w1.end(), w1);
+        S = std::copy(R.S.begin(), R.S.end(), S);
+        tf = std::copy(R.tf.begin(), R.tf.end(), tf);
+        x0 = std::copy(R.x0.begin(), R.x0.end(), x0);
+    }
+    SHARP_API_END
+}
+
+/* Test entry: the per-cluster mean rows of a host matrix through ONE cluster_means_dev call (include/sharp_hip.h). */
+int sharp_cluster_means(const double *E, long long ld, int n, int p, const int *uid, int nC, double *means, long long cap) {
+    SHARP_API_BEGIN
+    ctx();
+    const std::string w = "sharp_cluster_means";
+    SHARP_REQUIRE(E && uid && means, w + ": null argument");
+    SHARP_REQUIRE(n >= 1 && p >= 1 && ld >= p && nC >= 1 && nC <= n && cap >= 0, w + ": bad sizes");
+    std::fill_n(means, cap, nan_sentinel());
+    SHARP_REQUIRE(cap >= static_cast<long long>(nC) * p, w + ": the output buffer is too small");
+    std::vector<int> ids(uid, uid + n), seen(nC, 0);
+    for (int i = 0; i < n; ++i) {
+        SHARP_REQUIRE(ids[i] >= 0 && ids[i] < nC, w + ": uid out of range");
+        seen[ids[i]] = 1;
+    }
+    SHARP_REQUIRE(std::find(seen.begin(), seen.end(), 0) == seen.end(), w + ": a cluster without cells");
+    const size_t nE = static_cast<size_t>(n - 1) * ld + p;           // (the last row ends with its p-th value)
+    DevBuf<double> dE(nE), dM(static_cast<size_t>(nC) * p);
+    dE.upload(E, nE);
+    cluster_means_dev(dE.p, ld, n, p, ids, nC, dM.p);
+    dM.download(means, static_cast<size_t>(nC) * p);
+    SHARP_API_END
+}
+
+/* Test entry: viE = (sum of the K projections of a host E) / K through ONE ensemble_mean_dev call (include/sharp_hip.h). */
+int sharp_ensemble_mean(const double *E, long long ldE, int n, int p, int K, double *viE, long long cap) {
+    SHARP_API_BEGIN
+    ctx();
+    const std::string w = "sharp_ensemble_mean";
+    SHARP_REQUIRE(E && viE, w + ": null argument");
+    SHARP_REQUIRE(n >= 1 && p >= 1 && K >= 1 && ldE >= static_cast<long long>(K) * p && cap >= 0, w + ": bad sizes");
+    std::fill_n(viE, cap, nan_sentinel());
+    SHARP_REQUIRE(cap >= static_cast<long long>(n) * p, w + ": the output buffer is too small");
+    const size_t nE = static_cast<size_t>(n - 1) * ldE + static_cast<size_t>(K) * p;
+    DevBuf<double> dE(nE), dV(static_cast<size_t>(n) * p);
+    dE.upload(E, nE);
+    ensemble_mean_dev(dE.p, ldE, n, p, K, dV.p);
+    dV.download(viE, static_cast<size_t>(n) * p);
+    SHARP_API_END
 }
 
 }  // extern "C"

@@ -27,9 +27,7 @@ void wmetac_batch(const std::vector<WmTask> &tasks, bool want_x0, bool want_debu
 // ---- sMetaC
 // Per-label mean rows of a device-resident n x p matrix (R/sMetaC.R:58-63).  uid[i] in [0, nC) is the
 // first-appearance index of cell i's label.  d_means: nC x p device buffer (row-major).
-// row_of_cell (optional): cell i lives in row row_of_cell[i] of d_E; sums still run in ascending cell order.
-void cluster_means_dev(const double *d_E, long long ld, int n, int p, const std::vector<int> &uid, int nC, double *d_means,
-                       const int *row_of_cell = nullptr);
+void cluster_means_dev(const double *d_E, long long ld, int n, int p, const std::vector<int> &uid, int nC, double *d_means);
 
 struct SmResult {
     int rc = 0;
