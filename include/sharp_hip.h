@@ -729,6 +729,59 @@ int sharp_harmony_correct(const double *Z, const double *R, const int *batch, co
 int sharp_harmony_ridge(const double *N, const double *S, int B, int K, int d, double lam, double *W);
 int sharp_harmony_caps(int *slab, int *lds_tile);
 
+/* ---- doublet detection from sparse count blocks (sharp_amd/csrc/doublets.hip; the specification is the project's own,
+ * modelled on Scrublet, with no parity with the scrublet or scanpy packages claimed) ----
+ * The blocks are raw counts as sharp_expr_pca_csc takes them; a negative or non-finite value is refused before anything is allocated.
+ * round(x) = floor(x + 0.5) throughout.
+ * sharp_doublet_plan (no device): n_sim = round(ratio n); n_neighbors 0: the default min(round(0.5 sqrt(n)), the largest value whose
+ *   k_adj fits); k_adj = round(n_neighbors (1 + n_sim / n)), the K of the k-NN, which must be <= 255 and <= n + n_sim - 1: an explicit
+ *   n_neighbors beyond that is refused by name.
+ * sharp_doublet_pairs (no device): parents[2 s + j] = floor((double)(h(s, j) >> 11) 2^-53 (double)n), h(s, j) = mix(mix(seed G + s) + j)
+ *   with Omega's 64-bit mix; 0 <= seed < 2^53.  A doublet may have the same parent twice.
+ * sharp_doublet_synth_csc: doublet s = column parents[2 s] + column parents[2 s + 1] over all m genes, made on the device slab after
+ *   slab (max_doublets_per_slab 0: the library's memory budget alone cuts the slabs; no result depends on it) and brought back as
+ *   colptr_out (n_sim + 1), rowidx_out / val_out (capacity entries: a smaller capacity than the doublets need is refused by name; the
+ *   parents' entries added up always suffice), genes strictly ascending, a gene of both parents stored once; cell_sum_out (n_sim or
+ *   NULL) = L_a + L_b.
+ * sharp_doublet_project_csc: the doublets' scores (n_sim x n_components) in a fit of sharp_expr_pca_sub_csc (loadings, center, scale with
+ *   a row per kept gene; genes / n_genes its subset, NULL and 0 for all genes): per slab the transform, the subset and the cell-side
+ *   product of sharp_expr_pca_transform_sub_csc.  On integer counts the scores are bit for bit that entry's on the host-built blocks.
+ * sharp_doublet_neighbor_counts: counts[i] = the entries of row i of index (rows x K, 0-based) that are >= n_obs.
+ * sharp_doublet_score_table (no device): table[c] = q rho / r / (1 - rho - q (1 - rho - rho / r)), q = (c + 1) / (k_adj + 2), c = 0 ..
+ *   k_adj, r = n_sim / n, rho the expected doublet rate.
+ * sharp_doublet_threshold (no device): threshold_in NaN: the minimum between the two modes of the simulated scores' 256-bin histogram
+ *   over [min, max], smoothed by three-bin means ((a + b) + c) / 3 with reflected ends until at most two local maxima remain (at most
+ *   10000 times); *found = 0 and *threshold = NaN when two maxima never stand, and predicted / rates are then left alone.  Otherwise
+ *   predicted[i] = scores_obs[i] > threshold, rates = {detected (share of observed above), detectable (share of simulated above),
+ *   overall = detected / detectable}.  A given threshold is used as it is (*found stays 0).
+ * sharp_scrublet_csc: the whole call.  fit_* all NULL: variable genes (n_top_genes, unless genes is given) and the sparse PCA of the
+ *   observed cells (n_prin_comps components, oversample 10, 4 iterations, seed 0) are computed first; otherwise the caller's fit
+ *   (fit_scores n x n_prin_comps, the rest as for sharp_doublet_project_csc) is used as it is.  nn_method 0: the exact k-NN, 1:
+ *   NN-descent with nn_args = {n_projections, max_candidates, n_iters, delta, seed} (NULL: 8, 0, 12, 0.001, 10).  threshold NaN: find
+ *   it.  Out: doublet_scores (n), doublet_scores_sim (n_sim), predicted (n; left alone without a threshold), threshold_out (NaN
+ *   without one), threshold_found, rates (3), n_neighbors_out, k_adj_out, parents (2 n_sim), genes_out (room for min(n_top_genes, m) or
+ *   n_genes values) and n_genes_out (0: all genes), neighbor_counts (n + n_sim), sim_pca (n_sim x n_prin_comps, or NULL). */
+int sharp_doublet_plan(long long n, double sim_doublet_ratio, int n_neighbors, long long *n_sim, int *n_neighbors_out, int *k_adj);
+int sharp_doublet_pairs(long long n, long long n_sim, long long seed, long long *parents);
+int sharp_doublet_synth_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks,
+                            int m, const long long *parents, long long n_sim, int max_doublets_per_slab, long long capacity,
+                            long long *colptr_out, int *rowidx_out, double *val_out, double *cell_sum_out);
+int sharp_doublet_project_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks,
+                              int m, const long long *parents, long long n_sim, double normalize_total, int log1p, const double *loadings,
+                              const double *center, const double *scale, int n_components, const int *genes, int n_genes,
+                              int max_doublets_per_slab, double *scores);
+int sharp_doublet_neighbor_counts(const int *index, long long rows, int K, long long n_obs, int *counts);
+int sharp_doublet_score_table(int k_adj, double r, double expected_doublet_rate, double *table);
+int sharp_doublet_threshold(const double *scores_obs, long long n, const double *scores_sim, long long n_sim, double threshold_in,
+                            double *threshold, int *found, int *predicted, double *rates, int *passes);
+int sharp_scrublet_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks, int m,
+                       double sim_doublet_ratio, double expected_doublet_rate, int n_neighbors, int n_prin_comps, int n_top_genes,
+                       const int *genes, int n_genes, const double *fit_scores, const double *fit_loadings, const double *fit_center,
+                       const double *fit_scale, double normalize_total, int log1p, int scale, double threshold, int nn_method,
+                       const double *nn_args, long long seed, int max_doublets_per_slab, double *doublet_scores, double *doublet_scores_sim,
+                       int *predicted, double *threshold_out, int *threshold_found, double *rates, int *n_neighbors_out, int *k_adj_out,
+                       long long *parents, int *genes_out, int *n_genes_out, int *neighbor_counts, double *sim_pca);
+
 /* ---- synthetic inputs (bench / tests; not part of the reference) ------------ */
 /* Counter-based generator, value = f(seed, gene, cell): bit-identical to
  * oracle_synth_value().  Fills dX (fp32, m x ncell column-major, leading dim ld). */
@@ -1002,6 +1055,17 @@ void sharp_C_harmony(double *Z, double *n, int *d, int *batch, int *n_batches, i
                      int *max_iter, int *max_iter_cluster, int *n_blocks, double *epsilon_cluster, double *epsilon_harmony, int *init_iter,
                      double *seed, double *Z_corr, double *Y, double *objective, int *rounds, int *n_iter, int *converged, int *want_R, double *R,
                      int *status);
+/* sharp_scrublet_csc in the same convention, the blocks as sharp_C_expr_pca_sub_csc takes them: seed as double; *n_genes = 0: no gene list
+ * (genes is a buffer that is left alone); *have_fit = 0: the fit_* are buffers that are left alone; *threshold NA / NaN: find it;
+ * *have_nn_args = 0: the defaults; parents as int (n_sim x 2, rows of two, 0-based); *want_sim_pca = 0: sim_pca is left alone */
+void sharp_C_scrublet_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, double *sim_doublet_ratio,
+                          double *expected_doublet_rate, int *n_neighbors, int *n_prin_comps, int *n_top_genes, int *genes, int *n_genes,
+                          int *have_fit, double *fit_scores, double *fit_loadings, double *fit_center, double *fit_scale,
+                          double *normalize_total, int *log1p, int *scale, double *threshold, int *nn_method, int *have_nn_args,
+                          double *nn_args, double *seed, int *max_doublets_per_slab, double *doublet_scores, double *doublet_scores_sim,
+                          int *predicted, double *threshold_out, int *threshold_found, double *rates, int *n_neighbors_out, int *k_adj_out,
+                          int *parents, int *genes_out, int *n_genes_out, int *neighbor_counts, int *want_sim_pca, double *sim_pca,
+                          int *status);
 
 #ifdef __cplusplus
 }

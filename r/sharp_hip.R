@@ -905,6 +905,70 @@ sharp_harmony <- function(Z, batch, n.clusters = NULL, sigma = 0.1, theta = 2, l
 # the block number of every cell of a list of genes x cells blocks, in sharp_expression_pca's order: the batch of sharp_harmony
 sharp_batch_of_blocks <- function(blocks) rep(seq_along(blocks), vapply(blocks, ncol, 1L))
 
+# Scrublet-style doublet detection on raw counts (DESIGN.md 24): scExp as sharp_expression_pca takes it.  round(sim.doublet.ratio n)
+# doublets are simulated on the GPU as sums of two cells, placed in the observed cells' PCA (fitted here on n.top.genes variable genes,
+# or on `genes`, 1-based; or the caller's pca = a result of sharp_expression_pca_genes / sharp_expression_pca, used as it is) and every
+# cell is scored by the simulated share of its k.adj = round(n.neighbors (1 + n.sim / n)) nearest neighbours.  k.adj must be <= 255 (the
+# k-NN's limit): the default n.neighbors is min(round(0.5 sqrt(n)), the largest value that fits), an explicit one beyond it is refused.
+# threshold NULL: the minimum between the two modes of the simulated scores' histogram; when it never shows two modes a warning says so
+# and threshold, predicted.doublets and the rates are NA / NULL.  list(doublet.scores, doublet.scores.sim, predicted.doublets,
+# threshold, threshold.found, detected.doublet.rate, detectable.doublet.fraction, overall.doublet.rate, n.neighbors, k.adj, n.sim,
+# parents (n.sim x 2, 1-based), genes (1-based, or NULL), neighbor.counts, and sim.pca with ret.sim).
+sharp_scrublet <- function(scExp, sim.doublet.ratio = 2, expected.doublet.rate = 0.1, n.neighbors = NULL, n.prin.comps = 30L,
+                           n.top.genes = 2000L, genes = NULL, pca = NULL, normalize.total = 1e4, log1p = TRUE, scale = TRUE, threshold = NULL,
+                           nn.method = c("exact", "descent"), nn.args = NULL, seed = 0, ret.sim = FALSE) {
+    who <- "sharp_scrublet"
+    nn.method <- match.arg(nn.method)
+    b <- .sharp_csc_cat(scExp, who)
+    n <- sum(b$ncb)
+    n.sim <- floor(sim.doublet.ratio * n + 0.5)
+    if (!is.finite(n.sim) || n.sim < 1) stop("scrublet: sim_doublet_ratio gives fewer than 1 simulated doublet")
+    have.fit <- !is.null(pca)
+    if (have.fit) {
+        if (!is.null(genes)) stop("scrublet: genes belongs to the fit; with pca the pca's own gene subset is used")
+        m.fit <- if (is.null(pca$genes)) nrow(pca$loadings) else pca$n.genes.in
+        if (m.fit != b$m) stop(paste0("scrublet: the pca was fitted on ", m.fit, " genes, the blocks have ", b$m))
+        if (nrow(pca$scores) != n) stop(paste0("scrublet: the pca's scores are ", nrow(pca$scores), " cells, the blocks have ", n))
+        g <- if (is.null(pca$genes)) NULL else as.integer(pca$genes) - 1L
+        k <- ncol(pca$loadings)
+        normalize.total <- pca$normalize.total; log1p <- pca$log1p
+        fit <- list(as.double(t(pca$scores)), as.double(t(pca$loadings)), as.double(pca$center), as.double(pca$scale))
+    } else {
+        g <- if (is.null(genes)) NULL else .sharp_genes0(genes, b$m, who)
+        k <- as.integer(n.prin.comps)
+        fit <- list(double(1), double(1), double(1), double(1))
+    }
+    top <- as.integer(n.top.genes)
+    ng <- length(g)
+    nn <- c(8, 0, 12, 0.001, 10)
+    names(nn) <- c("n_projections", "max_candidates", "n_iters", "delta", "seed")
+    if (!is.null(nn.args)) {
+        if (nn.method != "descent") stop("scrublet: nn_args belong to nn_method = \"descent\"")
+        if (!all(names(nn.args) %in% names(nn))) stop("scrublet: nn.args takes n_projections, max_candidates, n_iters, delta, seed")
+        nn[names(nn.args)] <- as.double(unlist(nn.args))
+    }
+    r <- .C("sharp_C_scrublet_csc", as.integer(b$p), as.integer(b$i), b$x, b$nb, b$ncb, b$m, as.double(sim.doublet.ratio),
+            as.double(expected.doublet.rate), as.integer(if (is.null(n.neighbors)) 0L else n.neighbors), as.integer(k), top,
+            if (ng) g else integer(1), as.integer(ng), as.integer(have.fit), fit[[1]], fit[[2]], fit[[3]], fit[[4]],
+            as.double(if (is.null(normalize.total)) 0 else normalize.total), as.integer(log1p), as.integer(scale),
+            as.double(if (is.null(threshold)) NA_real_ else threshold), as.integer(nn.method == "descent"), as.integer(!is.null(nn.args)),
+            as.double(nn), as.double(seed), 0L, scores = double(n), scores_sim = double(n.sim), predicted = integer(n), threshold = double(1),
+            found = integer(1), rates = double(3), nn = integer(1), k_adj = integer(1), parents = integer(2 * n.sim),
+            genes = integer(max(ng, min(top, b$m), 1L)), n_genes = integer(1), counts = integer(n + n.sim), as.integer(ret.sim),
+            sim_pca = double(if (ret.sim) n.sim * k else 1L), status = integer(1), NAOK = TRUE)
+    .sharp_check(r$status)
+    have <- !is.nan(r$threshold)
+    if (!have) warning("scrublet: no threshold found: the histogram of the simulated doublets' scores never shows two modes; predicted.doublets is NULL")
+    out <- list(doublet.scores = r$scores, doublet.scores.sim = r$scores_sim, predicted.doublets = if (have) r$predicted != 0L else NULL,
+                threshold = if (have) r$threshold else NA_real_, threshold.found = r$found != 0L,
+                detected.doublet.rate = if (have) r$rates[1] else NA_real_, detectable.doublet.fraction = if (have) r$rates[2] else NA_real_,
+                overall.doublet.rate = if (have) r$rates[3] else NA_real_, n.neighbors = r$nn, k.adj = r$k_adj, n.sim = n.sim,
+                parents = t(matrix(r$parents, nrow = 2)) + 1L, genes = if (r$n_genes > 0) r$genes[seq_len(r$n_genes)] + 1L else NULL,
+                neighbor.counts = r$counts)
+    if (ret.sim) out$sim.pca <- t(matrix(r$sim_pca, nrow = k))
+    out
+}
+
 # the same on any symmetric graph: a dgCMatrix-like triple (row_ptr 0-based with n + 1 values, col 0-based, val)
 sharp_louvain_graph <- function(row_ptr, col, val, resolution = 1, seed = 10, tol = 1e-7, max_levels = 20L, max_rounds = 200L,
                                 max_fails = 4L, ret_levels = FALSE) {

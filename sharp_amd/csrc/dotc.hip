@@ -532,4 +532,32 @@ void sharp_C_harmony(double *Z, double *n, int *d, int *batch, int *n_batches, i
                             *want_R ? R : nullptr);
 }
 
+/* Doublet detection: the plain entry's bits */
+void sharp_C_scrublet_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, double *sim_doublet_ratio,
+                          double *expected_doublet_rate, int *n_neighbors, int *n_prin_comps, int *n_top_genes, int *genes, int *n_genes,
+                          int *have_fit, double *fit_scores, double *fit_loadings, double *fit_center, double *fit_scale,
+                          double *normalize_total, int *log1p, int *scale, double *threshold, int *nn_method, int *have_nn_args,
+                          double *nn_args, double *seed, int *max_doublets_per_slab, double *doublet_scores, double *doublet_scores_sim,
+                          int *predicted, double *threshold_out, int *threshold_found, double *rates, int *n_neighbors_out, int *k_adj_out,
+                          int *parents, int *genes_out, int *n_genes_out, int *neighbor_counts, int *want_sim_pca, double *sim_pca,
+                          int *status) {
+    const CscList L(pcat, icat, xcat, *nblocks, ncb, status);
+    if (!L.ok) return;
+    long long n = 0, n_sim = 0;
+    for (int b = 0; b < *nblocks; ++b) n += L.nc[b];
+    int nn = 0, ka = 0;
+    *status = sharp_doublet_plan(n, *sim_doublet_ratio, *n_neighbors, &n_sim, &nn, &ka);
+    if (*status != 0) return;
+    std::vector<long long> par(static_cast<size_t>(n_sim) * 2);
+    const bool fit = *have_fit != 0;
+    *status = sharp_scrublet_csc(L.cp.data(), L.ri.data(), L.vx.data(), L.nc.data(), *nblocks, *m, *sim_doublet_ratio, *expected_doublet_rate,
+                                 *n_neighbors, *n_prin_comps, *n_top_genes, *n_genes ? genes : nullptr, *n_genes, fit ? fit_scores : nullptr,
+                                 fit ? fit_loadings : nullptr, fit ? fit_center : nullptr, fit ? fit_scale : nullptr, *normalize_total, *log1p,
+                                 *scale, *threshold, *nn_method, *have_nn_args ? nn_args : nullptr, as_ll(seed), *max_doublets_per_slab,
+                                 doublet_scores, doublet_scores_sim, predicted, threshold_out, threshold_found, rates, n_neighbors_out,
+                                 k_adj_out, par.data(), genes_out, n_genes_out, neighbor_counts, *want_sim_pca ? sim_pca : nullptr);
+    if (*status == 0)
+        for (size_t e = 0; e < par.size(); ++e) parents[e] = static_cast<int>(par[e]);
+}
+
 }  // extern "C"

@@ -524,7 +524,7 @@ void check_l(const std::string &who, int k, int oversample, long long n, int m) 
 
 // Drops the entries of the genes that `genes` does not keep and renumbers the kept ones by their position in it: a count
 // per cell, the scan, a fill into fresh buffers.  genes was checked by expr_check_genes.
-void expr_subset(ExprData &D, const int *genes, int mk) {
+void subset_impl(ExprData &D, const int *genes, int mk) {
     Ctx &c = ctx();
     KernelTimer timer("expr_subset");
     const long long n = D.n;
@@ -557,6 +557,15 @@ void expr_subset(ExprData &D, const int *genes, int mk) {
 }  // namespace
 
 unsigned wave_grid(long long items) { return grid_for(items, 4); }
+
+void expr_transform(ExprData &D, double normalize_total, bool lg) {
+    if (normalize_total > 0.0 || lg)
+        hipLaunchKernelGGL(expr_transform_kernel, dim3(wave_grid(D.n)), dim3(256), 0, ctx().stream, D.cptr.p, D.lsum.p, D.n, normalize_total,
+                           lg ? 1 : 0, D.t.p);
+    launch_check("expr_transform_kernel");
+}
+
+void expr_subset(ExprData &D, const int *genes, int n_genes) { subset_impl(D, genes, n_genes); }
 
 void expr_check_options(const std::string &who, double normalize_total, int m) {
     SHARP_REQUIRE(m >= 1 && m <= kExprMaxM, who + ": need 1 <= m <= 16777216 genes");
@@ -654,17 +663,14 @@ void expr_load(const std::string &who, const ExprBlocks &B, double normalize_tot
             }
         }
         hipLaunchKernelGGL(expr_cell_sums_kernel, dim3(wave_grid(n)), dim3(256), 0, c.stream, D.cptr.p, D.t.p, n, D.lsum.p);
-        if (normalize_total > 0.0 || lg)
-            hipLaunchKernelGGL(expr_transform_kernel, dim3(wave_grid(n)), dim3(256), 0, c.stream, D.cptr.p, D.lsum.p, n, normalize_total, lg ? 1 : 0,
-                               D.t.p);
-        launch_check("expr_transform_kernel");
+        expr_transform(D, normalize_total, lg);
         if (extra.want_tsum) {
             D.tsum.alloc(std::max<long long>(n, 1));
             hipLaunchKernelGGL(expr_cell_sums_kernel, dim3(wave_grid(n)), dim3(256), 0, c.stream, D.cptr.p, D.t.p, n, D.tsum.p);
             launch_check("expr_cell_sums_kernel");
         }
     }
-    if (extra.genes) expr_subset(D, extra.genes, mk);
+    if (extra.genes) subset_impl(D, extra.genes, mk);
     if (!genes) return;
     const int m = D.m;
     {

@@ -58,6 +58,10 @@ struct ExprData {
 // gene-major copy is built; from there on D.m = extra.n_genes.
 void expr_load(const std::string &who, const ExprBlocks &B, double normalize_total, bool log1p, bool genes, bool scale, int l_work,
                long long min_cells, ExprData &D, const ExprExtra &extra = ExprExtra());
+// two steps of expr_load for a caller that made the cell-major copy itself (doublets.hip: D.cptr, D.ridx, D.t, D.lsum, D.n, D.m, D.nnz):
+// the transform of the values in place, and the drop of the genes that `genes` (checked by expr_check_genes) does not keep
+void expr_transform(ExprData &D, double normalize_total, bool log1p);
+void expr_subset(ExprData &D, const int *genes, int n_genes);
 // the genes kept of m: n_genes when `genes` is a strictly ascending list within [0, m), m for (nullptr, 0); anything else is refused by name
 int expr_check_genes(const std::string &who, const int *genes, int n_genes, int m);
 // the checks of the options and of the block list that need no device; the second returns the cells in all
