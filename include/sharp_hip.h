@@ -605,6 +605,39 @@ int sharp_louvain_aggregate(const long long *row_ptr, const int *col, const long
                             int *col_out, long long *q_out, long long *nnz_out, long long *nc_out, int *new_out);
 int sharp_louvain_row_caps(int *wave_cap, int *block_cap);
 
+/* ---- Leiden community detection on the neighbour graph (sharp_amd/csrc/leiden.hip) ----------------------------
+ * Louvain's levels with a refinement between a level's move phase and its aggregation: the level's partition P is re-partitioned into
+ * well-connected sub-communities, the coarse graph is built from those, and the next level starts from the connected parts of P.  The
+ * returned communities are connected.  The project's own deterministic form: a pure function of its arguments, two calls give the
+ * same bits; no parity with leidenalg, igraph or scanpy is claimed.  The three entries take the arguments of their sharp_louvain_*
+ * counterparts plus max_refine_rounds (1 .. 100000; 200 in the front ends), refuse what those refuse, and fill the same outputs plus
+ * modularity (Q of the returned membership on the input graph: sharp_louvain_modularity of it, bit for bit), level_sub_communities and
+ * level_refine_rounds (level_cap values each).  level_communities and level_q describe a level's P; level_membership: NULL, or
+ * level_cap * n ints, the 0-based rank of the community P of every input vertex at each level. */
+int sharp_leiden_graph(const long long *row_ptr, const int *col, const double *val, long long n, double resolution, double tol, int max_levels,
+                       int max_rounds, int max_fails, int max_refine_rounds, double seed, int *membership, double *modularity, int level_cap,
+                       long long *level_n, long long *level_communities, long long *level_sub_communities, int *level_rounds,
+                       int *level_refine_rounds, double *level_q, int *n_levels, int *level_membership);
+int sharp_leiden_neighbors(const int *index, const double *distance, long long n, int K, int squared, double resolution, double tol, int max_levels,
+                           int max_rounds, int max_fails, int max_refine_rounds, double seed, int *membership, double *modularity, int level_cap,
+                           long long *level_n, long long *level_communities, long long *level_sub_communities, int *level_rounds,
+                           int *level_refine_rounds, double *level_q, int *n_levels, int *level_membership);
+int sharp_leiden_snn(const int *index, long long n, int K, double prune, double resolution, double tol, int max_levels, int max_rounds, int max_fails,
+                     int max_refine_rounds, double seed, int *membership, double *modularity, int level_cap, long long *level_n,
+                     long long *level_communities, long long *level_sub_communities, int *level_rounds, int *level_refine_rounds, double *level_q,
+                     int *n_levels, int *level_membership);
+/* The stages one at a time (tests), on an integer-weighted CSR (a level's graph, as sharp_louvain_move takes it).
+ * level: rule L1, the move phase of a level from the membership comm0 (ids in [0, n)) -> the accepted membership, the rounds and its Q.
+ * refine: one round of rule L2 from the state ref inside the partition P (ids in [0, n) both; round: r, counted from 0) -> the
+ * proposals, the number of vertices that moved, and the number that hold a candidate with a positive gain whatever the round's bits.
+ * split: out[v] = the smallest vertex of v's component in the graph restricted to the entries whose two ends carry the same label
+ * (any ints; self-loops ignored); count = the number of such components. */
+int sharp_leiden_level(const long long *row_ptr, const int *col, const long long *q, long long n, const int *comm0, double resolution, double tol,
+                       int max_rounds, int max_fails, double seed, int level, int *comm, int *rounds, double *Q);
+int sharp_leiden_refine(const long long *row_ptr, const int *col, const long long *q, long long n, const int *P, const int *ref, double resolution,
+                        double seed, int level, int round, int *proposal, long long *moved, long long *wanting);
+int sharp_leiden_split(const long long *row_ptr, const int *col, const long long *q, long long n, const int *label, int *out, long long *count);
+
 /* ---- The SNN / Jaccard neighbour graph (sharp_amd/csrc/snn.hip) ------------------------------------------------
  * index: n x K row-major, 0-based, each row K other rows, no index twice in a row (sharp_tsne_knn's and sharp_knn_descent's lists;
  * validated on the device before an index is dereferenced: range, self, twice).  2 <= n <= 16777216, 1 <= K <= 255, K <= n - 1.
@@ -1017,6 +1050,17 @@ void sharp_C_louvain_neighbors(int *index, double *distance, double *n, int *K, 
                                int *max_rounds, int *max_fails, double *seed, int *membership, int *level_cap, double *levels, int *n_levels,
                                int *want_levels, int *level_membership, int *status);
 void sharp_C_louvain_modularity(double *row_ptr, int *col, double *val, double *n, int *membership, double *resolution, double *Q, int *status);
+/* sharp_leiden_graph / sharp_leiden_neighbors / sharp_leiden_snn in the same convention; levels: level_cap rows x 6 (n, communities,
+ * sub-communities, rounds, refine rounds, modularity; row-major) */
+void sharp_C_leiden_graph(double *row_ptr, int *col, double *val, double *n, double *resolution, double *tol, int *max_levels, int *max_rounds,
+                          int *max_fails, int *max_refine_rounds, double *seed, int *membership, double *modularity, int *level_cap, double *levels,
+                          int *n_levels, int *want_levels, int *level_membership, int *status);
+void sharp_C_leiden_neighbors(int *index, double *distance, double *n, int *K, int *squared, double *resolution, double *tol, int *max_levels,
+                              int *max_rounds, int *max_fails, int *max_refine_rounds, double *seed, int *membership, double *modularity,
+                              int *level_cap, double *levels, int *n_levels, int *want_levels, int *level_membership, int *status);
+void sharp_C_leiden_snn(int *index, double *n, int *K, double *prune, double *resolution, double *tol, int *max_levels, int *max_rounds,
+                        int *max_fails, int *max_refine_rounds, double *seed, int *membership, double *modularity, int *level_cap, double *levels,
+                        int *n_levels, int *want_levels, int *level_membership, int *status);
 /* sharp_snn_graph / sharp_louvain_snn in the same convention: n, cap, nnz and row_ptr (n + 1 values) as double, index 0-based;
  * want: 1 = fill col / val (0: the count alone, col / val / shared are buffers of length >= 1 that are left alone), 2 = shared too */
 void sharp_C_snn_graph(int *index, double *n, int *K, double *prune, double *cap, double *row_ptr, int *col, double *val, int *shared, int *want,

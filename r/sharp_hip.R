@@ -991,3 +991,54 @@ sharp_modularity <- function(row_ptr, col, val, membership, resolution = 1) {
     .sharp_check(r$status)
     r$Q
 }
+
+# ---- Leiden on the neighbour graph (DESIGN.md 25) ------------------------------------------------------------------------------------------
+.sharp_leiden_result <- function(r, n, ret_levels) {
+    nl <- r$n_levels
+    lev <- matrix(r$levels, ncol = 6, byrow = TRUE)[seq_len(nl), , drop = FALSE]
+    colnames(lev) <- c("n", "communities", "sub_communities", "rounds", "refine_rounds", "modularity")
+    out <- list(membership = r$membership, n_communities = max(r$membership), modularity = r$Q, levels = lev)
+    if (ret_levels) out$level_membership <- matrix(r$lm[seq_len(nl * n)], nl, n, byrow = TRUE) + 1L
+    out
+}
+
+# sharp_louvain's arguments and graphs with Leiden's refinement between a level's move phase and its aggregation (scanpy's sc.tl.leiden,
+# Seurat's FindClusters(algorithm = 4)): every returned community is connected.  levels: one row (n, communities, sub_communities, rounds,
+# refine_rounds, modularity) per level; modularity: of the returned membership (sharp_modularity of it).  The project's own deterministic
+# form of the method: no random choice among the candidates, one iteration; no parity with leidenalg or igraph is claimed.
+sharp_leiden <- function(X, n_neighbors = 15L, resolution = 1, seed = 10, tol = 1e-7, max_levels = 20L, max_rounds = 200L, max_fails = 4L,
+                         max_refine_rounds = 200L, ret_levels = FALSE, graph = c("fuzzy", "snn"), prune = NULL) {
+    graph <- match.arg(graph)
+    if (graph == "fuzzy" && !is.null(prune)) stop("prune belongs to graph = \"snn\"")
+    nn <- if (is.list(X) && !is.null(X$index)) X else sharp_knn(.sharp_dmat(X), as.integer(n_neighbors) - 1L)
+    index <- as.matrix(nn$index)
+    n <- nrow(index)
+    K <- ncol(index)
+    cap <- as.integer(max_levels)
+    if (graph == "snn") {
+        r <- .C("sharp_C_leiden_snn", as.integer(t(index) - 1L), as.double(n), as.integer(K), as.double(if (is.null(prune)) 1 / 15 else prune),
+                as.double(resolution), as.double(tol), cap, as.integer(max_rounds), as.integer(max_fails), as.integer(max_refine_rounds),
+                as.double(seed), membership = integer(n), Q = double(1), cap, levels = double(6 * cap), n_levels = integer(1),
+                as.integer(ret_levels), lm = integer(if (ret_levels) cap * n else 1L), status = integer(1))
+    } else {
+        r <- .C("sharp_C_leiden_neighbors", as.integer(t(index) - 1L), as.double(t(as.matrix(nn$distance))), as.double(n), as.integer(K), 0L,
+                as.double(resolution), as.double(tol), cap, as.integer(max_rounds), as.integer(max_fails), as.integer(max_refine_rounds),
+                as.double(seed), membership = integer(n), Q = double(1), cap, levels = double(6 * cap), n_levels = integer(1),
+                as.integer(ret_levels), lm = integer(if (ret_levels) cap * n else 1L), status = integer(1))
+    }
+    .sharp_check(r$status)
+    .sharp_leiden_result(r, n, ret_levels)
+}
+
+# the same on any symmetric graph: sharp_louvain_graph's triple
+sharp_leiden_graph <- function(row_ptr, col, val, resolution = 1, seed = 10, tol = 1e-7, max_levels = 20L, max_rounds = 200L,
+                               max_fails = 4L, max_refine_rounds = 200L, ret_levels = FALSE) {
+    n <- length(row_ptr) - 1L
+    cap <- as.integer(max_levels)
+    r <- .C("sharp_C_leiden_graph", as.double(row_ptr), as.integer(col), as.double(val), as.double(n), as.double(resolution),
+            as.double(tol), cap, as.integer(max_rounds), as.integer(max_fails), as.integer(max_refine_rounds), as.double(seed),
+            membership = integer(n), Q = double(1), cap, levels = double(6 * cap), n_levels = integer(1), as.integer(ret_levels),
+            lm = integer(if (ret_levels) cap * n else 1L), status = integer(1))
+    .sharp_check(r$status)
+    .sharp_leiden_result(r, n, ret_levels)
+}

@@ -1,5 +1,5 @@
-"""louvain(), louvain_neighbors(), louvain_snn(), louvain_graph() and modularity(): a clustering read off the neighbour graph
-(DESIGN.md 18, 19).
+"""louvain(), louvain_neighbors(), louvain_snn(), louvain_graph(), their leiden*() counterparts and modularity(): a clustering read off
+the neighbour graph.
 
 The graph is the fuzzy union umap() builds from the k-NN lists -- scanpy's connectivities --, the shared-nearest-neighbour graph with
 Jaccard weights that Seurat clusters (louvain_snn(), louvain(graph="snn"); snn_graph() returns it), or any symmetric CSR the caller
@@ -7,7 +7,11 @@ has.  The method is this project's own synchronous form of Louvain: weights are 
 once, so every sum of weights is exact whatever the order of the GPU's atomics; a round moves all vertices at once from the round's start
 state, a hashed bit per community deciding whether it may lose or gain members in that round; a round is kept when the modularity rises.
 A call is a pure function of its arguments: two calls give the same bits.  No parity with networkx, igraph or cuGraph is claimed.
-Computed by libsharp_hip.so (csrc/louvain.hip); there is no CPU path."""
+leiden*() run the same levels with Leiden's refinement between a level's move phase and its aggregation: every community is
+re-partitioned into well-connected sub-communities, those become the next level's vertices, and the next level starts from the
+community partition, so parts of a community can still change sides; the returned communities are connected.  It is the project's own
+deterministic form (no random choice among the candidates, one iteration); no parity with leidenalg, igraph or scanpy is claimed.
+Computed by libsharp_hip.so (csrc/louvain.hip, csrc/leiden.hip); there is no CPU path."""
 import ctypes as C
 
 import numpy as np
@@ -17,7 +21,8 @@ from ._lib import SharpError, check, f64, i32, i64, lib
 from .snn import PRUNE, _lists, _prune, _search
 from .tsne import _neighbour_arrays
 
-__all__ = ["louvain", "louvain_neighbors", "louvain_snn", "louvain_graph", "modularity"]
+__all__ = ["louvain", "louvain_neighbors", "louvain_snn", "louvain_graph", "leiden", "leiden_neighbors", "leiden_snn", "leiden_graph",
+           "modularity"]
 
 _MAX_N = 16777216
 
@@ -149,6 +154,20 @@ def louvain_snn(index, prune=PRUNE, resolution=1.0, seed=10, tol=1e-7, max_level
     return _result(n, mem, ln, lc, lr, lq, nl.value, lm, a[5])
 
 
+def _graph_choice(who, nn_method, nn_args, graph, prune):
+    """the refusals of louvain()'s and leiden()'s search and graph arguments -> prune (graph = "snn": checked, None: 1/15)"""
+    from .tsne import _nn_method
+
+    method = _nn_method(nn_method, who)
+    if nn_args and method != "descent":
+        raise SharpError(f"{who}: nn_args belong to nn_method = \"descent\"")
+    if graph not in ("fuzzy", "snn"):
+        raise SharpError(f"{who}: graph must be \"fuzzy\" or \"snn\", not {graph!r}")
+    if graph == "fuzzy" and prune is not None:
+        raise SharpError(f"{who}: prune belongs to graph = \"snn\"")
+    return _prune(PRUNE if prune is None else prune, who) if graph == "snn" else prune
+
+
 def louvain(X, n_neighbors=15, resolution=1.0, nn_method="exact", nn_args=None, pca=None, seed=10, tol=1e-7, max_levels=20,
             ret_levels=False, ret_nn=False, pca_center=True, max_rounds=200, max_fails=4, graph="fuzzy", prune=None):
     """Louvain on the neighbour graph of the rows of X, as sc.tl.louvain runs it on scanpy's connectivities.  The input is prepared and
@@ -157,22 +176,116 @@ def louvain(X, n_neighbors=15, resolution=1.0, nn_method="exact", nn_args=None, 
     louvain_neighbors' on those lists; with ret_nn it also carries "nn": {"index", "distance"}.  graph="snn": the SNN / Jaccard graph
     of those lists instead (n_neighbors is Seurat's k.param; prune in [0, 1], None: 1/15) -- louvain_snn's result.  prune belongs to
     graph="snn"."""
-    from .tsne import _nn_method
-
     who = "louvain"
-    method = _nn_method(nn_method, who)
-    if nn_args and method != "descent":
-        raise SharpError(f"{who}: nn_args belong to nn_method = \"descent\"")
-    if graph not in ("fuzzy", "snn"):
-        raise SharpError(f"{who}: graph must be \"fuzzy\" or \"snn\", not {graph!r}")
-    if graph == "fuzzy" and prune is not None:
-        raise SharpError(f"{who}: prune belongs to graph = \"snn\"")
-    if graph == "snn":
-        prune = _prune(PRUNE if prune is None else prune, who)
+    prune = _graph_choice(who, nn_method, nn_args, graph, prune)
     a = _limits(who, resolution, tol, max_levels, max_rounds, max_fails, seed)
     idx, dist, method = _search(X, n_neighbors, nn_method, nn_args, pca, pca_center, who)
     kw = dict(resolution=a[0], seed=a[5], tol=a[1], max_levels=a[2], max_rounds=a[3], max_fails=a[4], ret_levels=ret_levels)
     out = louvain_snn(idx, prune, **kw) if graph == "snn" else louvain_neighbors(idx, dist, **kw)
+    if ret_nn:
+        out["nn"] = {"index": idx, "distance": dist}
+        if method == "descent":
+            out["nn"]["method"] = "descent"
+    return out
+
+
+# ---- Leiden ---------------------------------------------------------------------------------------------------------------------------
+def _refine_limit(who, max_refine_rounds):
+    if not 1 <= int(max_refine_rounds) <= 100000:
+        raise SharpError(f"{who}: max_refine_rounds must be in 1 .. 100000")
+    return int(max_refine_rounds)
+
+
+class _LeidenOut:
+    """the output buffers of a sharp_leiden_* call and the result dict made of them"""
+
+    def __init__(self, n, max_levels, ret_levels):
+        self.mem = np.zeros(n, np.int32)
+        self.ln, self.lc, self.ls = (np.zeros(max_levels, np.int64) for _ in range(3))
+        self.lr, self.lf = np.zeros(max_levels, np.int32), np.zeros(max_levels, np.int32)
+        self.lq = np.zeros(max_levels)
+        self.lm = np.zeros((max_levels, n), np.int32) if ret_levels else None
+        self.q, self.nl, self.cap = C.c_double(), C.c_int(), max_levels
+
+    def args(self):
+        return (i32(self.mem), C.byref(self.q), self.cap, i64(self.ln), i64(self.lc), i64(self.ls), i32(self.lr), i32(self.lf), f64(self.lq),
+                C.byref(self.nl), i32(self.lm))
+
+    def result(self, seed):
+        levels = [{"n": int(self.ln[i]), "communities": int(self.lc[i]), "sub_communities": int(self.ls[i]), "rounds": int(self.lr[i]),
+                   "refine_rounds": int(self.lf[i]), "modularity": float(self.lq[i])} for i in range(self.nl.value)]
+        if self.lm is not None:
+            for i, lev in enumerate(levels):
+                lev["membership"] = self.lm[i] + 1
+        return {"membership": self.mem, "n_communities": int(self.mem.max()), "modularity": self.q.value, "levels": levels, "seed": seed}
+
+
+def leiden_graph(row_ptr, col, val, resolution=1.0, seed=10, tol=1e-7, max_levels=20, max_rounds=200, max_fails=4, max_refine_rounds=200,
+                 ret_levels=False):
+    """Leiden on any symmetric weighted graph given as a CSR (louvain_graph's input and refusals).  Returns louvain_graph's dict:
+    "membership" (int32, 1 .. G by decreasing size; every community is connected in the graph), "n_communities", "modularity" (of the
+    membership: modularity() of it, bit for bit), "levels": [{"n", "communities" and "modularity" (of the level's partition P),
+    "sub_communities" (what the refinement made of P: the next level's vertices), "rounds" (of the move phase), "refine_rounds"}, ...],
+    "seed"; with ret_levels each level also carries "membership" (the 1-based rank of the community P of every input vertex).  The run
+    ends at the first level whose refinement merges nothing, or at max_levels; the last level's P, split into its connected components,
+    is returned.  max_refine_rounds (1 .. 100000): the cap on a level's refinement rounds."""
+    who = "leiden_graph"
+    a = _limits(who, resolution, tol, max_levels, max_rounds, max_fails, seed)
+    mrr = _refine_limit(who, max_refine_rounds)
+    rp, cc, vv = _symmetric_csr(row_ptr, col, val, who)
+    n = rp.size - 1
+    _lib.ensure_init()
+    o = _LeidenOut(n, a[2], ret_levels)
+    check(lib().sharp_leiden_graph(i64(rp), i32(cc), f64(vv), n, a[0], a[1], a[2], a[3], a[4], mrr, float(a[5]), *o.args()))
+    return o.result(a[5])
+
+
+def leiden_neighbors(index, distance, squared=False, resolution=1.0, seed=10, tol=1e-7, max_levels=20, max_rounds=200, max_fails=4,
+                     max_refine_rounds=200, ret_levels=False):
+    """Leiden on the fuzzy graph of neighbour lists the caller already has (louvain_neighbors' input): the graph is built on the device
+    and never leaves it.  The result is leiden_graph's."""
+    who = "leiden_neighbors"
+    a = _limits(who, resolution, tol, max_levels, max_rounds, max_fails, seed)
+    mrr = _refine_limit(who, max_refine_rounds)
+    index, distance = _neighbour_arrays(index, distance, who)
+    n, K = index.shape
+    if n > _MAX_N:
+        raise SharpError(f"{who}: need 2 <= n <= {_MAX_N} rows")
+    _lib.ensure_init()
+    o = _LeidenOut(n, a[2], ret_levels)
+    check(lib().sharp_leiden_neighbors(i32(index), f64(distance), n, int(K), int(bool(squared)), a[0], a[1], a[2], a[3], a[4], mrr, float(a[5]),
+                                       *o.args()))
+    return o.result(a[5])
+
+
+def leiden_snn(index, prune=PRUNE, resolution=1.0, seed=10, tol=1e-7, max_levels=20, max_rounds=200, max_fails=4, max_refine_rounds=200,
+               ret_levels=False):
+    """Leiden on the SNN graph of neighbour lists the caller already has (louvain_snn's input): snn_graph(index, prune)'s graph, built on
+    the device.  The result is leiden_graph's on that graph, bit for bit."""
+    who = "leiden_snn"
+    a = _limits(who, resolution, tol, max_levels, max_rounds, max_fails, seed)
+    mrr = _refine_limit(who, max_refine_rounds)
+    prune = _prune(prune, who)
+    index = _lists(index, who)
+    n, K = index.shape
+    _lib.ensure_init()
+    o = _LeidenOut(n, a[2], ret_levels)
+    check(lib().sharp_leiden_snn(i32(index), n, int(K), prune, a[0], a[1], a[2], a[3], a[4], mrr, float(a[5]), *o.args()))
+    return o.result(a[5])
+
+
+def leiden(X, n_neighbors=15, resolution=1.0, nn_method="exact", nn_args=None, pca=None, seed=10, tol=1e-7, max_levels=20,
+           ret_levels=False, ret_nn=False, pca_center=True, max_rounds=200, max_fails=4, graph="fuzzy", prune=None, max_refine_rounds=200):
+    """Leiden on the neighbour graph of the rows of X, as sc.tl.leiden runs it on scanpy's connectivities (graph="snn": as Seurat's
+    FindClusters(algorithm = 4) on its SNN graph).  louvain()'s arguments, preparation and search; the result is leiden_neighbors' (or
+    leiden_snn's) on those lists; with ret_nn it also carries "nn"."""
+    who = "leiden"
+    prune = _graph_choice(who, nn_method, nn_args, graph, prune)
+    a = _limits(who, resolution, tol, max_levels, max_rounds, max_fails, seed)
+    mrr = _refine_limit(who, max_refine_rounds)
+    idx, dist, method = _search(X, n_neighbors, nn_method, nn_args, pca, pca_center, who)
+    kw = dict(resolution=a[0], seed=a[5], tol=a[1], max_levels=a[2], max_rounds=a[3], max_fails=a[4], max_refine_rounds=mrr, ret_levels=ret_levels)
+    out = leiden_snn(idx, prune, **kw) if graph == "snn" else leiden_neighbors(idx, dist, **kw)
     if ret_nn:
         out["nn"] = {"index": idx, "distance": dist}
         if method == "descent":
@@ -253,3 +366,38 @@ def _aggregate(row_ptr, col, q, comm):
     nnz, nc = C.c_longlong(), C.c_longlong()
     check(lib().sharp_louvain_aggregate(i64(rp), i32(cc), i64(qq), n, i32(comm), i64(orp), i32(oc), i64(oq), C.byref(nnz), C.byref(nc), i32(new)))
     return orp[: nc.value + 1].copy(), oc[: nnz.value].copy(), oq[: nnz.value].copy(), new
+
+
+def _leiden_level(row_ptr, col, q, comm0, resolution=1.0, seed=10, level=0, tol=1e-7, max_rounds=200, max_fails=4):
+    """(comm, rounds, Q): a level's move phase from comm0 (sharp_leiden_level)"""
+    rp, cc, qq = _int_csr(row_ptr, col, q)
+    n = rp.size - 1
+    comm0 = np.ascontiguousarray(comm0, np.int32)
+    _lib.ensure_init()
+    comm, rounds, Q = np.zeros(n, np.int32), C.c_int(), C.c_double()
+    check(lib().sharp_leiden_level(i64(rp), i32(cc) if cc.size else None, i64(qq) if qq.size else None, n, i32(comm0), float(resolution),
+                                   float(tol), int(max_rounds), int(max_fails), float(seed), int(level), i32(comm), C.byref(rounds), C.byref(Q)))
+    return comm, rounds.value, Q.value
+
+
+def _leiden_refine(row_ptr, col, q, P, ref, resolution=1.0, seed=10, level=0, rnd=0):
+    """(proposal, moved, wanting) of one refinement round from the state ref inside P (sharp_leiden_refine)"""
+    rp, cc, qq = _int_csr(row_ptr, col, q)
+    n = rp.size - 1
+    P, ref = np.ascontiguousarray(P, np.int32), np.ascontiguousarray(ref, np.int32)
+    _lib.ensure_init()
+    prop, moved, wanting = np.zeros(n, np.int32), C.c_longlong(), C.c_longlong()
+    check(lib().sharp_leiden_refine(i64(rp), i32(cc) if cc.size else None, i64(qq) if qq.size else None, n, i32(P), i32(ref), float(resolution),
+                                    float(seed), int(level), int(rnd), i32(prop), C.byref(moved), C.byref(wanting)))
+    return prop, moved.value, wanting.value
+
+
+def _leiden_split(row_ptr, col, q, label):
+    """(out, count): the components inside a labelling, named by their smallest vertex (sharp_leiden_split)"""
+    rp, cc, qq = _int_csr(row_ptr, col, q)
+    n = rp.size - 1
+    label = np.ascontiguousarray(label, np.int32)
+    _lib.ensure_init()
+    out, count = np.zeros(n, np.int32), C.c_longlong()
+    check(lib().sharp_leiden_split(i64(rp), i32(cc) if cc.size else None, i64(qq) if qq.size else None, n, i32(label), i32(out), C.byref(count)))
+    return out, count.value

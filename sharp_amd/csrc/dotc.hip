@@ -400,6 +400,58 @@ void sharp_C_louvain_modularity(double *row_ptr, int *col, double *val, double *
     *status = sharp_louvain_modularity(rp.data(), col, val, nullptr, nn, membership, *resolution, Q);
 }
 
+/* Leiden (sharp_leiden_graph, sharp_leiden_neighbors, sharp_leiden_snn): as the Louvain entries; levels: level_cap rows of (n,
+ * communities, sub-communities, rounds, refine rounds, modularity) */
+struct LeidenLevelsOut {
+    std::vector<long long> ln, lc, ls;
+    std::vector<int> lr, lf;
+    std::vector<double> lq;
+    explicit LeidenLevelsOut(int level_cap) {
+        const size_t cap = level_cap > 0 ? static_cast<size_t>(level_cap) : 1;
+        ln.resize(cap); lc.resize(cap); ls.resize(cap); lr.resize(cap); lf.resize(cap); lq.resize(cap);
+    }
+    void write(int status, int nl, double *levels) const {
+        if (status != 0) return;
+        for (int l = 0; l < nl; ++l) {
+            levels[6 * l] = static_cast<double>(ln[l]);
+            levels[6 * l + 1] = static_cast<double>(lc[l]);
+            levels[6 * l + 2] = static_cast<double>(ls[l]);
+            levels[6 * l + 3] = static_cast<double>(lr[l]);
+            levels[6 * l + 4] = static_cast<double>(lf[l]);
+            levels[6 * l + 5] = lq[l];
+        }
+    }
+};
+void sharp_C_leiden_graph(double *row_ptr, int *col, double *val, double *n, double *resolution, double *tol, int *max_levels, int *max_rounds,
+                          int *max_fails, int *max_refine_rounds, double *seed, int *membership, double *modularity, int *level_cap, double *levels,
+                          int *n_levels, int *want_levels, int *level_membership, int *status) {
+    const long long nn = as_ll(n);
+    const std::vector<long long> rp = row_ptr_ll(row_ptr, nn);
+    LeidenLevelsOut o(*level_cap);
+    *status = sharp_leiden_graph(rp.data(), col, val, nn, *resolution, *tol, *max_levels, *max_rounds, *max_fails, *max_refine_rounds, *seed,
+                                 membership, modularity, *level_cap, o.ln.data(), o.lc.data(), o.ls.data(), o.lr.data(), o.lf.data(), o.lq.data(),
+                                 n_levels, *want_levels ? level_membership : nullptr);
+    o.write(*status, *n_levels, levels);
+}
+void sharp_C_leiden_neighbors(int *index, double *distance, double *n, int *K, int *squared, double *resolution, double *tol, int *max_levels,
+                              int *max_rounds, int *max_fails, int *max_refine_rounds, double *seed, int *membership, double *modularity,
+                              int *level_cap, double *levels, int *n_levels, int *want_levels, int *level_membership, int *status) {
+    LeidenLevelsOut o(*level_cap);
+    *status = sharp_leiden_neighbors(index, distance, as_ll(n), *K, *squared, *resolution, *tol, *max_levels, *max_rounds, *max_fails,
+                                     *max_refine_rounds, *seed, membership, modularity, *level_cap, o.ln.data(), o.lc.data(), o.ls.data(),
+                                     o.lr.data(), o.lf.data(), o.lq.data(), n_levels, *want_levels ? level_membership : nullptr);
+    o.write(*status, *n_levels, levels);
+}
+void sharp_C_leiden_snn(int *index, double *n, int *K, double *prune, double *resolution, double *tol, int *max_levels, int *max_rounds,
+                        int *max_fails, int *max_refine_rounds, double *seed, int *membership, double *modularity, int *level_cap, double *levels,
+                        int *n_levels, int *want_levels, int *level_membership, int *status) {
+    LeidenLevelsOut o(*level_cap);
+    *status = sharp_leiden_snn(index, as_ll(n), *K, *prune, *resolution, *tol, *max_levels, *max_rounds, *max_fails, *max_refine_rounds, *seed,
+                               membership, modularity, *level_cap, o.ln.data(), o.lc.data(), o.ls.data(), o.lr.data(), o.lf.data(), o.lq.data(),
+                               n_levels, *want_levels ? level_membership : nullptr);
+    o.write(*status, *n_levels, levels);
+}
+
 /* The SNN graph (sharp_snn_graph: the same count-then-fill protocol) and Louvain on it (sharp_louvain_snn): n, cap, nnz and row_ptr
  * as double; want: 1 fill col / val (0: the count alone), 2 shared as well */
 void sharp_C_snn_graph(int *index, double *n, int *K, double *prune, double *cap, double *row_ptr, int *col, double *val, int *shared, int *want,

@@ -12,6 +12,7 @@
 //                                                n-slot row in HBM that the workgroup owns, integer atomics in, zeroed again on the way out
 //              The table's slot order, the order of the atomics and the row class do not reach the result: kin is an integer sum and
 //              the arg-max is a reduction under a total order.
+//              (The table, the probe, the gain and the arg-max are louvain_dev.hpp's, shared with Leiden's refine kernels.)
 //   state      tot and in by int64 global atomics, the surviving communities counted and ranked by a scan, the fp64 terms
 //              in / 2m - gamma (tot / 2m)^2 written at their ranks and sorted by value (rocprim radix sort: Q is a function of the partition, not of its labels)
 //              and summed by graph.hpp's two-stage fixed-order reduction (no floating-point atomic).  The host reads Q and the
@@ -20,6 +21,7 @@
 //              binary search
 #include "louvain.hpp"
 #include "graph_prim.hpp"
+#include "louvain_dev.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -33,12 +35,6 @@
 
 namespace sharp {
 namespace {
-
-// x1 = mix(mix(seed * golden + level) + round); h(c) = the top bit of mix(x1 + c)
-inline u64 round_key(u64 seed, int level, int round) {
-    return mix64(mix64(seed * 0x9E3779B97F4A7C15ull + static_cast<u64>(level)) + static_cast<u64>(round));
-}
-__device__ __forceinline__ bool hbit(u64 x1, int c) { return (mix64(x1 + static_cast<u64>(c)) >> 63) != 0; }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // quantise, rows, strengths
@@ -90,37 +86,6 @@ __global__ __launch_bounds__(256) void lv_strength_kernel(const int *__restrict_
 // ---------------------------------------------------------------------------------------------------------------------------
 // move
 // ---------------------------------------------------------------------------------------------------------------------------
-constexpr int kNone = INT_MAX;
-struct Best { double g; int c; };
-// the total order of the arg-max: a candidate beats none; then the larger gain; then the lower id
-__device__ __forceinline__ bool better(double g, int c, const Best &b) { return c != kNone && (b.c == kNone || g > b.g || (g == b.g && c < b.c)); }
-
-__device__ __forceinline__ void wave_best(Best &b, long long &kin0) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double og = __shfl_xor(b.g, off);
-        const int oc = __shfl_xor(b.c, off);
-        const long long ok = __shfl_xor(kin0, off);
-        if (better(og, oc, b)) { b.g = og; b.c = oc; }
-        kin0 = ok > kin0 ? ok : kin0;
-    }
-}
-
-// gain(c) = (double)kin - ((gamma * (double)k_v) * (double)tot') / (double)(2m), in this order
-__device__ __forceinline__ double gain_of(long long kin, double gk, long long totp, double m2) {
-    return static_cast<double>(kin) - (gk * static_cast<double>(totp)) / m2;
-}
-
-template <int GROUP>
-__device__ __forceinline__ void group_sync() {
-    if (GROUP == 64) {
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-    } else {
-        __syncthreads();
-    }
-}
-
 // GROUP lanes per row (64: a wave, four rows per workgroup; 256: the workgroup), a table of SLOTS > the row's entries.  rows: the ids
 // of the class's rows.  prop holds comm on entry; a vertex that moves overwrites its slot.
 template <int GROUP, int SLOTS>
@@ -131,56 +96,39 @@ __global__ __launch_bounds__(256) void lv_move_lds_kernel(const int *__restrict_
     constexpr int G = 256 / GROUP;
     __shared__ int keys[G][SLOTS];
     __shared__ u64 vals[G][SLOTS];
-    __shared__ double red_g[4];
-    __shared__ int red_c[4];
-    __shared__ long long red_k[4];
+    __shared__ LvRed red;
     const int g = threadIdx.x / GROUP, lane = threadIdx.x % GROUP;
     const int ri = blockIdx.x * G + g;
     if (ri >= nrows) return;                               // (GROUP 64: whole waves leave; GROUP 256: the grid is nrows)
     const int v = rows[ri];
     const int c0 = comm[v];
-    if (!hbit(x1, c0)) return;                             // a closed source: v stays (uniform over the group)
-    for (int s = lane; s < SLOTS; s += GROUP) { keys[g][s] = -1; vals[g][s] = 0; }
-    group_sync<GROUP>();
+    if (!lv_hbit(x1, c0)) return;                          // a closed source: v stays (uniform over the group)
+    lv_table_clear<GROUP, SLOTS>(keys[g], vals[g], lane);
+    lv_group_sync<GROUP>();
     const long long b0 = rp[v], e1 = rp[v + 1];
     for (long long e = b0 + lane; e < e1; e += GROUP) {
         const int u = col[e];
         if (u == v) continue;                              // v's own self-loop
-        const int c = comm[u];
-        unsigned s = (static_cast<unsigned>(c) * 0x9E3779B1u) & (SLOTS - 1);
-        for (;;) {                                         // (fewer distinct keys than slots: the probe ends)
-            const int prev = atomicCAS(&keys[g][s], -1, c);
-            if (prev == -1 || prev == c) { atomicAdd(&vals[g][s], q[e]); break; }
-            s = (s + 1) & (SLOTS - 1);
-        }
+        lv_table_add<SLOTS>(keys[g], vals[g], comm[u], q[e]);
     }
-    group_sync<GROUP>();
+    lv_group_sync<GROUP>();
     const long long kv = static_cast<long long>(k[v]);
     const double gk = gamma * static_cast<double>(kv);
-    Best b{0.0, kNone};
+    LvBest b{0.0, kLvNone};
     long long kin0 = 0;
     for (int s = lane; s < SLOTS; s += GROUP) {
         const int c = keys[g][s];
         if (c < 0) continue;
         const long long kin = static_cast<long long>(vals[g][s]);
         if (c == c0) { kin0 = kin; continue; }
-        if (hbit(x1, c)) continue;                         // a closed target
-        const double gn = gain_of(kin, gk, static_cast<long long>(tot[c]), m2);
-        if (better(gn, c, b)) { b.g = gn; b.c = c; }
+        if (lv_hbit(x1, c)) continue;                      // a closed target
+        const double gn = lv_gain(kin, gk, static_cast<long long>(tot[c]), m2);
+        if (lv_better(gn, c, b)) { b.g = gn; b.c = c; }
     }
-    wave_best(b, kin0);
-    if (GROUP == 256) {
-        const int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { red_g[w] = b.g; red_c[w] = b.c; red_k[w] = kin0; }
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (int o = 1; o < 4; ++o) {
-                if (better(red_g[o], red_c[o], b)) { b.g = red_g[o]; b.c = red_c[o]; }
-                kin0 = red_k[o] > kin0 ? red_k[o] : kin0;
-            }
-    }
-    if (lane == 0 && b.c != kNone) {
-        const double stay = gain_of(kin0, gk, static_cast<long long>(tot[c0]) - kv, m2);
+    lv_wave_best(b, kin0);
+    if (GROUP == 256) lv_block_best(b, kin0, red);
+    if (lane == 0 && b.c != kLvNone) {
+        const double stay = lv_gain(kin0, gk, static_cast<long long>(tot[c0]) - kv, m2);
         if (b.g > stay) prop[v] = b.c;
     }
 }
@@ -192,15 +140,13 @@ __global__ __launch_bounds__(256) void lv_move_dense_kernel(const int *__restric
                                                             const int *__restrict__ col, const u64 *__restrict__ q, const int *__restrict__ comm,
                                                             const u64 *__restrict__ k, const u64 *__restrict__ tot, double gamma, double m2, u64 x1,
                                                             u64 *__restrict__ scratch, long long n, int *__restrict__ prop) {
-    __shared__ double red_g[4];
-    __shared__ int red_c[4];
-    __shared__ long long red_k[4];
+    __shared__ LvRed red;
     u64 *S = scratch + static_cast<long long>(blockIdx.x) * n;
     const int tid = threadIdx.x;
     for (int ri = blockIdx.x; ri < nrows; ri += gridDim.x) {
         const int v = rows[ri];
         const int c0 = comm[v];
-        if (!hbit(x1, c0)) continue;                       // (uniform over the workgroup)
+        if (!lv_hbit(x1, c0)) continue;                    // (uniform over the workgroup)
         const long long b0 = rp[v], e1 = rp[v + 1];
         for (long long e = b0 + tid; e < e1; e += 256) {
             const int u = col[e];
@@ -209,7 +155,7 @@ __global__ __launch_bounds__(256) void lv_move_dense_kernel(const int *__restric
         __syncthreads();
         const long long kv = static_cast<long long>(k[v]);
         const double gk = gamma * static_cast<double>(kv);
-        Best b{0.0, kNone};
+        LvBest b{0.0, kLvNone};
         long long kin0 = 0;
         for (long long e = b0 + tid; e < e1; e += 256) {
             const int u = col[e];
@@ -218,25 +164,20 @@ __global__ __launch_bounds__(256) void lv_move_dense_kernel(const int *__restric
             // (an atomic load at device scope: the sums were made by atomics in L2)
             const long long kin = static_cast<long long>(__hip_atomic_load(&S[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
             if (c == c0) { kin0 = kin; continue; }
-            if (hbit(x1, c)) continue;
-            const double gn = gain_of(kin, gk, static_cast<long long>(tot[c]), m2);
-            if (better(gn, c, b)) { b.g = gn; b.c = c; }
+            if (lv_hbit(x1, c)) continue;
+            const double gn = lv_gain(kin, gk, static_cast<long long>(tot[c]), m2);
+            if (lv_better(gn, c, b)) { b.g = gn; b.c = c; }
         }
-        wave_best(b, kin0);
-        if ((tid & 63) == 0) { red_g[tid >> 6] = b.g; red_c[tid >> 6] = b.c; red_k[tid >> 6] = kin0; }
-        __syncthreads();
+        lv_wave_best(b, kin0);
+        lv_block_best(b, kin0, red);
         if (tid == 0) {
-            for (int o = 1; o < 4; ++o) {
-                if (better(red_g[o], red_c[o], b)) { b.g = red_g[o]; b.c = red_c[o]; }
-                kin0 = red_k[o] > kin0 ? red_k[o] : kin0;
-            }
-            if (b.c != kNone) {
-                const double stay = gain_of(kin0, gk, static_cast<long long>(tot[c0]) - kv, m2);
+            if (b.c != kLvNone) {
+                const double stay = lv_gain(kin0, gk, static_cast<long long>(tot[c0]) - kv, m2);
                 if (b.g > stay) prop[v] = b.c;
             }
         }
         for (long long e = b0 + tid; e < e1; e += 256) __hip_atomic_store(&S[comm[col[e]]], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();                                   // (the zeros are in place, red_* are free again)
+        __syncthreads();                                   // (the zeros are in place, red is free again)
     }
 }
 
@@ -330,10 +271,12 @@ __global__ __launch_bounds__(256) void lv_new_kernel(const int *__restrict__ pre
     if (c < n) out[c] = present[c] ? pos[c] : -1;
 }
 
+}  // namespace
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------
-void fill_strengths(LouvainGraph &L) {
+void lv_fill_strengths(LouvainGraph &L) {
     Ctx &c = ctx();
     L.k.alloc(L.n);
     L.k.zero();
@@ -343,40 +286,30 @@ void fill_strengths(LouvainGraph &L) {
     }
 }
 
-// the buffers of a level (sized for its n) and the row classes of its graph
-struct Work {
-    long long n = 0;
-    DevBuf<u64> tot, tot2, in, scratch;
-    DevBuf<int> present, pos;
-    RowClasses rows;
-    DevBuf<double> terms, sorted, part, out;
-    Scratch tmp, tmp_sort;                   // (sized by the level's first lv_state, whose counts are its largest; reused by every round)
-    bool sized = false;
+void LouvainWork::size(long long nn) {
+    n = nn;
+    tot.alloc(n); tot2.alloc(n); in.alloc(n);
+    present.alloc(n + 1); pos.alloc(n + 1);
+    terms.alloc(n); sorted.alloc(n); part.alloc(kRedBlocks); out.alloc(1);
+}
 
-    void size(long long nn) {
-        n = nn;
-        tot.alloc(n); tot2.alloc(n); in.alloc(n);
-        present.alloc(n + 1); pos.alloc(n + 1);
-        terms.alloc(n); sorted.alloc(n); part.alloc(kRedBlocks); out.alloc(1);
+void LouvainWork::classify(const LouvainGraph &L) {
+    std::vector<long long> len(L.n + 1);
+    L.row_ptr.download(len.data(), len.size());
+    for (long long v = 0; v < L.n; ++v) len[v] = len[v + 1] - len[v];
+    len.pop_back();
+    rows.classify(len, kLvWaveCap, kLvBlockCap, true);   // (an empty row has nothing to move by)
+    if (rows.n_dense) {                                // dense rows of n slots each: at most 1 GB in all
+        scratch.alloc(static_cast<size_t>(rows.dense_grid) * L.n);
+        scratch.zero();
     }
-
-    void classify(const LouvainGraph &L) {
-        std::vector<long long> len(L.n + 1);
-        L.row_ptr.download(len.data(), len.size());
-        for (long long v = 0; v < L.n; ++v) len[v] = len[v + 1] - len[v];
-        len.pop_back();
-        rows.classify(len, kLvWaveCap, kLvBlockCap, true);   // (an empty row has nothing to move by)
-        if (rows.n_dense) {                                // dense rows of n slots each: at most 1 GB in all
-            scratch.alloc(static_cast<size_t>(rows.dense_grid) * L.n);
-            scratch.zero();
-        }
-    }
-};
+}
+using Work = LouvainWork;
 
 // tot, present / pos and Q of the membership comm; returns Q and the number of communities.  bound: a number the communities cannot
 // exceed (0: n) -- a round's proposals name communities of the state they start from only, so the accepted state's count bounds them;
 // only that many terms are sorted
-double lv_state(const LouvainGraph &L, const int *comm, u64 *tot, Work &W, double gamma, long long *nc_out, long long bound = 0) {
+double lv_state(const LouvainGraph &L, const int *comm, u64 *tot, Work &W, double gamma, long long *nc_out, long long bound) {
     Ctx &c = ctx();
     KernelTimer t("louvain_state");
     const long long n = L.n;
@@ -452,12 +385,44 @@ void lv_aggregate(const LouvainGraph &L, const int *comm, const Work &W, long lo
     C.col.alloc(m);
     C.row_ptr.alloc(nc + 1);
     merged_to_csr<u64>(ukeys.p, C.nnz, nc, true, C.row_ptr.p, C.col.p, C.row.p);   // (a coarse vertex may be left without entries)
-    fill_strengths(C);
+    lv_fill_strengths(C);
     stream_sync();                                         // (the sort's buffers go out of scope)
 }
 
+double lv_level(const LouvainGraph &L, const LouvainArgs &a, int lev, int *&comm, int *&prop, Work &W, int *rounds_out, long long *nc_out) {
+    u64 *tot = W.tot.p, *tot2 = W.tot2.p;
+    long long nc = 0;
+    double Q = lv_state(L, comm, tot, W, a.resolution, &nc);
+    int rounds = 0, fails = 0;
+    while (rounds < a.max_rounds && fails < a.max_fails) {
+        lv_move(L, comm, tot, W, a.resolution, lv_round_key(a.seed, lev, rounds), prop);
+        ++rounds;
+        long long nc2 = 0;
+        const double Q2 = lv_state(L, prop, tot2, W, a.resolution, &nc2, nc);
+        SHARP_REQUIRE(nc2 <= nc, "louvain: a round made more communities than it started from");
+        if (Q2 > Q + a.tol) {
+            std::swap(comm, prop);
+            std::swap(tot, tot2);
+            Q = Q2;
+            nc = nc2;
+            fails = 0;
+        } else {
+            ++fails;
+        }
+    }
+    lv_state(L, comm, tot, W, a.resolution, &nc, nc);      // the ranks (W.pos) of the accepted membership
+    *rounds_out = rounds;
+    *nc_out = nc;
+    return Q;
+}
+
+void lv_compose(int *vmap, long long n0, const int *comm, const int *pos) {
+    hipLaunchKernelGGL(lv_compose_kernel, dim3(grid_for(n0, 256)), dim3(256), 0, ctx().stream, vmap, n0, comm, pos);
+    launch_check("lv_compose_kernel");
+}
+
 // 1 .. G by decreasing size, ties to the community with the smallest member (SHARP_unlimited's convention)
-void relabel_by_size(const std::vector<int> &lab, long long nc, std::vector<int> &out) {
+void lv_relabel_by_size(const std::vector<int> &lab, long long nc, std::vector<int> &out) {
     std::vector<long long> size(nc, 0), first(nc, -1);
     for (size_t v = 0; v < lab.size(); ++v) {
         if (first[lab[v]] < 0) first[lab[v]] = static_cast<long long>(v);
@@ -471,8 +436,6 @@ void relabel_by_size(const std::vector<int> &lab, long long nc, std::vector<int>
     out.resize(lab.size());
     for (size_t v = 0; v < lab.size(); ++v) out[v] = rank[lab[v]];
 }
-
-}  // namespace
 
 void louvain_quantise(const Graph &G, LouvainGraph &L) {
     Ctx &c = ctx();
@@ -502,7 +465,7 @@ void louvain_quantise(const Graph &G, LouvainGraph &L) {
     hipLaunchKernelGGL(lv_compact_kernel, dim3(grid_for(nnz, 256)), dim3(256), 0, c.stream, pos.p, G.col.p, row.p, q.p, nnz, L.col.p, L.row.p, L.val.p);
     hipLaunchKernelGGL(lv_rowptr_map_kernel, dim3(grid_for(G.n + 1, 256)), dim3(256), 0, c.stream, G.row_ptr.p, pos.p, G.n, L.row_ptr.p);
     launch_check("lv_compact_kernel");
-    fill_strengths(L);
+    lv_fill_strengths(L);
     std::vector<u64> hk(L.n);
     L.k.download(hk.data(), hk.size());                    // (synchronises: the temporaries go out of scope)
     L.m2 = 0;
@@ -511,7 +474,7 @@ void louvain_quantise(const Graph &G, LouvainGraph &L) {
 
 void louvain_run(LouvainGraph &L0, const LouvainArgs &a, std::vector<int> &membership, std::vector<LouvainLevel> &levels,
                  std::vector<int> *level_membership) {
-    Ctx &c = ctx();
+    ctx();
     SHARP_REQUIRE(L0.m2 > 0, "louvain: the graph holds no positive weight");
     const long long n0 = L0.n;
     DevBuf<int> vmap(n0);
@@ -528,29 +491,10 @@ void louvain_run(LouvainGraph &L0, const LouvainArgs &a, std::vector<int> &membe
         W.classify(*L);
         DevBuf<int> comm_a(n), comm_b(n);
         int *comm = comm_a.p, *prop = comm_b.p;
-        u64 *tot = W.tot.p, *tot2 = W.tot2.p;
         iota(comm, n);
-        double Q = lv_state(*L, comm, tot, W, a.resolution, &nc);
-        int rounds = 0, fails = 0;
-        while (rounds < a.max_rounds && fails < a.max_fails) {
-            lv_move(*L, comm, tot, W, a.resolution, round_key(a.seed, lev, rounds), prop);
-            ++rounds;
-            long long nc2 = 0;
-            const double Q2 = lv_state(*L, prop, tot2, W, a.resolution, &nc2, nc);
-            SHARP_REQUIRE(nc2 <= nc, "louvain: a round made more communities than it started from");
-            if (Q2 > Q + a.tol) {
-                std::swap(comm, prop);
-                std::swap(tot, tot2);
-                Q = Q2;
-                nc = nc2;
-                fails = 0;
-            } else {
-                ++fails;
-            }
-        }
-        lv_state(*L, comm, tot, W, a.resolution, &nc, nc);   // the ranks (W.pos) of the accepted membership
-        hipLaunchKernelGGL(lv_compose_kernel, dim3(grid_for(n0, 256)), dim3(256), 0, c.stream, vmap.p, n0, comm, W.pos.p);
-        launch_check("lv_compose_kernel");
+        int rounds = 0;
+        const double Q = lv_level(*L, a, lev, comm, prop, W, &rounds, &nc);
+        lv_compose(vmap.p, n0, comm, W.pos.p);
         LouvainLevel rec;
         rec.n = n; rec.communities = nc; rec.rounds = rounds; rec.q = Q;
         levels.push_back(rec);
@@ -567,16 +511,11 @@ void louvain_run(LouvainGraph &L0, const LouvainArgs &a, std::vector<int> &membe
     }
     std::vector<int> lab(n0);
     vmap.download(lab.data(), n0);
-    relabel_by_size(lab, nc, membership);
+    lv_relabel_by_size(lab, nc, membership);
 }
 
-}  // namespace sharp
 
-using namespace sharp;
-
-namespace {
-
-void check_csr_shape(const std::string &w, const long long *row_ptr, const int *col, long long n) {
+void lv_check_csr_shape(const std::string &w, const long long *row_ptr, const int *col, long long n) {
     SHARP_REQUIRE(row_ptr && col, w + ": null row_ptr / col");
     SHARP_REQUIRE(n >= 2 && n <= kLvMaxN, w + ": need 2 <= n <= 16777216 vertices");
     SHARP_REQUIRE(row_ptr[0] == 0, w + ": row_ptr must start at 0");
@@ -591,8 +530,8 @@ void check_csr_shape(const std::string &w, const long long *row_ptr, const int *
 }
 
 // a float-weighted symmetric CSR without diagonal entries on the device (the input of rule 1)
-void upload_float_graph(const std::string &w, const long long *row_ptr, const int *col, const double *val, long long n, Graph &G) {
-    check_csr_shape(w, row_ptr, col, n);
+void lv_upload_float_graph(const std::string &w, const long long *row_ptr, const int *col, const double *val, long long n, Graph &G) {
+    lv_check_csr_shape(w, row_ptr, col, n);
     SHARP_REQUIRE(val, w + ": null val");
     const long long nnz = row_ptr[n];
     SHARP_REQUIRE(nnz >= 1, w + ": the graph holds no entry");
@@ -621,8 +560,8 @@ void upload_float_graph(const std::string &w, const long long *row_ptr, const in
 }
 
 // an integer-weighted CSR (a level's graph: self-loops allowed) on the device, for the stage entries
-void upload_int_graph(const std::string &w, const long long *row_ptr, const int *col, const long long *q, long long n, LouvainGraph &L) {
-    check_csr_shape(w, row_ptr, col, n);
+void lv_upload_int_graph(const std::string &w, const long long *row_ptr, const int *col, const long long *q, long long n, LouvainGraph &L) {
+    lv_check_csr_shape(w, row_ptr, col, n);
     SHARP_REQUIRE(q, w + ": null q");
     const long long nnz = row_ptr[n];
     long long m2 = 0;
@@ -644,10 +583,10 @@ void upload_int_graph(const std::string &w, const long long *row_ptr, const int 
         hipLaunchKernelGGL(lv_rows_kernel, dim3(grid_for(nnz, 256)), dim3(256), 0, ctx().stream, L.row_ptr.p, n, nnz, L.row.p);
         launch_check("lv_rows_kernel");
     }
-    fill_strengths(L);
+    lv_fill_strengths(L);
 }
 
-void upload_comm(const std::string &w, const int *comm, long long n, DevBuf<int> &d) {
+void lv_upload_comm(const std::string &w, const int *comm, long long n, DevBuf<int> &d) {
     SHARP_REQUIRE(comm, w + ": null membership");
     for (long long v = 0; v < n; ++v) SHARP_REQUIRE(comm[v] >= 0 && comm[v] < n, w + ": a community id outside [0, n)");
     d.alloc(n);
@@ -666,6 +605,12 @@ LouvainArgs louvain_args(const std::string &w, double resolution, double tol, in
     a.seed = static_cast<u64>(static_cast<long long>(seed));
     return a;
 }
+
+}  // namespace sharp
+
+using namespace sharp;
+
+namespace {
 
 void run_and_report(const std::string &w, const Graph &G, const LouvainArgs &a, int *membership, int level_cap, long long *level_n,
                     long long *level_communities, int *level_rounds, double *level_q, int *n_levels, int *level_membership) {
@@ -704,7 +649,7 @@ int sharp_louvain_quantise(const long long *row_ptr, const int *col, const doubl
     const std::string w("sharp_louvain_quantise");
     SHARP_REQUIRE(q && k && m2, w + ": null output");
     Graph G;
-    upload_float_graph(w, row_ptr, col, val, n, G);
+    lv_upload_float_graph(w, row_ptr, col, val, n, G);
     DevBuf<u64> dq(G.nnz);
     DevBuf<long long> flag(G.nnz + 1);
     hipLaunchKernelGGL(lv_quantise_kernel, dim3(grid_for(G.nnz + 1, 256)), dim3(256), 0, c.stream, G.val.p, G.nnz, G.wmax, dq.p, flag.p);
@@ -716,7 +661,7 @@ int sharp_louvain_quantise(const long long *row_ptr, const int *col, const doubl
     hipLaunchKernelGGL(lv_rows_kernel, dim3(grid_for(G.nnz, 256)), dim3(256), 0, c.stream, G.row_ptr.p, n, G.nnz, L.row.p);
     launch_check("lv_rows_kernel");
     L.val = std::move(dq);
-    fill_strengths(L);
+    lv_fill_strengths(L);
     L.val.download(reinterpret_cast<u64 *>(q), G.nnz);
     L.k.download(reinterpret_cast<u64 *>(k), n);
     *m2 = 0;
@@ -733,16 +678,16 @@ int sharp_louvain_move(const long long *row_ptr, const int *col, const long long
     SHARP_REQUIRE(level >= 0 && round >= 0, w + ": level and round must be >= 0");
     const LouvainArgs a = louvain_args(w, resolution, 0.0, 1, 1, 1, seed);
     LouvainGraph L;
-    upload_int_graph(w, row_ptr, col, q, n, L);
+    lv_upload_int_graph(w, row_ptr, col, q, n, L);
     SHARP_REQUIRE(L.m2 > 0, w + ": the graph holds no positive weight");
     DevBuf<int> dcomm, dprop(n);
-    upload_comm(w, comm, n, dcomm);
+    lv_upload_comm(w, comm, n, dcomm);
     Work W;
     W.size(n);
     W.classify(L);
     long long nc = 0;
     lv_state(L, dcomm.p, W.tot.p, W, a.resolution, &nc);
-    lv_move(L, dcomm.p, W.tot.p, W, a.resolution, round_key(a.seed, level, round), dprop.p);
+    lv_move(L, dcomm.p, W.tot.p, W, a.resolution, lv_round_key(a.seed, level, round), dprop.p);
     dprop.download(proposal, n);
     SHARP_API_END
 }
@@ -758,14 +703,14 @@ int sharp_louvain_modularity(const long long *row_ptr, const int *col, const dou
     LouvainGraph L;
     if (val) {
         Graph G;
-        upload_float_graph(w, row_ptr, col, val, n, G);
+        lv_upload_float_graph(w, row_ptr, col, val, n, G);
         louvain_quantise(G, L);
     } else {
-        upload_int_graph(w, row_ptr, col, q, n, L);
+        lv_upload_int_graph(w, row_ptr, col, q, n, L);
         SHARP_REQUIRE(L.m2 > 0, w + ": the graph holds no positive weight");
     }
     DevBuf<int> dcomm;
-    upload_comm(w, membership, n, dcomm);
+    lv_upload_comm(w, membership, n, dcomm);
     Work W;
     W.size(n);
     long long nc = 0;
@@ -780,10 +725,10 @@ int sharp_louvain_aggregate(const long long *row_ptr, const int *col, const long
     const std::string w("sharp_louvain_aggregate");
     SHARP_REQUIRE(row_ptr_out && col_out && q_out && nnz_out && nc_out && new_out, w + ": null output");
     LouvainGraph L, Cg;
-    upload_int_graph(w, row_ptr, col, q, n, L);
+    lv_upload_int_graph(w, row_ptr, col, q, n, L);
     SHARP_REQUIRE(L.nnz >= 1, w + ": the graph holds no entry");
     DevBuf<int> dcomm, dnew(n);
-    upload_comm(w, comm, n, dcomm);
+    lv_upload_comm(w, comm, n, dcomm);
     Work W;
     W.size(n);
     long long nc = 0;
@@ -810,7 +755,7 @@ int sharp_louvain_graph(const long long *row_ptr, const int *col, const double *
     const LouvainArgs a = louvain_args(w, resolution, tol, max_levels, max_rounds, max_fails, seed);
     SHARP_REQUIRE(level_cap >= max_levels, w + ": level_cap must be at least max_levels");
     Graph G;
-    upload_float_graph(w, row_ptr, col, val, n, G);
+    lv_upload_float_graph(w, row_ptr, col, val, n, G);
     run_and_report(w, G, a, membership, level_cap, level_n, level_communities, level_rounds, level_q, n_levels, level_membership);
     SHARP_API_END
 }

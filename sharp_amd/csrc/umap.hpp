@@ -35,6 +35,10 @@ struct UmapSpectral {
 };
 // the number of connected components of G's pattern; label (n, device) = the smallest vertex of each vertex's component when wanted
 long long umap_components(const UmapGraph &G, DevBuf<int> *label = nullptr);
+// the same sweeps on any CSR pattern on the device (1 <= n < 2^31): label[i] = the smallest vertex of i's component; within (n, device,
+// or null): only the entries whose two ends carry the same value count -- the components inside a labelling (Leiden).
+// Self-loops never count.  timer: the name the sweeps are timed under.  Returns the number of components.
+long long csr_components(const long long *row_ptr, const int *col, long long n, const int *within, DevBuf<int> &label, const char *timer);
 // tol <= 0 / max_steps <= 0: the library's defaults (1e-6, 400); max_steps is capped at n - 2
 void umap_spectral(const UmapGraph &G, int dims, double tol, int max_steps, UmapSpectral &R);
 // what the calling context's last sharp_umap / sharp_umap_neighbors call started from (init codes: 0 pca, 1 random, 2 Y_init,

@@ -38,14 +38,19 @@ __global__ __launch_bounds__(256) void cc_init_kernel(int *__restrict__ label, i
 
 // One wave per row.  prev holds the sweep's starting labels (every tree is flat: prev[i] is i's root) and is only read; the roots'
 // entries of label are lowered.  An edge is taken in both directions, so a pattern that is not symmetric is treated as undirected.
+// WITHIN: only the entries whose two ends carry the same value of `within` count (the components inside a labelling).
+template <bool WITHIN>
 __global__ __launch_bounds__(256) void cc_hook_kernel(const long long *__restrict__ rp, const int *__restrict__ col, const int *__restrict__ prev,
-                                                      int *__restrict__ label, long long n, int *__restrict__ changed) {
+                                                      int *__restrict__ label, long long n, int *__restrict__ changed,
+                                                      const int *__restrict__ within) {
     const int lane = threadIdx.x & 63;
     const long long i = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
     const int li = prev[i];
     const long long e1 = rp[i + 1];
+    const int wi = WITHIN ? within[i] : 0;
     for (long long e = rp[i] + lane; e < e1; e += 64) {
+        if (WITHIN && within[col[e]] != wi) continue;
         const int lj = prev[col[e]];
         if (lj < li) {
             atomicMin(&label[li], lj);
@@ -280,21 +285,27 @@ UmapInitInfo &umap_init_info() { return per_slot<UmapInitInfo>(); }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 long long umap_components(const UmapGraph &G, DevBuf<int> *label_out) {
+    SHARP_REQUIRE(G.n >= 1 && G.n < INT_MAX, "umap_components: need 1 <= n < 2^31 rows");
+    DevBuf<int> label_l;
+    return csr_components(G.row_ptr.p, G.col.p, G.n, nullptr, label_out ? *label_out : label_l, "umap_components");
+}
+
+long long csr_components(const long long *row_ptr, const int *col, long long n, const int *within, DevBuf<int> &label, const char *timer) {
     Ctx &c = ctx();
-    const long long n = G.n;
-    SHARP_REQUIRE(n >= 1 && n < INT_MAX, "umap_components: need 1 <= n < 2^31 rows");
-    DevBuf<int> label_l, prev(n), flag(1);
-    DevBuf<int> &label = label_out ? *label_out : label_l;
+    DevBuf<int> prev(n), flag(1);
     label.alloc(n);
     hipLaunchKernelGGL(cc_init_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c.stream, label.p, prev.p, n);
     launch_check("cc_init_kernel");
     // a sweep at least halves the trees of a path, and a flat tree per component is the fixed point; n sweeps are never needed
     for (long long sweep = 0;; ++sweep) {
-        SHARP_REQUIRE(sweep <= n, "umap_components: the sweeps did not end");
-        KernelTimer t("umap_components");
+        SHARP_REQUIRE(sweep <= n, std::string(timer) + ": the sweeps did not end");
+        KernelTimer t(timer);
         int changed = 0;
         flag.zero();
-        hipLaunchKernelGGL(cc_hook_kernel, dim3(grid_for(n, 4)), dim3(256), 0, c.stream, G.row_ptr.p, G.col.p, prev.p, label.p, n, flag.p);
+        if (within)
+            hipLaunchKernelGGL(cc_hook_kernel<true>, dim3(grid_for(n, 4)), dim3(256), 0, c.stream, row_ptr, col, prev.p, label.p, n, flag.p, within);
+        else
+            hipLaunchKernelGGL(cc_hook_kernel<false>, dim3(grid_for(n, 4)), dim3(256), 0, c.stream, row_ptr, col, prev.p, label.p, n, flag.p, within);
         launch_check("cc_hook_kernel");
         flag.download(&changed, 1);
         if (!changed) break;
