@@ -638,6 +638,41 @@ int sharp_leiden_refine(const long long *row_ptr, const int *col, const long lon
                         double seed, int level, int round, int *proposal, long long *moved, long long *wanting);
 int sharp_leiden_split(const long long *row_ptr, const int *col, const long long *q, long long n, const int *label, int *out, long long *count);
 
+/* ---- Diffusion maps and diffusion pseudotime on the neighbour graph (sharp_amd/csrc/diffmap.hip) ---------------
+ * The project's own specification, modelled on scanpy's tl.diffmap / tl.dpt and Haghverdi et al. 2016; no parity with scanpy or destiny
+ * is claimed.  W: a symmetric CSR (sharp_umap_spectral's input: weights >= 0, finite, every non-empty row's sum positive), q_i =
+ * sum_j W_ij.  density_normalize != 0: K = Q^-1 W Q^-1, z_i = sum_j K_ij, T = Z^-1/2 K Z^-1/2; 0: K = W, z = q (T is then
+ * sharp_umap_spectral's M).  T is applied as (T x)_i = a_i sum_j W_ij a_j x_j with a_i = 1 / (q_i sqrt(z_i)) (or 1 / sqrt(q_i)).
+ * sharp_diffmap_graph: the solve runs on ONE connected component: root's when root >= 0, the largest when root = -1 (ties to the
+ * smallest label, a label being the component's smallest vertex); a component with fewer than n_comps + 2 rows is refused.  evals
+ * (n_comps): 1.0, then the n_comps - 1 largest eigenvalues of T below it, descending; evecs (n x n_comps row-major): sqrt(z) / ||sqrt(z)||,
+ * then their unit eigenvectors (each vector's largest |component| positive, ties to the lowest index), NaN in the rows outside the
+ * component; residual (n_comps): the true ||T v - theta v||; in_component (n): 1 / 0.  2 <= n_comps <= 64.  Thick-restart Lanczos with
+ * full reorthogonalisation; tol <= 0: 1e-6; max_matvecs <= 0: 4000 operator applications.  *outcome: 0 every residual <= tol, 2 the cap
+ * was reached (the last Ritz vectors and their true residuals are still returned; not an error status).  *steps: operator applications
+ * of the recurrence; *restarts: rotations of the basis onto its top Ritz vectors.  Two calls give the same bits.
+ * sharp_diffmap_neighbors: the same on the fuzzy graph of neighbour lists (sharp_umap_neighbors' input and graph: index n x K row-major,
+ * 0-based, distance Euclidean, or squared with squared != 0); the graph is built on the device and never leaves it; the result is
+ * sharp_diffmap_graph's on sharp_umap_graph's CSR, bit for bit.
+ * Stages (tests).  sharp_diffmap_transitions: a and z (n each; 0 for an empty row).  sharp_diffmap_component: the chosen label, the
+ * number of components, the component as a CSR of its own (sub_row_ptr: room for n + 1, sub_col / sub_val: room for row_ptr[n]; rows and
+ * columns renumbered in ascending order of the old ids) and new_id (n; -1 outside); the same refusal by size.
+ * sharp_dpt: out (n x n_roots row-major) = sqrt(sum_{l=1}^{n_dcs-1} (evals_l / (1 - evals_l) (evecs[root, l] - evecs[i, l]))^2), l
+ * ascending; inf for a row of NaN; normalize != 0: each root's column divided by its largest finite value.  2 <= n_dcs <= n_comps;
+ * roots 0-based, inside the solved component. */
+int sharp_diffmap_graph(const long long *row_ptr, const int *col, const double *val, long long n, int n_comps, int density_normalize, long long root,
+                        double tol, int max_matvecs, double *evals, double *evecs, double *residual, int *in_component, int *steps, int *restarts,
+                        long long *components, long long *component_size, int *outcome);
+int sharp_diffmap_neighbors(const int *index, const double *distance, long long n, int K, int squared, int n_comps, int density_normalize,
+                            long long root, double tol, int max_matvecs, double *evals, double *evecs, double *residual, int *in_component,
+                            int *steps, int *restarts, long long *components, long long *component_size, int *outcome);
+int sharp_diffmap_transitions(const long long *row_ptr, const int *col, const double *val, long long n, int density_normalize, double *a, double *z);
+int sharp_diffmap_component(const long long *row_ptr, const int *col, const double *val, long long n, int n_comps, long long root, int *label,
+                            long long *components, long long *sub_n, long long *sub_nnz, long long *sub_row_ptr, int *sub_col, double *sub_val,
+                            int *new_id);
+int sharp_dpt(const double *evals, const double *evecs, long long n, int n_comps, int n_dcs, const int *roots, int n_roots, int normalize,
+              double *out);
+
 /* ---- The SNN / Jaccard neighbour graph (sharp_amd/csrc/snn.hip) ------------------------------------------------
  * index: n x K row-major, 0-based, each row K other rows, no index twice in a row (sharp_tsne_knn's and sharp_knn_descent's lists;
  * validated on the device before an index is dereferenced: range, self, twice).  2 <= n <= 16777216, 1 <= K <= 255, K <= n - 1.
@@ -1110,6 +1145,19 @@ void sharp_C_scrublet_csc(int *pcat, int *icat, double *xcat, int *nblocks, doub
                           int *predicted, double *threshold_out, int *threshold_found, double *rates, int *n_neighbors_out, int *k_adj_out,
                           int *parents, int *genes_out, int *n_genes_out, int *neighbor_counts, int *want_sim_pca, double *sim_pca,
                           int *status);
+/* sharp_diffmap_graph / sharp_diffmap_transitions / sharp_diffmap_component / sharp_dpt in the same convention: row_ptr (n + 1 values),
+ * n, root, the counts and sub_row_ptr as double; col, roots and new_id 0-based */
+void sharp_C_diffmap_graph(double *row_ptr, int *col, double *val, double *n, int *n_comps, int *density_normalize, double *root, double *tol,
+                           int *max_matvecs, double *evals, double *evecs, double *residual, int *in_component, int *steps, int *restarts,
+                           double *components, double *component_size, int *outcome, int *status);
+void sharp_C_diffmap_neighbors(int *index, double *distance, double *n, int *K, int *squared, int *n_comps, int *density_normalize, double *root,
+                               double *tol, int *max_matvecs, double *evals, double *evecs, double *residual, int *in_component, int *steps,
+                               int *restarts, double *components, double *component_size, int *outcome, int *status);
+void sharp_C_diffmap_transitions(double *row_ptr, int *col, double *val, double *n, int *density_normalize, double *a, double *z, int *status);
+void sharp_C_diffmap_component(double *row_ptr, int *col, double *val, double *n, int *n_comps, double *root, int *label, double *components,
+                               double *sub_n, double *sub_nnz, double *sub_row_ptr, int *sub_col, double *sub_val, int *new_id, int *status);
+void sharp_C_dpt(double *evals, double *evecs, double *n, int *n_comps, int *n_dcs, int *roots, int *n_roots, int *normalize, double *out,
+                 int *status);
 
 #ifdef __cplusplus
 }

@@ -1042,3 +1042,54 @@ sharp_leiden_graph <- function(row_ptr, col, val, resolution = 1, seed = 10, tol
     .sharp_check(r$status)
     .sharp_leiden_result(r, n, ret_levels)
 }
+
+# ---- diffusion maps and diffusion pseudotime on the neighbour graph (DESIGN.md 26; scanpy's tl.diffmap / tl.dpt without the branchings).
+# The project's own specification; no parity with scanpy or destiny is claimed.  These wrappers have not been run in R.
+.sharp_diffmap_result <- function(r, n, n_comps, who, density_normalize) {
+    .sharp_check(r$status)
+    if (r$components > 1)
+        warning(sprintf("%s: the graph has %d connected components; the one of %d cells was solved and %d cells are left out", who,
+                        as.integer(r$components), as.integer(r$size), as.integer(n - r$size)))
+    if (r$outcome != 0)
+        warning(sprintf("%s: not converged after %d operator applications: the largest residual is %.3e", who, r$steps, max(r$residual)))
+    list(evals = r$evals, evecs = matrix(r$evecs, n, n_comps, byrow = TRUE), residual = r$residual, converged = r$outcome == 0,
+         steps = r$steps, restarts = r$restarts, components = r$components, component_size = r$size,
+         in_component = as.logical(r$inside), density_normalize = density_normalize)
+}
+
+# X: a matrix (rows are cells), or sharp_knn's list (1-based index, Euclidean distance).  root: NULL (the largest component) or a
+# 1-based cell whose component is solved.  evecs: n x n_comps, NaN in the rows outside the solved component; evals[1] = 1.
+sharp_diffmap <- function(X, n_neighbors = 15L, n_comps = 15L, density_normalize = TRUE, root = NULL, tol = 0, max_matvecs = 0L) {
+    nn <- if (is.list(X) && !is.null(X$index)) X else sharp_knn(.sharp_dmat(X), as.integer(n_neighbors) - 1L)
+    index <- as.matrix(nn$index)
+    n <- nrow(index)
+    nc <- as.integer(n_comps)
+    r <- .C("sharp_C_diffmap_neighbors", as.integer(t(index) - 1L), as.double(t(as.matrix(nn$distance))), as.double(n), as.integer(ncol(index)),
+            0L, nc, as.integer(density_normalize), as.double(if (is.null(root)) -1 else root - 1), as.double(tol), as.integer(max_matvecs),
+            evals = double(nc), evecs = double(n * nc), residual = double(nc), inside = integer(n), steps = integer(1),
+            restarts = integer(1), components = double(1), size = double(1), outcome = integer(1), status = integer(1))
+    .sharp_diffmap_result(r, n, nc, "sharp_diffmap", density_normalize)
+}
+
+# the same on any symmetric graph: sharp_louvain_graph's triple (row_ptr and col 0-based)
+sharp_diffmap_graph <- function(row_ptr, col, val, n_comps = 15L, density_normalize = TRUE, root = NULL, tol = 0, max_matvecs = 0L) {
+    n <- length(row_ptr) - 1L
+    nc <- as.integer(n_comps)
+    r <- .C("sharp_C_diffmap_graph", as.double(row_ptr), as.integer(col), as.double(val), as.double(n), nc, as.integer(density_normalize),
+            as.double(if (is.null(root)) -1 else root - 1), as.double(tol), as.integer(max_matvecs), evals = double(nc),
+            evecs = double(n * nc), residual = double(nc), inside = integer(n), steps = integer(1), restarts = integer(1),
+            components = double(1), size = double(1), outcome = integer(1), status = integer(1))
+    .sharp_diffmap_result(r, n, nc, "sharp_diffmap_graph", density_normalize)
+}
+
+# pseudotime from a sharp_diffmap result: roots 1-based cells inside the solved component -> n x length(roots) (a vector for one root);
+# Inf outside the component; normalize: each root's values divided by their largest finite one
+sharp_dpt <- function(dm, roots, n_dcs = 10L, normalize = TRUE) {
+    n <- nrow(dm$evecs)
+    nc <- ncol(dm$evecs)
+    r <- .C("sharp_C_dpt", as.double(dm$evals), as.double(t(dm$evecs)), as.double(n), as.integer(nc), as.integer(n_dcs),
+            as.integer(roots - 1L), length(roots), as.integer(normalize), out = double(n * length(roots)), status = integer(1), NAOK = TRUE)   # (evecs holds NaN outside the component)
+    .sharp_check(r$status)
+    out <- matrix(r$out, n, length(roots), byrow = TRUE)
+    if (length(roots) == 1L) out[, 1] else out
+}

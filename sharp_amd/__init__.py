@@ -12,6 +12,7 @@ from .validity import calinski_harabasz, cutree, silhouette  # noqa: F401
 from .mapquality import continuity, knn_recall, neighbor_ranks, trustworthiness  # noqa: F401
 from .community import louvain, louvain_graph, louvain_neighbors, louvain_snn, modularity  # noqa: F401
 from .community import leiden, leiden_graph, leiden_neighbors, leiden_snn  # noqa: F401
+from .diffmap import diffmap, diffmap_graph, diffmap_neighbors, dpt  # noqa: F401
 from .snn import snn, snn_graph  # noqa: F401
 from .expr_pca import expression_pca, expression_pca_transform, gene_stats  # noqa: F401
 from .hvg import highly_variable_genes  # noqa: F401

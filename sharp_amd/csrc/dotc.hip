@@ -612,4 +612,48 @@ void sharp_C_scrublet_csc(int *pcat, int *icat, double *xcat, int *nblocks, doub
         for (size_t e = 0; e < par.size(); ++e) parents[e] = static_cast<int>(par[e]);
 }
 
+/* Diffusion maps and pseudotime: the plain entries' bits; row_ptr, n, root and the counts as double */
+void sharp_C_diffmap_graph(double *row_ptr, int *col, double *val, double *n, int *n_comps, int *density_normalize, double *root, double *tol,
+                           int *max_matvecs, double *evals, double *evecs, double *residual, int *in_component, int *steps, int *restarts,
+                           double *components, double *component_size, int *outcome, int *status) {
+    const long long nn = as_ll(n);
+    const std::vector<long long> rp = row_ptr_ll(row_ptr, nn);
+    long long k = 0, cs = 0;
+    *status = sharp_diffmap_graph(rp.data(), col, val, nn, *n_comps, *density_normalize, as_ll(root), *tol, *max_matvecs, evals, evecs, residual,
+                                  in_component, steps, restarts, &k, &cs, outcome);
+    *components = static_cast<double>(k);
+    *component_size = static_cast<double>(cs);
+}
+void sharp_C_diffmap_neighbors(int *index, double *distance, double *n, int *K, int *squared, int *n_comps, int *density_normalize, double *root,
+                               double *tol, int *max_matvecs, double *evals, double *evecs, double *residual, int *in_component, int *steps,
+                               int *restarts, double *components, double *component_size, int *outcome, int *status) {
+    long long k = 0, cs = 0;
+    *status = sharp_diffmap_neighbors(index, distance, as_ll(n), *K, *squared, *n_comps, *density_normalize, as_ll(root), *tol, *max_matvecs,
+                                      evals, evecs, residual, in_component, steps, restarts, &k, &cs, outcome);
+    *components = static_cast<double>(k);
+    *component_size = static_cast<double>(cs);
+}
+void sharp_C_diffmap_transitions(double *row_ptr, int *col, double *val, double *n, int *density_normalize, double *a, double *z, int *status) {
+    const long long nn = as_ll(n);
+    const std::vector<long long> rp = row_ptr_ll(row_ptr, nn);
+    *status = sharp_diffmap_transitions(rp.data(), col, val, nn, *density_normalize, a, z);
+}
+void sharp_C_diffmap_component(double *row_ptr, int *col, double *val, double *n, int *n_comps, double *root, int *label, double *components,
+                               double *sub_n, double *sub_nnz, double *sub_row_ptr, int *sub_col, double *sub_val, int *new_id, int *status) {
+    const long long nn = as_ll(n);
+    const std::vector<long long> rp = row_ptr_ll(row_ptr, nn);
+    std::vector<long long> srp(rp.size(), 0);
+    long long k = 0, sn = 0, snnz = 0;
+    *status = sharp_diffmap_component(rp.data(), col, val, nn, *n_comps, as_ll(root), label, &k, &sn, &snnz, srp.data(), sub_col, sub_val, new_id);
+    *components = static_cast<double>(k);
+    *sub_n = static_cast<double>(sn);
+    *sub_nnz = static_cast<double>(snnz);
+    if (*status == 0)
+        for (long long i = 0; i <= sn; ++i) sub_row_ptr[i] = static_cast<double>(srp[i]);
+}
+void sharp_C_dpt(double *evals, double *evecs, double *n, int *n_comps, int *n_dcs, int *roots, int *n_roots, int *normalize, double *out,
+                 int *status) {
+    *status = sharp_dpt(evals, evecs, as_ll(n), *n_comps, *n_dcs, roots, *n_roots, *normalize, out);
+}
+
 }  // extern "C"
