@@ -850,6 +850,31 @@ int sharp_scrublet_csc(const int *const *colptr, const int *const *rowidx, const
                        int *predicted, double *threshold_out, int *threshold_found, double *rates, int *n_neighbors_out, int *k_adj_out,
                        long long *parents, int *genes_out, int *n_genes_out, int *neighbor_counts, double *sim_pca);
 
+/* ---- rank_genes_groups: per-cluster differential expression (sharp_amd/csrc/rank_genes.hip; the specification is the
+ * project's own, no parity with scanpy or Seurat is claimed) ------------------------------------------------------------------------
+ * The blocks, normalize_total, log1p and genes / n_genes as sharp_expr_pca_sub_csc takes them (the transform runs over all m genes, then
+ * the subset is applied; mk = the kept genes).  labels: one dense code 0 .. n_groups - 1 per cell in the blocks' order, 2 <= n_groups <=
+ * 1024, every code present, n <= 2 097 151 cells.  reference: -1 = each group against all other cells ("rest"), or a code: every other
+ * group against that group alone, ranks taken among the cells of the two groups, the reference's own row NaN.  method: 0 = Wilcoxon
+ * rank sum (normal approximation; tie_correct, continuity 0 / 1), 1 = Welch's t-test (every tested group and the reference side need 2
+ * cells).  Stored and implicit zeros (and -0.0) are one tie group; values are ranked by the full 64-bit double.
+ * Outputs, n_groups x mk row-major (a group's genes are contiguous): scores (z or t), pvals (two-sided), pvals_adj (Benjamini-Hochberg
+ * per group over the mk genes), logfoldchanges, auc (U / (n_g n_ref)), means, means_ref, pct, pct_ref (shares of non-zero values);
+ * group_sizes (n_groups); order (n_groups x n_order, 1 <= n_order <= mk): the genes of each group by score descending, ties to the lower
+ * gene, NaN scores last.  Bitwise reproducible; one block and the same cells cut into several give the same bits.
+ * sharp_rank_sums_csc (stage entry for the tests): the exact integers behind the Wilcoxon test.  rank2 (n_groups x mk) = 2 x the sum of
+ * the group's average ranks within the comparison; ties = the sum of t^3 - t over the comparison's tie groups: mk values for "rest",
+ * n_groups x mk for a reference; nnz_counts (n_groups x mk) = the group's cells with a non-zero value.  With a reference the reference's
+ * rows of all three are left as the caller filled them. */
+int sharp_rank_genes_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks, int m,
+                         const int *labels, int n_groups, int method, int reference, double normalize_total, int log1p, const int *genes,
+                         int n_genes, int tie_correct, int continuity, int n_order, long long *group_sizes, double *scores, double *pvals,
+                         double *pvals_adj, double *logfoldchanges, double *auc, double *means, double *means_ref, double *pct,
+                         double *pct_ref, long long *order);
+int sharp_rank_sums_csc(const int *const *colptr, const int *const *rowidx, const double *const *val, const long long *ncb, int nblocks, int m,
+                        const int *labels, int n_groups, int reference, double normalize_total, int log1p, const int *genes, int n_genes,
+                        long long *rank2, long long *ties, long long *nnz_counts);
+
 /* ---- synthetic inputs (bench / tests; not part of the reference) ------------ */
 /* Counter-based generator, value = f(seed, gene, cell): bit-identical to
  * oracle_synth_value().  Fills dX (fp32, m x ncell column-major, leading dim ld). */
@@ -1158,6 +1183,12 @@ void sharp_C_diffmap_component(double *row_ptr, int *col, double *val, double *n
                                double *sub_n, double *sub_nnz, double *sub_row_ptr, int *sub_col, double *sub_val, int *new_id, int *status);
 void sharp_C_dpt(double *evals, double *evecs, double *n, int *n_comps, int *n_dcs, int *roots, int *n_roots, int *normalize, double *out,
                  int *status);
+/* sharp_rank_genes_csc in the same convention, the blocks as sharp_C_expr_pca_sub_csc takes them: labels 0-based codes, *reference = -1
+ * for "rest", *n_genes = 0 for all genes; group_sizes as double, order as int (0-based genes) */
+void sharp_C_rank_genes_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, int *labels, int *n_groups, int *method,
+                            int *reference, double *normalize_total, int *log1p, int *genes, int *n_genes, int *tie_correct, int *continuity,
+                            int *n_order, double *group_sizes, double *scores, double *pvals, double *pvals_adj, double *logfoldchanges,
+                            double *auc, double *means, double *means_ref, double *pct, double *pct_ref, int *order, int *status);
 
 #ifdef __cplusplus
 }

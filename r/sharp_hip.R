@@ -1093,3 +1093,36 @@ sharp_dpt <- function(dm, roots, n_dcs = 10L, normalize = TRUE) {
     out <- matrix(r$out, n, length(roots), byrow = TRUE)
     if (length(roots) == 1L) out[, 1] else out
 }
+
+# per-group differential expression (DESIGN.md 27): scExp as sharp_expression_pca takes it, groups one label per cell (sort(unique())
+# orders them).  method "wilcoxon" or "t-test"; reference "rest" or one of the labels (its own row is NA).  Returns the levels, the
+# sizes and G x m matrices scores, pvals, pvals.adj, logfoldchanges, auc, means, means.ref, pct, pct.ref; order: G x n.genes, each
+# group's genes (1-based among the kept genes) by score descending, ties to the lower gene.
+sharp_rank_genes_groups <- function(scExp, groups, method = "wilcoxon", reference = "rest", normalize.total = 1e4, log1p = TRUE,
+                                    genes = NULL, tie.correct = TRUE, continuity = FALSE, n.genes = NULL) {
+    who <- "sharp_rank_genes_groups"
+    b <- .sharp_csc_cat(scExp, who)
+    if (length(groups) != sum(b$ncb)) stop(paste0(who, ": groups must hold one label per cell"))
+    levels <- sort(unique(groups))
+    codes <- match(groups, levels) - 1L
+    G <- length(levels)
+    meth <- match(method, c("wilcoxon", "t-test")) - 1L
+    if (is.na(meth)) stop(paste0(who, ": method must be \"wilcoxon\" or \"t-test\""))
+    ref <- if (identical(reference, "rest") && !("rest" %in% levels)) -1L else match(reference, levels) - 1L
+    if (is.na(ref)) stop(paste0(who, ": reference must be \"rest\" or one of the group labels"))
+    g <- if (is.null(genes)) integer(1) else .sharp_genes0(genes, b$m, who)
+    mk <- if (is.null(genes)) b$m else length(g)
+    no <- if (is.null(n.genes)) mk else as.integer(n.genes)
+    tab <- function() double(max(G * mk, 1))
+    r <- .C("sharp_C_rank_genes_csc", as.integer(b$p), as.integer(b$i), b$x, b$nb, b$ncb, b$m, as.integer(codes), G, meth, ref,
+            as.double(if (is.null(normalize.total) || identical(normalize.total, FALSE)) 0 else normalize.total), as.integer(log1p), g,
+            if (is.null(genes)) 0L else mk, as.integer(tie.correct), as.integer(continuity), no, sizes = double(max(G, 1)), scores = tab(),
+            pvals = tab(), padj = tab(), lfc = tab(), auc = tab(), means = tab(), mref = tab(), pct = tab(), pref = tab(),
+            order = integer(max(G * no, 1)), status = integer(1))
+    .sharp_check(r$status)
+    mat <- function(v) matrix(v, G, mk, byrow = TRUE, dimnames = list(levels, NULL))
+    list(groups = levels, group.sizes = r$sizes, scores = mat(r$scores), pvals = mat(r$pvals), pvals.adj = mat(r$padj),
+         logfoldchanges = mat(r$lfc), auc = mat(r$auc), means = mat(r$means), means.ref = mat(r$mref), pct = mat(r$pct), pct.ref = mat(r$pref),
+         order = matrix(r$order, G, no, byrow = TRUE) + 1L, method = method, reference = reference,
+         genes = if (is.null(genes)) NULL else g + 1L)
+}

@@ -18,4 +18,5 @@ from .expr_pca import expression_pca, expression_pca_transform, gene_stats  # no
 from .hvg import highly_variable_genes  # noqa: F401
 from .harmony import batch_of_blocks, harmony_integrate  # noqa: F401
 from .doublets import scrublet, simulate_doublets  # noqa: F401
+from .rank_genes import rank_genes_groups  # noqa: F401
 from . import dist  # noqa: F401,E402  (the multi-GPU module; calling it is R's dist() on the GPU, sharp_amd/tree.py)

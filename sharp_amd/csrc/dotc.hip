@@ -656,4 +656,21 @@ void sharp_C_dpt(double *evals, double *evecs, double *n, int *n_comps, int *n_d
     *status = sharp_dpt(evals, evecs, as_ll(n), *n_comps, *n_dcs, roots, *n_roots, *normalize, out);
 }
 
+/* rank_genes_groups: the plain entry's bits; group_sizes as double, order as int */
+void sharp_C_rank_genes_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, int *labels, int *n_groups, int *method,
+                            int *reference, double *normalize_total, int *log1p, int *genes, int *n_genes, int *tie_correct, int *continuity,
+                            int *n_order, double *group_sizes, double *scores, double *pvals, double *pvals_adj, double *logfoldchanges,
+                            double *auc, double *means, double *means_ref, double *pct, double *pct_ref, int *order, int *status) {
+    const CscList L(pcat, icat, xcat, *nblocks, ncb, status);
+    if (!L.ok) return;
+    const size_t G = static_cast<size_t>(std::max(*n_groups, 0)), no = static_cast<size_t>(std::max(*n_order, 0));
+    std::vector<long long> sizes(G + 1), ord(G * no + 1);                 // (never empty: a bad count is refused by name inside)
+    *status = sharp_rank_genes_csc(L.cp.data(), L.ri.data(), L.vx.data(), L.nc.data(), *nblocks, *m, labels, *n_groups, *method, *reference,
+                                   *normalize_total, *log1p, *n_genes ? genes : nullptr, *n_genes, *tie_correct, *continuity, *n_order,
+                                   sizes.data(), scores, pvals, pvals_adj, logfoldchanges, auc, means, means_ref, pct, pct_ref, ord.data());
+    if (*status != 0) return;
+    for (size_t g = 0; g < G; ++g) group_sizes[g] = static_cast<double>(sizes[g]);
+    for (size_t e = 0; e < G * no; ++e) order[e] = static_cast<int>(ord[e]);
+}
+
 }  // extern "C"
