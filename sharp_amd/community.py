@@ -81,21 +81,42 @@ def _symmetric_csr(row_ptr, col, val, who):
     return rp, cc, vv
 
 
-def _result(n, mem, ln, lc, lr, lq, nl, lm, seed):
-    levels = [{"n": int(ln[i]), "communities": int(lc[i]), "rounds": int(lr[i]), "modularity": float(lq[i])} for i in range(nl)]
-    if lm is not None:
-        for i in range(nl):
-            levels[i]["membership"] = lm[i] + 1
-    return {"membership": mem, "n_communities": levels[-1]["communities"], "modularity": levels[-1]["modularity"], "levels": levels,
-            "seed": seed}
+class _Out:
+    """the output buffers of a sharp_louvain_* or sharp_leiden_* call and the result dict made of them"""
 
+    def __init__(self, n, max_levels, ret_levels, leiden):
+        self.leiden = leiden
+        self.mem = np.zeros(n, np.int32)
+        self.ln, self.lc, self.ls = (np.zeros(max_levels, np.int64) for _ in range(3))
+        self.lr, self.lf = np.zeros(max_levels, np.int32), np.zeros(max_levels, np.int32)
+        self.lq = np.zeros(max_levels)
+        self.lm = np.zeros((max_levels, n), np.int32) if ret_levels else None
+        self.q, self.nl, self.cap = C.c_double(), C.c_int(), max_levels
 
-def _outputs(n, max_levels, ret_levels):
-    mem = np.zeros(n, np.int32)
-    ln, lc = np.zeros(max_levels, np.int64), np.zeros(max_levels, np.int64)
-    lr, lq = np.zeros(max_levels, np.int32), np.zeros(max_levels)
-    lm = np.zeros((max_levels, n), np.int32) if ret_levels else None
-    return mem, ln, lc, lr, lq, lm
+    def args(self):
+        if self.leiden:
+            return (i32(self.mem), C.byref(self.q), self.cap, i64(self.ln), i64(self.lc), i64(self.ls), i32(self.lr), i32(self.lf),
+                    f64(self.lq), C.byref(self.nl), i32(self.lm))
+        return i32(self.mem), self.cap, i64(self.ln), i64(self.lc), i32(self.lr), f64(self.lq), C.byref(self.nl), i32(self.lm)
+
+    def result(self, seed):
+        levels = []
+        for i in range(self.nl.value):
+            lev = {"n": int(self.ln[i]), "communities": int(self.lc[i])}
+            if self.leiden:
+                lev["sub_communities"] = int(self.ls[i])
+            lev["rounds"] = int(self.lr[i])
+            if self.leiden:
+                lev["refine_rounds"] = int(self.lf[i])
+            lev["modularity"] = float(self.lq[i])
+            if self.lm is not None:
+                lev["membership"] = self.lm[i] + 1
+            levels.append(lev)
+        if self.leiden:                                       # of the returned membership, which the last level's P is split into
+            communities, q = int(self.mem.max()), self.q.value
+        else:
+            communities, q = levels[-1]["communities"], levels[-1]["modularity"]
+        return {"membership": self.mem, "n_communities": communities, "modularity": q, "levels": levels, "seed": seed}
 
 
 def louvain_graph(row_ptr, col, val, resolution=1.0, seed=10, tol=1e-7, max_levels=20, max_rounds=200, max_fails=4, ret_levels=False):
@@ -111,11 +132,9 @@ def louvain_graph(row_ptr, col, val, resolution=1.0, seed=10, tol=1e-7, max_leve
     rp, cc, vv = _symmetric_csr(row_ptr, col, val, who)
     n = rp.size - 1
     _lib.ensure_init()
-    mem, ln, lc, lr, lq, lm = _outputs(n, a[2], ret_levels)
-    nl = C.c_int()
-    check(lib().sharp_louvain_graph(i64(rp), i32(cc), f64(vv), n, a[0], a[1], a[2], a[3], a[4], float(a[5]), i32(mem), a[2], i64(ln), i64(lc),
-                                    i32(lr), f64(lq), C.byref(nl), i32(lm)))
-    return _result(n, mem, ln, lc, lr, lq, nl.value, lm, a[5])
+    o = _Out(n, a[2], ret_levels, False)
+    check(lib().sharp_louvain_graph(i64(rp), i32(cc), f64(vv), n, a[0], a[1], a[2], a[3], a[4], float(a[5]), *o.args()))
+    return o.result(a[5])
 
 
 def louvain_neighbors(index, distance, squared=False, resolution=1.0, seed=10, tol=1e-7, max_levels=20, max_rounds=200, max_fails=4,
@@ -130,11 +149,10 @@ def louvain_neighbors(index, distance, squared=False, resolution=1.0, seed=10, t
     if n > _MAX_N:
         raise SharpError(f"{who}: need 2 <= n <= {_MAX_N} rows")
     _lib.ensure_init()
-    mem, ln, lc, lr, lq, lm = _outputs(n, a[2], ret_levels)
-    nl = C.c_int()
+    o = _Out(n, a[2], ret_levels, False)
     check(lib().sharp_louvain_neighbors(i32(index), f64(distance), n, int(K), int(bool(squared)), a[0], a[1], a[2], a[3], a[4], float(a[5]),
-                                        i32(mem), a[2], i64(ln), i64(lc), i32(lr), f64(lq), C.byref(nl), i32(lm)))
-    return _result(n, mem, ln, lc, lr, lq, nl.value, lm, a[5])
+                                        *o.args()))
+    return o.result(a[5])
 
 
 def louvain_snn(index, prune=PRUNE, resolution=1.0, seed=10, tol=1e-7, max_levels=20, max_rounds=200, max_fails=4, ret_levels=False):
@@ -147,11 +165,9 @@ def louvain_snn(index, prune=PRUNE, resolution=1.0, seed=10, tol=1e-7, max_level
     index = _lists(index, who)
     n, K = index.shape
     _lib.ensure_init()
-    mem, ln, lc, lr, lq, lm = _outputs(n, a[2], ret_levels)
-    nl = C.c_int()
-    check(lib().sharp_louvain_snn(i32(index), n, int(K), prune, a[0], a[1], a[2], a[3], a[4], float(a[5]), i32(mem), a[2], i64(ln), i64(lc),
-                                  i32(lr), f64(lq), C.byref(nl), i32(lm)))
-    return _result(n, mem, ln, lc, lr, lq, nl.value, lm, a[5])
+    o = _Out(n, a[2], ret_levels, False)
+    check(lib().sharp_louvain_snn(i32(index), n, int(K), prune, a[0], a[1], a[2], a[3], a[4], float(a[5]), *o.args()))
+    return o.result(a[5])
 
 
 def _graph_choice(who, nn_method, nn_args, graph, prune):
@@ -168,6 +184,24 @@ def _graph_choice(who, nn_method, nn_args, graph, prune):
     return _prune(PRUNE if prune is None else prune, who) if graph == "snn" else prune
 
 
+def _on_rows(who, X, n_neighbors, nn_method, nn_args, pca, pca_center, graph, prune, ret_nn, ret_levels, limits, max_refine_rounds=None):
+    """louvain()'s body, and with max_refine_rounds leiden()'s: the refusals, the search, the clustering of the lists' fuzzy or SNN graph"""
+    prune = _graph_choice(who, nn_method, nn_args, graph, prune)
+    a = _limits(who, *limits)
+    kw = dict(resolution=a[0], seed=a[5], tol=a[1], max_levels=a[2], max_rounds=a[3], max_fails=a[4], ret_levels=ret_levels)
+    on_snn, on_lists = louvain_snn, louvain_neighbors
+    if max_refine_rounds is not None:
+        kw["max_refine_rounds"] = _refine_limit(who, max_refine_rounds)
+        on_snn, on_lists = leiden_snn, leiden_neighbors
+    idx, dist, method = _search(X, n_neighbors, nn_method, nn_args, pca, pca_center, who)
+    out = on_snn(idx, prune, **kw) if graph == "snn" else on_lists(idx, dist, **kw)
+    if ret_nn:
+        out["nn"] = {"index": idx, "distance": dist}
+        if method == "descent":
+            out["nn"]["method"] = "descent"
+    return out
+
+
 def louvain(X, n_neighbors=15, resolution=1.0, nn_method="exact", nn_args=None, pca=None, seed=10, tol=1e-7, max_levels=20,
             ret_levels=False, ret_nn=False, pca_center=True, max_rounds=200, max_fails=4, graph="fuzzy", prune=None):
     """Louvain on the neighbour graph of the rows of X, as sc.tl.louvain runs it on scanpy's connectivities.  The input is prepared and
@@ -176,17 +210,8 @@ def louvain(X, n_neighbors=15, resolution=1.0, nn_method="exact", nn_args=None, 
     louvain_neighbors' on those lists; with ret_nn it also carries "nn": {"index", "distance"}.  graph="snn": the SNN / Jaccard graph
     of those lists instead (n_neighbors is Seurat's k.param; prune in [0, 1], None: 1/15) -- louvain_snn's result.  prune belongs to
     graph="snn"."""
-    who = "louvain"
-    prune = _graph_choice(who, nn_method, nn_args, graph, prune)
-    a = _limits(who, resolution, tol, max_levels, max_rounds, max_fails, seed)
-    idx, dist, method = _search(X, n_neighbors, nn_method, nn_args, pca, pca_center, who)
-    kw = dict(resolution=a[0], seed=a[5], tol=a[1], max_levels=a[2], max_rounds=a[3], max_fails=a[4], ret_levels=ret_levels)
-    out = louvain_snn(idx, prune, **kw) if graph == "snn" else louvain_neighbors(idx, dist, **kw)
-    if ret_nn:
-        out["nn"] = {"index": idx, "distance": dist}
-        if method == "descent":
-            out["nn"]["method"] = "descent"
-    return out
+    return _on_rows("louvain", X, n_neighbors, nn_method, nn_args, pca, pca_center, graph, prune, ret_nn, ret_levels,
+                    (resolution, tol, max_levels, max_rounds, max_fails, seed))
 
 
 # ---- Leiden ---------------------------------------------------------------------------------------------------------------------------
@@ -194,30 +219,6 @@ def _refine_limit(who, max_refine_rounds):
     if not 1 <= int(max_refine_rounds) <= 100000:
         raise SharpError(f"{who}: max_refine_rounds must be in 1 .. 100000")
     return int(max_refine_rounds)
-
-
-class _LeidenOut:
-    """the output buffers of a sharp_leiden_* call and the result dict made of them"""
-
-    def __init__(self, n, max_levels, ret_levels):
-        self.mem = np.zeros(n, np.int32)
-        self.ln, self.lc, self.ls = (np.zeros(max_levels, np.int64) for _ in range(3))
-        self.lr, self.lf = np.zeros(max_levels, np.int32), np.zeros(max_levels, np.int32)
-        self.lq = np.zeros(max_levels)
-        self.lm = np.zeros((max_levels, n), np.int32) if ret_levels else None
-        self.q, self.nl, self.cap = C.c_double(), C.c_int(), max_levels
-
-    def args(self):
-        return (i32(self.mem), C.byref(self.q), self.cap, i64(self.ln), i64(self.lc), i64(self.ls), i32(self.lr), i32(self.lf), f64(self.lq),
-                C.byref(self.nl), i32(self.lm))
-
-    def result(self, seed):
-        levels = [{"n": int(self.ln[i]), "communities": int(self.lc[i]), "sub_communities": int(self.ls[i]), "rounds": int(self.lr[i]),
-                   "refine_rounds": int(self.lf[i]), "modularity": float(self.lq[i])} for i in range(self.nl.value)]
-        if self.lm is not None:
-            for i, lev in enumerate(levels):
-                lev["membership"] = self.lm[i] + 1
-        return {"membership": self.mem, "n_communities": int(self.mem.max()), "modularity": self.q.value, "levels": levels, "seed": seed}
 
 
 def leiden_graph(row_ptr, col, val, resolution=1.0, seed=10, tol=1e-7, max_levels=20, max_rounds=200, max_fails=4, max_refine_rounds=200,
@@ -235,7 +236,7 @@ def leiden_graph(row_ptr, col, val, resolution=1.0, seed=10, tol=1e-7, max_level
     rp, cc, vv = _symmetric_csr(row_ptr, col, val, who)
     n = rp.size - 1
     _lib.ensure_init()
-    o = _LeidenOut(n, a[2], ret_levels)
+    o = _Out(n, a[2], ret_levels, True)
     check(lib().sharp_leiden_graph(i64(rp), i32(cc), f64(vv), n, a[0], a[1], a[2], a[3], a[4], mrr, float(a[5]), *o.args()))
     return o.result(a[5])
 
@@ -252,7 +253,7 @@ def leiden_neighbors(index, distance, squared=False, resolution=1.0, seed=10, to
     if n > _MAX_N:
         raise SharpError(f"{who}: need 2 <= n <= {_MAX_N} rows")
     _lib.ensure_init()
-    o = _LeidenOut(n, a[2], ret_levels)
+    o = _Out(n, a[2], ret_levels, True)
     check(lib().sharp_leiden_neighbors(i32(index), f64(distance), n, int(K), int(bool(squared)), a[0], a[1], a[2], a[3], a[4], mrr, float(a[5]),
                                        *o.args()))
     return o.result(a[5])
@@ -269,7 +270,7 @@ def leiden_snn(index, prune=PRUNE, resolution=1.0, seed=10, tol=1e-7, max_levels
     index = _lists(index, who)
     n, K = index.shape
     _lib.ensure_init()
-    o = _LeidenOut(n, a[2], ret_levels)
+    o = _Out(n, a[2], ret_levels, True)
     check(lib().sharp_leiden_snn(i32(index), n, int(K), prune, a[0], a[1], a[2], a[3], a[4], mrr, float(a[5]), *o.args()))
     return o.result(a[5])
 
@@ -279,18 +280,8 @@ def leiden(X, n_neighbors=15, resolution=1.0, nn_method="exact", nn_args=None, p
     """Leiden on the neighbour graph of the rows of X, as sc.tl.leiden runs it on scanpy's connectivities (graph="snn": as Seurat's
     FindClusters(algorithm = 4) on its SNN graph).  louvain()'s arguments, preparation and search; the result is leiden_neighbors' (or
     leiden_snn's) on those lists; with ret_nn it also carries "nn"."""
-    who = "leiden"
-    prune = _graph_choice(who, nn_method, nn_args, graph, prune)
-    a = _limits(who, resolution, tol, max_levels, max_rounds, max_fails, seed)
-    mrr = _refine_limit(who, max_refine_rounds)
-    idx, dist, method = _search(X, n_neighbors, nn_method, nn_args, pca, pca_center, who)
-    kw = dict(resolution=a[0], seed=a[5], tol=a[1], max_levels=a[2], max_rounds=a[3], max_fails=a[4], max_refine_rounds=mrr, ret_levels=ret_levels)
-    out = leiden_snn(idx, prune, **kw) if graph == "snn" else leiden_neighbors(idx, dist, **kw)
-    if ret_nn:
-        out["nn"] = {"index": idx, "distance": dist}
-        if method == "descent":
-            out["nn"]["method"] = "descent"
-    return out
+    return _on_rows("leiden", X, n_neighbors, nn_method, nn_args, pca, pca_center, graph, prune, ret_nn, ret_levels,
+                    (resolution, tol, max_levels, max_rounds, max_fails, seed), max_refine_rounds)
 
 
 def modularity(row_ptr, col, val, membership, resolution=1.0):

@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "graph_prim.hpp"
-#include "knn.hpp"
+#include "graph_source.hpp"
 #include "prepare.hpp"
 #include "spectral_dev.hpp"
 
@@ -700,14 +700,8 @@ int sharp_diffmap_neighbors(const int *index, const double *distance, long long 
     SHARP_REQUIRE(K >= 1 && K <= 255 && K <= n - 1, w + ": need 1 <= K <= 255 neighbours per row and K <= n - 1");
     diffmap_args(w, n, n_comps, root, tol);
     SHARP_REQUIRE(evals && evecs && residual && in_component && steps && restarts && components && component_size && outcome, w + ": null argument");
-    DevBuf<int> idx;
-    DevBuf<double> dist;
-    upload_neighbours(w.c_str(), index, distance, n, K, true, idx, dist);
-    if (squared) umap_sqrt_lists(dist, n, K);
     Graph G;
-    umap_graph(idx, dist, n, K, G);   // (the fuzzy union of umap_neighbors: it never leaves the device)
-    idx.release();
-    dist.release();
+    fuzzy_graph_from_lists(w, index, distance, n, K, squared != 0, G);   // (the fuzzy union of umap_neighbors: it never leaves the device)
     run_diffmap(w, G, n_comps, density_normalize, root, tol, max_matvecs, evals, evecs, residual, in_component, steps, restarts, components,
                 component_size, outcome);
     SHARP_API_END

@@ -35,6 +35,67 @@ int flashmark_method(int flashmark, int hmethod, int *status) {
     return 1;
 }
 
+/* dense blocks one after the other (unlist(lapply(scExp, as.double)): block b is m x ncb[b] column-major) as the pointer list of the
+ * plain entries */
+struct DenseList {
+    std::vector<const double *> ptrs;
+    std::vector<long long> nc;
+    bool ok = false;
+    DenseList(double *Xcat, int B, double *ncb, int m, int *status) {
+        if (B < 1) { sharp::set_error("No expression data is provided!"); *status = SHARP_ERR_ARG; return; }
+        ptrs.resize(B); nc.resize(B);
+        long long off = 0;
+        for (int b = 0; b < B; ++b) { ptrs[b] = Xcat + off * m; nc[b] = as_ll(ncb + b); off += nc[b]; }
+        ok = true;
+    }
+};
+
+/* a list of dgCMatrix blocks laid out as sharp_C_SHARP_unlimited_csc takes it, as the pointer lists of the plain entries */
+struct CscList {
+    std::vector<const int *> cp, ri;
+    std::vector<const double *> vx;
+    std::vector<long long> nc;
+    bool ok = false;
+    CscList(int *pcat, int *icat, double *xcat, int B, double *ncb, int *status) {
+        if (B < 1) { sharp::set_error("No expression data is provided!"); *status = SHARP_ERR_ARG; return; }
+        cp.resize(B); ri.resize(B); vx.resize(B); nc.resize(B);
+        long long poff = 0, eoff = 0;
+        for (int b = 0; b < B; ++b) {
+            nc[b] = as_ll(ncb + b);
+            if (nc[b] < 0) { sharp::set_error("a block with a negative number of cells"); *status = SHARP_ERR_ARG; return; }
+            cp[b] = pcat + poff; ri[b] = icat + eoff; vx[b] = xcat + eoff;
+            eoff += static_cast<long long>(cp[b][nc[b]]) - cp[b][0];
+            poff += nc[b] + 1;
+        }
+        ok = true;
+    }
+};
+
+/* what the Louvain and Leiden entries write per level, and the caller's table made of it: level_cap rows of (n, communities, rounds,
+ * modularity), for Leiden of (n, communities, sub-communities, rounds, refine rounds, modularity) */
+struct LevelsOut {
+    const bool leiden;
+    std::vector<long long> ln, lc, ls;
+    std::vector<int> lr, lf;
+    std::vector<double> lq;
+    LevelsOut(int level_cap, bool leiden_) : leiden(leiden_) {
+        const size_t cap = level_cap > 0 ? static_cast<size_t>(level_cap) : 1;
+        ln.resize(cap); lc.resize(cap); ls.resize(cap); lr.resize(cap); lf.resize(cap); lq.resize(cap);
+    }
+    void write(int status, int nl, double *levels) const {
+        if (status != 0) return;
+        for (int l = 0; l < nl; ++l) {
+            double *row = levels + (leiden ? 6 : 4) * l;
+            *row++ = static_cast<double>(ln[l]);
+            *row++ = static_cast<double>(lc[l]);
+            if (leiden) *row++ = static_cast<double>(ls[l]);
+            *row++ = static_cast<double>(lr[l]);
+            if (leiden) *row++ = static_cast<double>(lf[l]);
+            *row = lq[l];
+        }
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -151,13 +212,9 @@ void sharp_C_last_rpinfo(int *dims, int *enrp, double *indE, int *want, int *sta
  * info[2]: n_pred, p_used */
 void sharp_C_SHARP_unlimited(double *Xcat, int *nblocks, double *ncb, int *m, int *ensize_K, int *N_cluster, int *minN, int *maxN,
                              double *rN_seed, int *pred, double *viE, int *info, int *want, int *status) {
-    const int B = *nblocks;
-    if (B < 1) { sharp::set_error("No expression data is provided!"); *status = SHARP_ERR_ARG; return; }
-    std::vector<const double *> ptrs(static_cast<size_t>(B));
-    std::vector<long long> nc(static_cast<size_t>(B));
-    long long off = 0;
-    for (int b = 0; b < B; ++b) { ptrs[b] = Xcat + off * (*m); nc[b] = as_ll(ncb + b); off += nc[b]; }
-    *status = sharp_SHARP_unlimited_view(ptrs.data(), nc.data(), B, *m, *ensize_K, *N_cluster, *minN, *maxN, *rN_seed, pred, &info[0],
+    const DenseList L(Xcat, *nblocks, ncb, *m, status);
+    if (!L.ok) return;
+    *status = sharp_SHARP_unlimited_view(L.ptrs.data(), L.nc.data(), *nblocks, *m, *ensize_K, *N_cluster, *minN, *maxN, *rN_seed, pred, &info[0],
                                          &info[1], (*want & 1) ? viE : nullptr);
 }
 /* arms the device-side view reduction for the NEXT sharp_C_SHARP_unlimited* call (sharp_unlimited_view_dim; R/SHARP_unlimited.R:216-228): its viE
@@ -168,13 +225,9 @@ void sharp_C_last_decisions(double *rows, int *cap_rows, int *n_rows, int *statu
 /* the same on several GPUs (sharp_SHARP_unlimited_multi): devices = integer vector of device indices, block b on devices[b mod ndev] */
 void sharp_C_SHARP_unlimited_multi(double *Xcat, int *nblocks, double *ncb, int *m, int *ensize_K, int *N_cluster, int *minN, int *maxN,
                                    double *rN_seed, int *devices, int *ndevices, int *pred, double *viE, int *info, int *want, int *status) {
-    const int B = *nblocks;
-    if (B < 1) { sharp::set_error("No expression data is provided!"); *status = SHARP_ERR_ARG; return; }
-    std::vector<const double *> ptrs(static_cast<size_t>(B));
-    std::vector<long long> nc(static_cast<size_t>(B));
-    long long off = 0;
-    for (int b = 0; b < B; ++b) { ptrs[b] = Xcat + off * (*m); nc[b] = as_ll(ncb + b); off += nc[b]; }
-    *status = sharp_SHARP_unlimited_multi(ptrs.data(), nc.data(), B, *m, *ensize_K, *N_cluster, *minN, *maxN, *rN_seed, devices, *ndevices,
+    const DenseList L(Xcat, *nblocks, ncb, *m, status);
+    if (!L.ok) return;
+    *status = sharp_SHARP_unlimited_multi(L.ptrs.data(), L.nc.data(), *nblocks, *m, *ensize_K, *N_cluster, *minN, *maxN, *rN_seed, devices, *ndevices,
                                           pred, &info[0], &info[1], (*want & 1) ? viE : nullptr);
 }
 /* a list of dgCMatrix blocks (R/SHARP_unlimited.R:125-135 hands each block to SHARP() as it is; R/SHARP.R:343-345,579 take a dgCMatrix):
@@ -183,32 +236,18 @@ void sharp_C_SHARP_unlimited_multi(double *Xcat, int *nblocks, double *ncb, int 
 void sharp_C_SHARP_unlimited_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, int *ensize_K, int *N_cluster,
                                  int *minN, int *maxN, double *rN_seed, int *devices, int *ndevices, int *pred, double *viE, int *info,
                                  int *want, int *status) {
-    const int B = *nblocks;
-    if (B < 1) { sharp::set_error("No expression data is provided!"); *status = SHARP_ERR_ARG; return; }
-    std::vector<const int *> cp(static_cast<size_t>(B)), ri(static_cast<size_t>(B));
-    std::vector<const double *> vx(static_cast<size_t>(B));
-    std::vector<long long> nc(static_cast<size_t>(B));
-    long long poff = 0, eoff = 0;
-    for (int b = 0; b < B; ++b) {
-        nc[b] = as_ll(ncb + b);
-        cp[b] = pcat + poff; ri[b] = icat + eoff; vx[b] = xcat + eoff;
-        eoff += static_cast<long long>(cp[b][nc[b]]) - cp[b][0];
-        poff += nc[b] + 1;
-    }
-    *status = sharp_SHARP_unlimited_csc_multi(cp.data(), ri.data(), vx.data(), nc.data(), B, *m, *ensize_K, *N_cluster, *minN, *maxN, *rN_seed,
+    const CscList L(pcat, icat, xcat, *nblocks, ncb, status);
+    if (!L.ok) return;
+    *status = sharp_SHARP_unlimited_csc_multi(L.cp.data(), L.ri.data(), L.vx.data(), L.nc.data(), *nblocks, *m, *ensize_K, *N_cluster, *minN, *maxN, *rN_seed,
                                               *ndevices > 0 ? devices : nullptr, *ndevices, pred, &info[0], &info[1], (*want & 1) ? viE : nullptr);
 }
 /* SHARP_unlimited2 (R/SHARP_unlimited2.R:29-292); same block layout */
 void sharp_C_SHARP_unlimited2(double *Xcat, int *nblocks, double *ncb, int *m, int *ensize_K, int *reduced_ndim, int *partition_ncells,
                               int *hmethod, int *N_cluster, int *enpN, int *indN, int *minN, int *maxN, double *sil_thre,
                               double *height_Ntimes, int *flag, double *rN_seed, int *pred, double *viE, int *info, int *want, int *status) {
-    const int B = *nblocks;
-    if (B < 1) { sharp::set_error("No expression data is provided!"); *status = SHARP_ERR_ARG; return; }
-    std::vector<const double *> ptrs(static_cast<size_t>(B));
-    std::vector<long long> nc(static_cast<size_t>(B));
-    long long off = 0;
-    for (int b = 0; b < B; ++b) { ptrs[b] = Xcat + off * (*m); nc[b] = as_ll(ncb + b); off += nc[b]; }
-    *status = sharp_SHARP_unlimited2(ptrs.data(), nc.data(), B, *m, *ensize_K, *reduced_ndim, *partition_ncells, *hmethod, *N_cluster, *enpN,
+    const DenseList L(Xcat, *nblocks, ncb, *m, status);
+    if (!L.ok) return;
+    *status = sharp_SHARP_unlimited2(L.ptrs.data(), L.nc.data(), *nblocks, *m, *ensize_K, *reduced_ndim, *partition_ncells, *hmethod, *N_cluster, *enpN,
                                      *indN, *minN, *maxN, *sil_thre, *height_Ntimes, *flag, *rN_seed, pred, &info[0], &info[1],
                                      (*want & 1) ? viE : nullptr);
 }
@@ -359,40 +398,24 @@ void sharp_C_neighbor_ranks(double *X, double *n, int *d, int *K, int *index, in
 
 /* Louvain on a graph or on neighbour lists (sharp_louvain_graph, sharp_louvain_neighbors, sharp_louvain_modularity): row_ptr and n as
  * double; levels: level_cap rows of (n, communities, rounds, modularity) */
-static void louvain_levels_out(int status, int nl, const std::vector<long long> &ln, const std::vector<long long> &lc, const std::vector<int> &lr,
-                               const std::vector<double> &lq, double *levels) {
-    if (status != 0) return;
-    for (int l = 0; l < nl; ++l) {
-        levels[4 * l] = static_cast<double>(ln[l]);
-        levels[4 * l + 1] = static_cast<double>(lc[l]);
-        levels[4 * l + 2] = static_cast<double>(lr[l]);
-        levels[4 * l + 3] = lq[l];
-    }
-}
 void sharp_C_louvain_graph(double *row_ptr, int *col, double *val, double *n, double *resolution, double *tol, int *max_levels, int *max_rounds,
                            int *max_fails, double *seed, int *membership, int *level_cap, double *levels, int *n_levels, int *want_levels,
                            int *level_membership, int *status) {
     const long long nn = as_ll(n);
     const std::vector<long long> rp = row_ptr_ll(row_ptr, nn);
-    const size_t cap = *level_cap > 0 ? static_cast<size_t>(*level_cap) : 1;
-    std::vector<long long> ln(cap), lc(cap);
-    std::vector<int> lr(cap);
-    std::vector<double> lq(cap);
+    LevelsOut o(*level_cap, false);
     *status = sharp_louvain_graph(rp.data(), col, val, nn, *resolution, *tol, *max_levels, *max_rounds, *max_fails, *seed, membership, *level_cap,
-                                  ln.data(), lc.data(), lr.data(), lq.data(), n_levels, *want_levels ? level_membership : nullptr);
-    louvain_levels_out(*status, *n_levels, ln, lc, lr, lq, levels);
+                                  o.ln.data(), o.lc.data(), o.lr.data(), o.lq.data(), n_levels, *want_levels ? level_membership : nullptr);
+    o.write(*status, *n_levels, levels);
 }
 void sharp_C_louvain_neighbors(int *index, double *distance, double *n, int *K, int *squared, double *resolution, double *tol, int *max_levels,
                                int *max_rounds, int *max_fails, double *seed, int *membership, int *level_cap, double *levels, int *n_levels,
                                int *want_levels, int *level_membership, int *status) {
-    const size_t cap = *level_cap > 0 ? static_cast<size_t>(*level_cap) : 1;
-    std::vector<long long> ln(cap), lc(cap);
-    std::vector<int> lr(cap);
-    std::vector<double> lq(cap);
+    LevelsOut o(*level_cap, false);
     *status = sharp_louvain_neighbors(index, distance, as_ll(n), *K, *squared, *resolution, *tol, *max_levels, *max_rounds, *max_fails, *seed,
-                                      membership, *level_cap, ln.data(), lc.data(), lr.data(), lq.data(), n_levels,
+                                      membership, *level_cap, o.ln.data(), o.lc.data(), o.lr.data(), o.lq.data(), n_levels,
                                       *want_levels ? level_membership : nullptr);
-    louvain_levels_out(*status, *n_levels, ln, lc, lr, lq, levels);
+    o.write(*status, *n_levels, levels);
 }
 void sharp_C_louvain_modularity(double *row_ptr, int *col, double *val, double *n, int *membership, double *resolution, double *Q, int *status) {
     const long long nn = as_ll(n);
@@ -402,32 +425,12 @@ void sharp_C_louvain_modularity(double *row_ptr, int *col, double *val, double *
 
 /* Leiden (sharp_leiden_graph, sharp_leiden_neighbors, sharp_leiden_snn): as the Louvain entries; levels: level_cap rows of (n,
  * communities, sub-communities, rounds, refine rounds, modularity) */
-struct LeidenLevelsOut {
-    std::vector<long long> ln, lc, ls;
-    std::vector<int> lr, lf;
-    std::vector<double> lq;
-    explicit LeidenLevelsOut(int level_cap) {
-        const size_t cap = level_cap > 0 ? static_cast<size_t>(level_cap) : 1;
-        ln.resize(cap); lc.resize(cap); ls.resize(cap); lr.resize(cap); lf.resize(cap); lq.resize(cap);
-    }
-    void write(int status, int nl, double *levels) const {
-        if (status != 0) return;
-        for (int l = 0; l < nl; ++l) {
-            levels[6 * l] = static_cast<double>(ln[l]);
-            levels[6 * l + 1] = static_cast<double>(lc[l]);
-            levels[6 * l + 2] = static_cast<double>(ls[l]);
-            levels[6 * l + 3] = static_cast<double>(lr[l]);
-            levels[6 * l + 4] = static_cast<double>(lf[l]);
-            levels[6 * l + 5] = lq[l];
-        }
-    }
-};
 void sharp_C_leiden_graph(double *row_ptr, int *col, double *val, double *n, double *resolution, double *tol, int *max_levels, int *max_rounds,
                           int *max_fails, int *max_refine_rounds, double *seed, int *membership, double *modularity, int *level_cap, double *levels,
                           int *n_levels, int *want_levels, int *level_membership, int *status) {
     const long long nn = as_ll(n);
     const std::vector<long long> rp = row_ptr_ll(row_ptr, nn);
-    LeidenLevelsOut o(*level_cap);
+    LevelsOut o(*level_cap, true);
     *status = sharp_leiden_graph(rp.data(), col, val, nn, *resolution, *tol, *max_levels, *max_rounds, *max_fails, *max_refine_rounds, *seed,
                                  membership, modularity, *level_cap, o.ln.data(), o.lc.data(), o.ls.data(), o.lr.data(), o.lf.data(), o.lq.data(),
                                  n_levels, *want_levels ? level_membership : nullptr);
@@ -436,7 +439,7 @@ void sharp_C_leiden_graph(double *row_ptr, int *col, double *val, double *n, dou
 void sharp_C_leiden_neighbors(int *index, double *distance, double *n, int *K, int *squared, double *resolution, double *tol, int *max_levels,
                               int *max_rounds, int *max_fails, int *max_refine_rounds, double *seed, int *membership, double *modularity,
                               int *level_cap, double *levels, int *n_levels, int *want_levels, int *level_membership, int *status) {
-    LeidenLevelsOut o(*level_cap);
+    LevelsOut o(*level_cap, true);
     *status = sharp_leiden_neighbors(index, distance, as_ll(n), *K, *squared, *resolution, *tol, *max_levels, *max_rounds, *max_fails,
                                      *max_refine_rounds, *seed, membership, modularity, *level_cap, o.ln.data(), o.lc.data(), o.ls.data(),
                                      o.lr.data(), o.lf.data(), o.lq.data(), n_levels, *want_levels ? level_membership : nullptr);
@@ -445,7 +448,7 @@ void sharp_C_leiden_neighbors(int *index, double *distance, double *n, int *K, i
 void sharp_C_leiden_snn(int *index, double *n, int *K, double *prune, double *resolution, double *tol, int *max_levels, int *max_rounds,
                         int *max_fails, int *max_refine_rounds, double *seed, int *membership, double *modularity, int *level_cap, double *levels,
                         int *n_levels, int *want_levels, int *level_membership, int *status) {
-    LeidenLevelsOut o(*level_cap);
+    LevelsOut o(*level_cap, true);
     *status = sharp_leiden_snn(index, as_ll(n), *K, *prune, *resolution, *tol, *max_levels, *max_rounds, *max_fails, *max_refine_rounds, *seed,
                                membership, modularity, *level_cap, o.ln.data(), o.lc.data(), o.ls.data(), o.lr.data(), o.lf.data(), o.lq.data(),
                                n_levels, *want_levels ? level_membership : nullptr);
@@ -469,43 +472,11 @@ void sharp_C_snn_graph(int *index, double *n, int *K, double *prune, double *cap
 void sharp_C_louvain_snn(int *index, double *n, int *K, double *prune, double *resolution, double *tol, int *max_levels, int *max_rounds,
                          int *max_fails, double *seed, int *membership, int *level_cap, double *levels, int *n_levels, int *want_levels,
                          int *level_membership, int *status) {
-    const size_t cap = *level_cap > 0 ? static_cast<size_t>(*level_cap) : 1;
-    std::vector<long long> ln(cap), lc(cap);
-    std::vector<int> lr(cap);
-    std::vector<double> lq(cap);
+    LevelsOut o(*level_cap, false);
     *status = sharp_louvain_snn(index, as_ll(n), *K, *prune, *resolution, *tol, *max_levels, *max_rounds, *max_fails, *seed, membership,
-                                *level_cap, ln.data(), lc.data(), lr.data(), lq.data(), n_levels, *want_levels ? level_membership : nullptr);
-    louvain_levels_out(*status, *n_levels, ln, lc, lr, lq, levels);
+                                *level_cap, o.ln.data(), o.lc.data(), o.lr.data(), o.lq.data(), n_levels, *want_levels ? level_membership : nullptr);
+    o.write(*status, *n_levels, levels);
 }
-
-}  // extern "C"
-
-namespace {
-
-/* a list of dgCMatrix blocks laid out as sharp_C_SHARP_unlimited_csc takes it, as the pointer lists of the plain entries */
-struct CscList {
-    std::vector<const int *> cp, ri;
-    std::vector<const double *> vx;
-    std::vector<long long> nc;
-    bool ok = false;
-    CscList(int *pcat, int *icat, double *xcat, int B, double *ncb, int *status) {
-        if (B < 1) { sharp::set_error("No expression data is provided!"); *status = SHARP_ERR_ARG; return; }
-        cp.resize(B); ri.resize(B); vx.resize(B); nc.resize(B);
-        long long poff = 0, eoff = 0;
-        for (int b = 0; b < B; ++b) {
-            nc[b] = as_ll(ncb + b);
-            if (nc[b] < 0) { sharp::set_error("a block with a negative number of cells"); *status = SHARP_ERR_ARG; return; }
-            cp[b] = pcat + poff; ri[b] = icat + eoff; vx[b] = xcat + eoff;
-            eoff += static_cast<long long>(cp[b][nc[b]]) - cp[b][0];
-            poff += nc[b] + 1;
-        }
-        ok = true;
-    }
-};
-
-}  // namespace
-
-extern "C" {
 
 /* The truncated PCA of sparse expression blocks: the plain entries' bits */
 void sharp_C_expr_pca_csc(int *pcat, int *icat, double *xcat, int *nblocks, double *ncb, int *m, int *n_components, int *oversample,

@@ -1,8 +1,10 @@
-// graph.hpp -- what the neighbour-graph stages share: the CSR types, the launch-grid, butterfly and hash helpers, the
-// fixed-order reduction, the rocprim calls behind plain host functions, the "unsorted (row * n + col, value) entries -> CSR" builder,
-// the wave / workgroup / dense row classes, iota and the reverse-list sort.  t-SNE's P (tsne.hip), UMAP's fuzzy graph (umap.hip),
-// Louvain's levels (louvain.hip), the SNN graph (snn.hip) and NN-descent (knn_descent.hip) are built from these.  The rocprim wrappers
-// are declared here and defined in graph_prim.hpp, which the files that sort or scan include.
+// graph.hpp -- what the neighbour-graph stages share: the CSR types and the upload of a caller's checked CSR, the
+// launch-grid, butterfly and hash helpers, the fixed-order reduction, the rocprim calls behind plain host functions, the "unsorted
+// (row * n + col, value) entries -> CSR" builder, the wave / workgroup / dense row classes, iota and the reverse-list sort.  t-SNE's P
+// (tsne.hip), UMAP's fuzzy graph (umap.hip), Louvain's levels (louvain.hip), the SNN graph (snn.hip) and NN-descent (knn_descent.hip)
+// are built from these; csr_to_device serves umap_epochs (umap.hip), the Lanczos solvers (spectral_dev.hpp) and Louvain / Leiden on a
+// caller's graph (louvain.hip).  How lists become a graph on the device is graph_source.hpp's.  The rocprim wrappers are declared here
+// and defined in graph_prim.hpp, which the files that sort or scan include.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -26,6 +28,22 @@ struct Csr {
 struct Graph : Csr<double> {
     double wmax = 0.0;
 };
+// a caller's CSR (host; n rows, row_ptr[n] entries) that its entry has checked, placed in G on ctx().stream; val may be null (the
+// pattern alone); wmax: the largest weight, found by that check.  A graph without an entry keeps one slot per array.
+SHARP_LOCAL inline void csr_to_device(const long long *row_ptr, const int *col, const double *val, long long n, double wmax, Graph &G) {
+    G.n = n;
+    G.nnz = row_ptr[n];
+    G.wmax = wmax;
+    const size_t slots = static_cast<size_t>(std::max<long long>(G.nnz, 1));
+    G.row_ptr.alloc(n + 1);
+    G.row_ptr.upload(row_ptr, n + 1);
+    G.col.alloc(slots);
+    if (G.nnz) G.col.upload(col, G.nnz);
+    if (val) {
+        G.val.alloc(slots);
+        if (G.nnz) G.val.upload(val, G.nnz);
+    }
+}
 
 // ---- small helpers --------------------------------------------------------------------------------------------------------------------
 // workgroups of `per` items that cover n items (one, doing nothing, for n = 0)

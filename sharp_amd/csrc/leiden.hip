@@ -23,7 +23,7 @@
 #include <string>
 #include <vector>
 
-#include "knn.hpp"
+#include "graph_source.hpp"
 #include "snn.hpp"
 #include "umap.hpp"
 
@@ -313,7 +313,7 @@ int ld_refine(const LouvainGraph &L, const LouvainArgs &a, int max_refine_rounds
 }  // namespace
 
 void leiden_run(LouvainGraph &L0, const LouvainArgs &a, int max_refine_rounds, std::vector<int> &membership, double *Q_out,
-                std::vector<LeidenLevel> &levels, std::vector<int> *level_membership) {
+                std::vector<LouvainLevel> &levels, std::vector<int> *level_membership) {
     Ctx &c = ctx();
     SHARP_REQUIRE(L0.m2 > 0, "leiden: the graph holds no positive weight");
     const long long n0 = L0.n;
@@ -334,7 +334,7 @@ void leiden_run(LouvainGraph &L0, const LouvainArgs &a, int max_refine_rounds, s
             SHARP_HIP_CHECK(hipMemcpyAsync(P, start.p, n * sizeof(int), hipMemcpyDeviceToDevice, c.stream));
         else
             iota(P, n);
-        LeidenLevel rec;
+        LouvainLevel rec;
         rec.n = n;
         rec.q = lv_level(*L, a, lev, P, prop, W, &rec.rounds, &rec.communities);
         if (level_membership) {                            // the rank of P of every input vertex (W.pos: the ranks of P)
@@ -386,38 +386,9 @@ using namespace sharp;
 
 namespace {
 
-struct LevelOut {
-    long long *n, *communities, *sub_communities;
-    int *rounds, *refine_rounds;
-    double *q;
-    int *n_levels, *membership;
-    bool complete() const { return n && communities && sub_communities && rounds && refine_rounds && q && n_levels; }
-};
-
 int refine_rounds_arg(const std::string &w, int max_refine_rounds) {
     SHARP_REQUIRE(max_refine_rounds >= 1 && max_refine_rounds <= kLdMaxRefineRounds, w + ": max_refine_rounds must be in 1 .. 100000");
     return max_refine_rounds;
-}
-
-void run_and_report(const std::string &w, const Graph &G, const LouvainArgs &a, int max_refine_rounds, int *membership, double *modularity,
-                    int level_cap, const LevelOut &o) {
-    LouvainGraph L;
-    louvain_quantise(G, L);
-    std::vector<int> mem, lm;
-    std::vector<LeidenLevel> levels;
-    leiden_run(L, a, max_refine_rounds, mem, modularity, levels, o.membership ? &lm : nullptr);
-    SHARP_REQUIRE(static_cast<int>(levels.size()) <= level_cap, w + ": level_cap is smaller than the number of levels");
-    std::copy(mem.begin(), mem.end(), membership);
-    for (size_t l = 0; l < levels.size(); ++l) {
-        o.n[l] = levels[l].n;
-        o.communities[l] = levels[l].communities;
-        o.sub_communities[l] = levels[l].sub_communities;
-        o.rounds[l] = levels[l].rounds;
-        o.refine_rounds[l] = levels[l].refine_rounds;
-        o.q[l] = levels[l].q;
-    }
-    *o.n_levels = static_cast<int>(levels.size());
-    if (o.membership) std::copy(lm.begin(), lm.end(), o.membership);
 }
 
 }  // namespace
@@ -497,7 +468,7 @@ int sharp_leiden_graph(const long long *row_ptr, const int *col, const double *v
     ctx();
     const std::string w("leiden_graph");
     const LevelOut o{level_n, level_communities, level_sub_communities, level_rounds, level_refine_rounds, level_q, n_levels, level_membership};
-    SHARP_REQUIRE(membership && modularity && o.complete(), w + ": null output");
+    SHARP_REQUIRE(membership && modularity && o.complete(true), w + ": null output");
     const LouvainArgs a = louvain_args(w, resolution, tol, max_levels, max_rounds, max_fails, seed);
     refine_rounds_arg(w, max_refine_rounds);
     SHARP_REQUIRE(level_cap >= max_levels, w + ": level_cap must be at least max_levels");
@@ -516,20 +487,13 @@ int sharp_leiden_neighbors(const int *index, const double *distance, long long n
     const std::string w("leiden_neighbors");
     const LevelOut o{level_n, level_communities, level_sub_communities, level_rounds, level_refine_rounds, level_q, n_levels, level_membership};
     SHARP_REQUIRE(index && distance, w + ": null index / distance");
-    SHARP_REQUIRE(membership && modularity && o.complete(), w + ": null output");
-    SHARP_REQUIRE(n >= 2 && n <= kLvMaxN, w + ": need 2 <= n <= 16777216 rows");
-    SHARP_REQUIRE(K >= 1 && K <= 255 && K <= n - 1, w + ": need 1 <= K <= 255 neighbours per row and K <= n - 1");
+    SHARP_REQUIRE(membership && modularity && o.complete(true), w + ": null output");
+    lv_check_list_shape(w, n, K);
     const LouvainArgs a = louvain_args(w, resolution, tol, max_levels, max_rounds, max_fails, seed);
     refine_rounds_arg(w, max_refine_rounds);
     SHARP_REQUIRE(level_cap >= max_levels, w + ": level_cap must be at least max_levels");
-    DevBuf<int> idx;
-    DevBuf<double> dist;
-    upload_neighbours(w.c_str(), index, distance, n, K, true, idx, dist);
-    if (squared) umap_sqrt_lists(dist, n, K);
     Graph G;
-    umap_graph(idx, dist, n, K, G);
-    idx.release();
-    dist.release();
+    fuzzy_graph_from_lists(w, index, distance, n, K, squared != 0, G);
     run_and_report(w, G, a, max_refine_rounds, membership, modularity, level_cap, o);
     SHARP_API_END
 }
@@ -542,19 +506,14 @@ int sharp_leiden_snn(const int *index, long long n, int K, double prune, double 
     const std::string w("leiden_snn");
     const LevelOut o{level_n, level_communities, level_sub_communities, level_rounds, level_refine_rounds, level_q, n_levels, level_membership};
     SHARP_REQUIRE(index, w + ": null index");
-    SHARP_REQUIRE(membership && modularity && o.complete(), w + ": null output");
+    SHARP_REQUIRE(membership && modularity && o.complete(true), w + ": null output");
     snn_check_args(w, n, K, prune);
     const LouvainArgs a = louvain_args(w, resolution, tol, max_levels, max_rounds, max_fails, seed);
     refine_rounds_arg(w, max_refine_rounds);
     SHARP_REQUIRE(level_cap >= max_levels, w + ": level_cap must be at least max_levels");
     ctx();
     Graph G;
-    {
-        DevBuf<int> idx(static_cast<size_t>(n) * K);
-        idx.upload(index, static_cast<size_t>(n) * K);
-        snn_graph(w, idx, n, K, prune, false, G, nullptr);   // (synchronises: idx leaves scope)
-    }
-    SHARP_REQUIRE(G.nnz >= 1 && G.wmax > 0.0, w + ": the pruned graph holds no positive weight");
+    snn_graph_from_lists(w, index, n, K, prune, G);
     run_and_report(w, G, a, max_refine_rounds, membership, modularity, level_cap, o);
     SHARP_API_END
 }

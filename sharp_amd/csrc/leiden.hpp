@@ -12,18 +12,13 @@
 
 namespace sharp {
 
-struct LeidenLevel {
-    long long n = 0, communities = 0, sub_communities = 0;
-    int rounds = 0, refine_rounds = 0;
-    double q = 0.0;                          // of P, the level's accepted partition
-};
-
 constexpr int kLdMaxRefineRounds = 100000;
 constexpr int kLdRefineRound0 = 1 << 30;     // the refinement's bits are §18's h at the round number 2^30 + r
 
 // rules L1 - L4 on a quantised graph; membership: 1 .. G by decreasing size (host, n values); Q: of that membership on L;
+// levels: louvain.hpp's record, with the sub-communities and the refinement's rounds filled in, q that of the level's P;
 // level_membership (when wanted): levels x n, the 0-based rank of the community P of every input vertex at each level
 void leiden_run(LouvainGraph &L, const LouvainArgs &a, int max_refine_rounds, std::vector<int> &membership, double *Q,
-                std::vector<LeidenLevel> &levels, std::vector<int> *level_membership);
+                std::vector<LouvainLevel> &levels, std::vector<int> *level_membership);
 
 }  // namespace sharp

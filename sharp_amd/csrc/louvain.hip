@@ -29,9 +29,9 @@
 #include <string>
 #include <vector>
 
+#include "graph_source.hpp"
+#include "leiden.hpp"
 #include "snn.hpp"
-#include "knn.hpp"
-#include "umap.hpp"
 
 namespace sharp {
 namespace {
@@ -548,15 +548,7 @@ void lv_upload_float_graph(const std::string &w, const long long *row_ptr, const
             wmax = std::max(wmax, val[e]);
         }
     SHARP_REQUIRE(wmax > 0.0, w + ": the graph holds no positive weight");
-    G.n = n;
-    G.nnz = nnz;
-    G.wmax = wmax;
-    G.row_ptr.alloc(n + 1);
-    G.col.alloc(nnz);
-    G.val.alloc(nnz);
-    G.row_ptr.upload(row_ptr, n + 1);
-    G.col.upload(col, nnz);
-    G.val.upload(val, nnz);
+    csr_to_device(row_ptr, col, val, n, wmax, G);
 }
 
 // an integer-weighted CSR (a level's graph: self-loops allowed) on the device, for the stage entries
@@ -606,32 +598,40 @@ LouvainArgs louvain_args(const std::string &w, double resolution, double tol, in
     return a;
 }
 
-}  // namespace sharp
+void lv_check_list_shape(const std::string &w, long long n, int K) {
+    SHARP_REQUIRE(n >= 2 && n <= kLvMaxN, w + ": need 2 <= n <= 16777216 rows");
+    SHARP_REQUIRE(K >= 1 && K <= 255 && K <= n - 1, w + ": need 1 <= K <= 255 neighbours per row and K <= n - 1");
+}
 
-using namespace sharp;
-
-namespace {
-
-void run_and_report(const std::string &w, const Graph &G, const LouvainArgs &a, int *membership, int level_cap, long long *level_n,
-                    long long *level_communities, int *level_rounds, double *level_q, int *n_levels, int *level_membership) {
+void run_and_report(const std::string &w, const Graph &G, const LouvainArgs &a, int max_refine_rounds, int *membership, double *modularity,
+                    int level_cap, const LevelOut &o) {
     LouvainGraph L;
     louvain_quantise(G, L);
     std::vector<int> mem, lm;
     std::vector<LouvainLevel> levels;
-    louvain_run(L, a, mem, levels, level_membership ? &lm : nullptr);
+    if (modularity)
+        leiden_run(L, a, max_refine_rounds, mem, modularity, levels, o.membership ? &lm : nullptr);
+    else
+        louvain_run(L, a, mem, levels, o.membership ? &lm : nullptr);
     SHARP_REQUIRE(static_cast<int>(levels.size()) <= level_cap, w + ": level_cap is smaller than the number of levels");
     std::copy(mem.begin(), mem.end(), membership);
     for (size_t l = 0; l < levels.size(); ++l) {
-        level_n[l] = levels[l].n;
-        level_communities[l] = levels[l].communities;
-        level_rounds[l] = levels[l].rounds;
-        level_q[l] = levels[l].q;
+        o.n[l] = levels[l].n;
+        o.communities[l] = levels[l].communities;
+        o.rounds[l] = levels[l].rounds;
+        o.q[l] = levels[l].q;
+        if (modularity) {
+            o.sub_communities[l] = levels[l].sub_communities;
+            o.refine_rounds[l] = levels[l].refine_rounds;
+        }
     }
-    *n_levels = static_cast<int>(levels.size());
-    if (level_membership) std::copy(lm.begin(), lm.end(), level_membership);
+    *o.n_levels = static_cast<int>(levels.size());
+    if (o.membership) std::copy(lm.begin(), lm.end(), o.membership);
 }
 
-}  // namespace
+}  // namespace sharp
+
+using namespace sharp;
 
 extern "C" {
 
@@ -751,12 +751,13 @@ int sharp_louvain_graph(const long long *row_ptr, const int *col, const double *
     SHARP_API_BEGIN
     ctx();
     const std::string w("louvain_graph");
-    SHARP_REQUIRE(membership && level_n && level_communities && level_rounds && level_q && n_levels, w + ": null output");
+    const LevelOut o{level_n, level_communities, nullptr, level_rounds, nullptr, level_q, n_levels, level_membership};
+    SHARP_REQUIRE(membership && o.complete(false), w + ": null output");
     const LouvainArgs a = louvain_args(w, resolution, tol, max_levels, max_rounds, max_fails, seed);
     SHARP_REQUIRE(level_cap >= max_levels, w + ": level_cap must be at least max_levels");
     Graph G;
     lv_upload_float_graph(w, row_ptr, col, val, n, G);
-    run_and_report(w, G, a, membership, level_cap, level_n, level_communities, level_rounds, level_q, n_levels, level_membership);
+    run_and_report(w, G, a, 0, membership, nullptr, level_cap, o);
     SHARP_API_END
 }
 
@@ -766,21 +767,15 @@ int sharp_louvain_neighbors(const int *index, const double *distance, long long 
     SHARP_API_BEGIN
     ctx();
     const std::string w("louvain_neighbors");
+    const LevelOut o{level_n, level_communities, nullptr, level_rounds, nullptr, level_q, n_levels, level_membership};
     SHARP_REQUIRE(index && distance, w + ": null index / distance");
-    SHARP_REQUIRE(membership && level_n && level_communities && level_rounds && level_q && n_levels, w + ": null output");
-    SHARP_REQUIRE(n >= 2 && n <= kLvMaxN, w + ": need 2 <= n <= 16777216 rows");
-    SHARP_REQUIRE(K >= 1 && K <= 255 && K <= n - 1, w + ": need 1 <= K <= 255 neighbours per row and K <= n - 1");
+    SHARP_REQUIRE(membership && o.complete(false), w + ": null output");
+    lv_check_list_shape(w, n, K);
     const LouvainArgs a = louvain_args(w, resolution, tol, max_levels, max_rounds, max_fails, seed);
     SHARP_REQUIRE(level_cap >= max_levels, w + ": level_cap must be at least max_levels");
-    DevBuf<int> idx;
-    DevBuf<double> dist;
-    upload_neighbours(w.c_str(), index, distance, n, K, true, idx, dist);
-    if (squared) umap_sqrt_lists(dist, n, K);
     Graph G;
-    umap_graph(idx, dist, n, K, G);
-    idx.release();
-    dist.release();
-    run_and_report(w, G, a, membership, level_cap, level_n, level_communities, level_rounds, level_q, n_levels, level_membership);
+    fuzzy_graph_from_lists(w, index, distance, n, K, squared != 0, G);
+    run_and_report(w, G, a, 0, membership, nullptr, level_cap, o);
     SHARP_API_END
 }
 
@@ -789,20 +784,16 @@ int sharp_louvain_snn(const int *index, long long n, int K, double prune, double
                       int *level_rounds, double *level_q, int *n_levels, int *level_membership) {
     SHARP_API_BEGIN
     const std::string w("louvain_snn");
+    const LevelOut o{level_n, level_communities, nullptr, level_rounds, nullptr, level_q, n_levels, level_membership};
     SHARP_REQUIRE(index, w + ": null index");
-    SHARP_REQUIRE(membership && level_n && level_communities && level_rounds && level_q && n_levels, w + ": null output");
+    SHARP_REQUIRE(membership && o.complete(false), w + ": null output");
     snn_check_args(w, n, K, prune);
     const LouvainArgs a = louvain_args(w, resolution, tol, max_levels, max_rounds, max_fails, seed);
     SHARP_REQUIRE(level_cap >= max_levels, w + ": level_cap must be at least max_levels");
     ctx();
     Graph G;
-    {
-        DevBuf<int> idx(static_cast<size_t>(n) * K);
-        idx.upload(index, static_cast<size_t>(n) * K);
-        snn_graph(w, idx, n, K, prune, false, G, nullptr);   // (synchronises: idx leaves scope)
-    }
-    SHARP_REQUIRE(G.nnz >= 1 && G.wmax > 0.0, w + ": the pruned graph holds no positive weight");
-    run_and_report(w, G, a, membership, level_cap, level_n, level_communities, level_rounds, level_q, n_levels, level_membership);
+    snn_graph_from_lists(w, index, n, K, prune, G);
+    run_and_report(w, G, a, 0, membership, nullptr, level_cap, o);
     SHARP_API_END
 }
 

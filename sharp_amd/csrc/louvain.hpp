@@ -3,7 +3,8 @@
 // weights is an exact int64 sum whatever the order of the atomics; a round of local moving works from the round's start state and lets
 // a community either lose or gain members (one hashed bit per community and round, rule 2); a round is kept when the modularity, summed
 // in a fixed order, rises by more than tol (rule 3); the communities become the next level's vertices (rule 4).  The graph is what
-// umap_graph or snn_graph leave on the device (graph.hpp's Graph), or any symmetric CSR.  The C ABI entries (sharp_louvain_*, include/sharp_hip.h) wrap these.
+// graph_source.hpp's fuzzy_graph_from_lists or snn_graph_from_lists leave on the device (graph.hpp's Graph), or any symmetric CSR.
+// The C ABI entries (sharp_louvain_*, include/sharp_hip.h) wrap these.
 #pragma once
 #include <string>
 #include <vector>
@@ -25,10 +26,23 @@ struct LouvainArgs {
     unsigned long long seed = 10;
 };
 
+// what a level of Louvain or of Leiden (leiden.hpp) did; sub_communities and refine_rounds are Leiden's and stay 0 for Louvain
 struct LouvainLevel {
-    long long n = 0, communities = 0;
-    int rounds = 0;
-    double q = 0.0;
+    long long n = 0, communities = 0, sub_communities = 0;
+    int rounds = 0, refine_rounds = 0;
+    double q = 0.0;                          // of the level's accepted partition
+};
+
+// where a C ABI entry wants the levels (host, level_cap values each; membership: levels x n, or null).  sub_communities and
+// refine_rounds are null in the Louvain entries.
+struct LevelOut {
+    long long *n, *communities, *sub_communities;
+    int *rounds, *refine_rounds;
+    double *q;
+    int *n_levels, *membership;
+    bool complete(bool leiden) const {
+        return n && communities && rounds && q && n_levels && (!leiden || (sub_communities && refine_rounds));
+    }
 };
 
 constexpr long long kLvMaxN = 1ll << 24;
@@ -81,5 +95,11 @@ SHARP_LOCAL void lv_upload_float_graph(const std::string &w, const long long *ro
 SHARP_LOCAL void lv_upload_int_graph(const std::string &w, const long long *row_ptr, const int *col, const long long *q, long long n, LouvainGraph &L);
 SHARP_LOCAL void lv_upload_comm(const std::string &w, const int *comm, long long n, DevBuf<int> &d);
 SHARP_LOCAL LouvainArgs louvain_args(const std::string &w, double resolution, double tol, int max_levels, int max_rounds, int max_fails, double seed);
+// the shape of the neighbour lists that louvain_neighbors and leiden_neighbors take
+SHARP_LOCAL void lv_check_list_shape(const std::string &w, long long n, int K);
+// what the six sharp_{louvain,leiden}_{graph,neighbors,snn} entries do behind their graph: quantise G, run, refuse a level_cap below the
+// number of levels, copy out.  modularity null (and max_refine_rounds 0): louvain_run; else leiden_run, which writes it.
+SHARP_LOCAL void run_and_report(const std::string &w, const Graph &G, const LouvainArgs &a, int max_refine_rounds, int *membership,
+                                double *modularity, int level_cap, const LevelOut &out);
 
 }  // namespace sharp

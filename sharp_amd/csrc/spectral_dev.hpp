@@ -129,11 +129,9 @@ void upload_csr(const char *who, const long long *row_ptr, const int *col, const
     SHARP_REQUIRE(row_ptr[0] == 0, w + ": row_ptr must start at 0");
     for (long long i = 0; i < n; ++i)
         SHARP_REQUIRE(row_ptr[i] <= row_ptr[i + 1] && row_ptr[i + 1] - row_ptr[i] <= n, w + ": row_ptr is not monotone, or a row holds more than n entries");
-    G.n = n;
-    G.nnz = row_ptr[n];
-    for (long long e = 0; e < G.nnz; ++e) SHARP_REQUIRE(col[e] >= 0 && col[e] < n, w + ": a column index out of range");
-    if (val) {
-        double wmax = 0.0;
+    for (long long e = 0; e < row_ptr[n]; ++e) SHARP_REQUIRE(col[e] >= 0 && col[e] < n, w + ": a column index out of range");
+    double wmax = 0.0;
+    if (val)
         for (long long i = 0; i < n; ++i) {
             double deg = 0.0;
             for (long long e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
@@ -143,16 +141,7 @@ void upload_csr(const char *who, const long long *row_ptr, const int *col, const
             }
             SHARP_REQUIRE(row_ptr[i] == row_ptr[i + 1] || (deg > 0.0 && deg <= DBL_MAX), w + ": a row whose weights sum to 0 or overflow");
         }
-        G.wmax = wmax;
-    }
-    G.row_ptr.alloc(n + 1);
-    G.row_ptr.upload(row_ptr, n + 1);
-    G.col.alloc(std::max<long long>(G.nnz, 1));
-    if (G.nnz) G.col.upload(col, G.nnz);
-    if (val) {
-        G.val.alloc(std::max<long long>(G.nnz, 1));
-        if (G.nnz) G.val.upload(val, G.nnz);
-    }
+    csr_to_device(row_ptr, col, val, n, wmax, G);
 }
 
 }  // namespace

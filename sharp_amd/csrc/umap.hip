@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "graph_source.hpp"
 #include "knn.hpp"
 #include "prepare.hpp"
 #include "rrng.hpp"
@@ -325,8 +326,6 @@ using namespace sharp;
 
 namespace {
 
-void sqrt_lists(DevBuf<double> &dist, long long n, int K) { umap_sqrt_lists(dist, n, K); }
-
 struct UmapArgs {
     int dims, n_epochs;
     double learning_rate, min_dist, spread;
@@ -440,13 +439,6 @@ void check_lists(const int *index, const double *distance, long long n, int K, c
     SHARP_REQUIRE(K <= n - 1, w + ": K neighbours per row need K <= n - 1");
 }
 
-// the caller's lists on the device, validated as sharp_tsne_neighbors validates them, as Euclidean distances
-void upload_lists(const char *who, const int *index, const double *distance, long long n, int K, bool squared, DevBuf<int> &idx,
-                  DevBuf<double> &dist) {
-    upload_neighbours(who, index, distance, n, K, true, idx, dist);   // (true: nothing is squared there)
-    if (squared) sqrt_lists(dist, n, K);
-}
-
 }  // namespace
 
 extern "C" {
@@ -483,7 +475,7 @@ int sharp_umap(const double *X, long long n, int d, long long ld, int n_neighbor
     DevBuf<int> idx;
     DevBuf<double> dist;
     knn_self("umap", Xp.p, n, dp, K, idx, dist);
-    sqrt_lists(dist, n, K);
+    umap_sqrt_lists(dist, n, K);
     if (nn_index) {
         idx.download(nn_index, static_cast<size_t>(n) * K);
         dist.download(nn_distance, static_cast<size_t>(n) * K);
@@ -505,7 +497,7 @@ int sharp_umap_neighbors(const int *index, const double *distance, long long n, 
     SHARP_REQUIRE(init != 0, "umap_neighbors: init = \"pca\" needs the data; give \"random\" or a matrix");
     DevBuf<int> idx;
     DevBuf<double> dist;
-    upload_lists("umap_neighbors", index, distance, n, K, squared != 0, idx, dist);
+    lists_to_device("umap_neighbors", index, distance, n, K, squared != 0, idx, dist);
     run_from_lists(idx, dist, n, K, nullptr, 0, u, Y);
     SHARP_API_END
 }
@@ -518,7 +510,7 @@ int sharp_umap_graph(const int *index, const double *distance, long long n, int 
     SHARP_REQUIRE(row_ptr && col && val && nnz && rho && sigma, "sharp_umap_graph: null output");
     DevBuf<int> idx;
     DevBuf<double> dist, drho, dsigma;
-    upload_lists("sharp_umap_graph", index, distance, n, K, squared != 0, idx, dist);
+    lists_to_device("sharp_umap_graph", index, distance, n, K, squared != 0, idx, dist);
     UmapGraph G;
     umap_graph(idx, dist, n, K, G, &drho, &dsigma);
     *nnz = G.nnz;
@@ -539,26 +531,18 @@ int sharp_umap_epochs(const long long *row_ptr, const int *col, const double *va
     SHARP_REQUIRE(dims >= 1 && dims <= 3, "umap: n_components must be 1, 2 or 3");
     SHARP_REQUIRE(std::isfinite(seed) && std::fabs(seed) < 9.0e18, "umap: seed must be a finite integer");
     SHARP_REQUIRE(row_ptr[0] == 0 && row_ptr[n] >= 1, "sharp_umap_epochs: row_ptr must run from 0 to nnz >= 1");
-    UmapGraph G;
-    G.n = n;
-    G.nnz = row_ptr[n];
     for (long long i = 0; i < n; ++i)
         SHARP_REQUIRE(row_ptr[i] <= row_ptr[i + 1] && row_ptr[i + 1] - row_ptr[i] <= n, "sharp_umap_epochs: row_ptr is not monotone, or a row holds more than n entries");
     double wmax = 0.0;
-    for (long long e = 0; e < G.nnz; ++e) {
+    for (long long e = 0; e < row_ptr[n]; ++e) {
         SHARP_REQUIRE(col[e] >= 0 && col[e] < n, "sharp_umap_epochs: a column index out of range");
         SHARP_REQUIRE(val[e] >= 0.0 && val[e] <= DBL_MAX, "sharp_umap_epochs: a weight that is NA / NaN / Inf or negative");
         wmax = std::max(wmax, val[e]);
     }
-    G.wmax = wmax;
     const size_t ne = static_cast<size_t>(n) * dims;
     for (size_t e = 0; e < ne; ++e) SHARP_REQUIRE(std::isfinite(Y[e]), "sharp_umap_epochs: Y holds NA / NaN / Inf");
-    G.row_ptr.alloc(n + 1);
-    G.row_ptr.upload(row_ptr, n + 1);
-    G.col.alloc(G.nnz);
-    G.val.alloc(G.nnz);
-    G.col.upload(col, G.nnz);
-    G.val.upload(val, G.nnz);
+    UmapGraph G;
+    csr_to_device(row_ptr, col, val, n, wmax, G);
     DevBuf<double> dY(ne);
     dY.upload(Y, ne);
     umap_epochs(G, dY.p, dims, n_epochs, ep0, ep1, learning_rate, a, b, negative_sample_rate, repulsion_strength,

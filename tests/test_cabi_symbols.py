@@ -78,6 +78,23 @@ def test_dotc_convention_without_a_device(so):
     assert st[0] != 0 and h[0] == 0
 
 
+def test_dotc_unlimited_csc_refuses_a_negative_block_size(so):
+    """sharp_C_SHARP_unlimited_csc lays its blocks out from ncb: a negative count is refused by name before a column pointer is read
+    at that offset.  No device is involved."""
+    one_int = lambda v=0: (C.c_int * 1)(v)                       # noqa: E731
+    one_dbl = lambda v=0.0: (C.c_double * 1)(v)                  # noqa: E731
+    st = one_int(0)
+    so.sharp_C_SHARP_unlimited_csc.restype = None
+    so.sharp_C_SHARP_unlimited_csc(one_int(), one_int(), one_dbl(), one_int(1), one_dbl(-1.0), one_int(1), one_int(3), one_int(), one_int(),
+                                   one_int(), one_dbl(7.0), one_int(), one_int(0), one_int(), one_dbl(), (C.c_int * 2)(0, 0), one_int(0), st)
+    assert st[0] == 2                                            # SHARP_ERR_ARG
+    buf = C.create_string_buffer(b" " * 255)
+    ln = one_int(256)
+    so.sharp_C_last_error.restype = None
+    so.sharp_C_last_error((C.c_char_p * 1)(C.addressof(buf)), ln)
+    assert b"negative number of cells" in buf.value
+
+
 def test_python_package_has_no_cpu_fallback():
     import torch
 

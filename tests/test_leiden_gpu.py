@@ -414,7 +414,7 @@ def test_refusals_by_message(sa):
     n = len(rp) - 1
 
     def call(values, resolution=1.0, max_refine_rounds=200, max_rounds=200):
-        o = community._LeidenOut(n, 20, False)
+        o = community._Out(n, 20, False, True)
         return lib().sharp_leiden_graph(i64(rp), i32(col), f64(values), n, resolution, 1e-7, 20, max_rounds, 4, max_refine_rounds, 10.0, *o.args())
 
     assert call(val) == 0
