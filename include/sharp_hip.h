@@ -386,6 +386,10 @@ int sharp_tsne_knn(const double *X, long long n, int d, long long ld, int K, int
 int sharp_tsne_affinities(const double *X, long long n, int d, long long ld, double perplexity, long long cap, long long *row_ptr, int *col,
                           double *val, long long *nnz);
 int sharp_tsne_gradient(const long long *row_ptr, const int *col, const double *val, long long n, int dims, const double *Y, double *dY);
+/* The host eigensolver behind _prepare's PCA, expression_pca's and diffmap's Rayleigh-Ritz step (Householder tridiagonalisation +
+ * implicit QL), on its own (tests); needs no device.  A: d x d row-major, symmetric (the lower triangle is what is read).  w (d): the
+ * eigenvalues ascending; V (d x d row-major): their eigenvectors as columns.  A matrix with a NaN is refused ("did not converge"). */
+int sharp_symmetric_eigen(int d, const double *A, double *w, double *V);
 /* sharp_tsne with bhtsne's Barnes-Hut repulsion (DESIGN.md §10 "Barnes-Hut"): theta is honoured.  0 < theta <= 1: a quadtree (octree
  * in 3-D) of Y rebuilt at every gradient evaluation, O(n log n) work per iteration; theta == 0: exactly sharp_tsne; theta outside
  * [0, 1] or not finite: "Incorrect theta." (SHARP_ERR_ARG).  Same arguments and outputs as sharp_tsne; bitwise reproducible on one GPU. */

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void project_kernel(const double *__restrict__
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // host symmetric eigensolver: Householder tridiagonalisation + implicit QL (the EISPACK tred2 / tql2 pair); V (n x n, row-major) holds
-// the matrix on entry and the eigenvectors (columns) on exit, w the eigenvalues in ascending order
+// the matrix on entry and the eigenvectors (columns) on exit, w their eigenvalues in the order QL leaves them (callers sort)
 // ---------------------------------------------------------------------------------------------------------------------------
 void tred2(int n, std::vector<double> &V, std::vector<double> &d, std::vector<double> &e) {
     auto A = [&](int i, int j) -> double & { return V[static_cast<size_t>(i) * n + j]; };
@@ -167,7 +167,7 @@ void tql2(const char *who, int n, std::vector<double> &V, std::vector<double> &d
                 p = -s * s2 * c3 * el1 * e[l] / dl1;
                 e[l] = s * p;
                 d[l] = c * p;
-            } while (std::fabs(e[l]) > eps * tst1 && ++guard < 60);
+            } while (!(std::fabs(e[l]) <= eps * tst1) && ++guard < 60);   // (a NaN keeps iterating and is refused below)
             SHARP_REQUIRE(guard < 60, std::string(who) + ": the PCA eigensolver did not converge (non-finite input?)");
         }
         d[l] += f;
@@ -310,3 +310,27 @@ void prepare_input(const char *who, const double *X, long long n, int d, long lo
 }
 
 }  // namespace sharp
+
+using namespace sharp;
+
+extern "C" {
+
+/* Test entry: symmetric_eigen on a host matrix (include/sharp_hip.h); no device is touched. */
+int sharp_symmetric_eigen(int d, const double *A, double *w, double *V) {
+    SHARP_API_BEGIN
+    SHARP_REQUIRE(d >= 1 && A && w && V, "sharp_symmetric_eigen: need d >= 1 and A, w, V");
+    const size_t dd = static_cast<size_t>(d) * d;
+    std::vector<double> M(A, A + dd), lam;
+    symmetric_eigen("sharp_symmetric_eigen", d, M, lam);
+    // symmetric_eigen leaves the pairs in the solver's order: ascending here, ties in that order
+    std::vector<int> ord(d);
+    for (int i = 0; i < d; ++i) ord[i] = i;
+    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return lam[a] < lam[b]; });
+    for (int j = 0; j < d; ++j) {
+        w[j] = lam[ord[j]];
+        for (int i = 0; i < d; ++i) V[static_cast<size_t>(i) * d + j] = M[static_cast<size_t>(i) * d + ord[j]];
+    }
+    SHARP_API_END
+}
+
+}  // extern "C"
